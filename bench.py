@@ -5,10 +5,13 @@ segmentation + disparity network on synthetic S-ROSeS-shaped 512x256 (WxH) batch
   python bench.py --gpus N --steps K --warmup W
   (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL; per-GPU batch fixed => weak scaling)
 
-Prints ONE JSON line on rank 0 (contract in the round prompt) including
+Prints ONE JSON line on rank 0: the headline (value, ms_per_step of the --steps timed steps) and step_roofline.
+With --full the line also holds what takes runs of its own:
   roofline     : the dominant kernel (5x5 64->64 conv of Conv2DownUp5) timed with HIP events on its own stream,
-                 algorithmic FLOPs / launch time vs the dense bf16 MFMA peak;
-  cpu_baseline : the CPU oracle (oracle/ref_models.py, "port") timed on this box's host cores on a bounded sample.
+                 algorithmic FLOPs / launch time vs the dense bf16 MFMA peak (roofline_hbm: the largest HBM-bound kernel);
+  secondary    : the other single-GPU workloads (dsnet, PSMNet(192), the f32 path, BASELINE configs 4 / 5);
+  cpu_baseline : the CPU oracle (oracle/ref_models.py, "port") timed on the host cores on a bounded sample.
+--dump-outputs DIR writes what the last timed step returned to its caller (dump_outputs).
 """
 import argparse
 import json
@@ -58,7 +61,15 @@ def parse():
     ap.add_argument("--cpu-steps", type=int, default=5)
     ap.add_argument("--cpu-warmup", type=int, default=3)
     ap.add_argument("--cpu-threads", type=int, default=16)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline / roofline_hbm, the secondary workloads and the CPU baseline (each can be left out "
+                         "with its --no-* switch); without it the run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write the loss the last timed step returned to DIR/loss.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def build_model(dtype, name="minidsnetExt"):
@@ -254,6 +265,16 @@ def cpu_baseline(B, H, W, steps, threads=16, warmup=3):
                       "CPU restatement pinned to the reference by tests/golden)" % (steps, B, W, H, warmup)}
 
 
+def dump_outputs(d, loss):
+    """What the last timed call `step(left, right, seg, disp)` returned to its caller: the loss, as DIR/loss.npy (float32).
+    The model state the steps leave behind (parameters, their gradients, running statistics) is not written: the weight
+    gradient and BatchNorm backward reductions add in an unordered sequence of float atomics, and the train-mode network
+    amplifies those last-bit differences (DESIGN.md, bf16 path), so two runs of one build do not hold the same state."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "loss.npy"), loss.detach().float().cpu().numpy().reshape(()))
+
+
 def spawn_ranks(a):
     """`python bench.py --gpus N` with no launcher environment: the parent starts N fresh rank processes (one per GPU,
     the counterpart of mp.spawn(runNetwork, nprocs) at torch_implementation.py:975) and relays their output.  The parent
@@ -341,6 +362,8 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     lossv = float(loss.item())
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, loss)
     if rank == 0:
         out = {"metric": "stereo-pairs/sec (train fwd+bwd) 512x256", "value": round(a.batch * world * a.steps / dt, 3),
                "unit": "stereo-pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -370,13 +393,13 @@ def main():
         sys.stderr.write("[bench] timed region done: %.3f ms/step\n" % (dt / a.steps * 1e3)); sys.stderr.flush()
         out["step_roofline"] = step_roofline(a.model if a.model != "dsnetnoCorr" else "dsnet", a.batch * world, a.height, a.width,
                                              dt / a.steps * 1e3, a.dtype)
-        if not a.no_roofline:
+        if a.full and not a.no_roofline:
             del step, model
             _ops.set_step_context(None)
             torch.cuda.empty_cache()
             out["roofline"] = kernel_roofline(dtype, a.batch, a.height, a.width)
             out["roofline_hbm"] = hbm_kernel_roofline(dtype, a.batch, a.height, a.width)
-        if world == 1 and not a.no_secondary and a.model == "minidsnetExt" and not a.no_graph:
+        if a.full and world == 1 and not a.no_secondary and a.model == "minidsnetExt" and not a.no_graph:
             sec = []
             f32 = torch.float32
             for name, sb, sdt, sh, sw, label in (
@@ -394,7 +417,7 @@ def main():
                             "dtype": sname, "value": round(sb / ms * 1e3, 2), "unit": "stereo-pairs/s", "ms_per_step": round(ms, 3),
                             "steps": a.secondary_steps, "loss": round(lv, 5), "step_roofline": step_roofline(name, sb, sh, sw, ms, sname)})
             out["secondary"] = sec
-        if world == 1 and not a.no_cpu_baseline and a.model == "minidsnetExt":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.model == "minidsnetExt":
             out["cpu_baseline"] = cpu_baseline(2, a.height, a.width, a.cpu_steps, a.cpu_threads, a.cpu_warmup)
         print(json.dumps(out))
     if world > 1:

@@ -71,6 +71,33 @@ def test_files_to_checkpoint_round_trip(tmp_path):
     assert torch.equal(fresh.flat_p, ts.flat_p) and fresh.steps_done == 3
 
 
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` times exactly K steps, leaves the `--full`
+    measurements out, and writes the loss the last timed step returned as a float32 .npy file."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                        "--height", "256", "--width", "256", "--dump-outputs", str(out)],
+                       env=env, capture_output=True, text=True, timeout=500)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rows = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(rows) == 1, r.stdout
+    j = rows[0]
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0
+    assert abs(j["value"] - 2 * 1e3 / j["ms_per_step"]) <= 1e-2 * j["value"]
+    assert not {"roofline", "roofline_hbm", "secondary", "cpu_baseline"} & set(j)
+    assert os.listdir(out) == ["loss.npy"]
+    loss = np.load(out / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == () and np.isfinite(loss)
+    assert abs(float(loss) - j["loss"]) <= 1e-4 * max(1.0, abs(j["loss"]))
+
+
 def test_bench_gpus_flag_starts_that_many_ranks():
     """`python bench.py --gpus N` with no launcher environment starts N rank processes itself (the counterpart of
     mp.spawn(runNetwork, nprocs), torch_implementation.py:975) with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set;
