@@ -381,6 +381,39 @@ int sdhip_lovasz_softmax(const void* logits, int ldy, const float* target, int l
                          int ignore_void, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Uncertainty-weighted multitask loss (`-multaskloss 1|2`: multiTask_loss, util/utilTorchLoss.py:521-540, called at
+ * models/dsnet_t2.py:1167,1296).  Per-pixel maps, reduction='none':
+ *   seg:  map[p] = exp(-lv) * CE(logits[p,:], labels[p]) + lv      (F.cross_entropy(..., ignore_index, reduction='none'))
+ *   disp: map[p] = exp(-lv) * |pred[p] - target[p]| + lv           (F.l1_loss(..., reduction='none'), no validity mask)
+ * log_var: the parameter, ONE f32 in device memory, read at every launch (no host synchronisation: a captured step's
+ * replays see the value its Adam launch just wrote).  labels: int64 (B,H,W), dense.  A pixel whose label is
+ * ignore_index (the reference passes 19 whatever the class count) has CE 0, so its map value is lv; a label outside
+ * [0, C) is invalid input (the reference raises) and is treated here exactly like ignore_index, never read as an index.
+ * map, lse, target, gmap: dense f32 per pixel.  The logits / grad rows may be channel slices (ld >= C): nothing past the
+ * last pixel's channel C-1 is read, and only the C logical channels of a gradient row are written.
+ * ------------------------------------------------------------------------- */
+/* map, lse[p] = logsumexp(logits[p,:]) (kept for the backward pass), sum += sum_weight * sum_p map[p] (f64, ONE atomic
+ * per workgroup: the caller clears sum, e.g. from the step's zero arena), and mean[0] = (float)*sum if mean != NULL
+ * (sum_weight = 1/npix makes it the map's mean). */
+int sdhip_mt_seg_fwd(const void* logits, int ldy, const int64_t* labels, const float* log_var, float* map, float* lse,
+                     double* sum, float* mean, long npix, int C, int ignore_index, float sum_weight, int dtype, void* stream);
+/* Upstream gradient of map[p]: gp = (gmap ? gmap[p * g_stride] : 0) + (gmean ? gmean[0] * gmean_scale : 0) — g_stride = 0
+ * reads an expanded scalar without materialising it; gmean is the gradient of the mean the forward produced.
+ * grad (optional) = gp * exp(-lv) * (softmax - onehot) for counted pixels, 0 for the others (written, not accumulated).
+ * grad_log_var (optional) += sum_p gp * (1 - exp(-lv) * ce_p) (ACCUMULATED: a parameter-gradient slice). */
+int sdhip_mt_seg_bwd(const void* logits, int ldy, const int64_t* labels, const float* lse, const float* log_var,
+                     const float* gmap, long g_stride, const float* gmean, float gmean_scale, void* grad, int ldg,
+                     float* grad_log_var, long npix, int C, int ignore_index, int dtype, void* stream);
+/* The disparity term: pred with pixel stride ldp (a 1-channel map), target dense; sum / mean as sdhip_mt_seg_fwd. */
+int sdhip_mt_l1_fwd(const void* pred, int ldp, const float* target, const float* log_var, float* map, double* sum,
+                    float* mean, long n, float sum_weight, int dtype, void* stream);
+/* grad (optional, pixel stride ldg) = gp * exp(-lv) * sign(pred - target), sign(0) = 0 as torch;
+ * grad_log_var (optional) += sum_p gp * (1 - exp(-lv) * |pred - target|).  gp as sdhip_mt_seg_bwd. */
+int sdhip_mt_l1_bwd(const void* pred, int ldp, const float* target, const float* log_var, const float* gmap, long g_stride,
+                    const float* gmean, float gmean_scale, void* grad, int ldg, float* grad_log_var, long n, int dtype,
+                    void* stream);
+
+/* ---------------------------------------------------------------------------
  * PSMNet pieces (models_psmnet/stackhourglass.py:110-119,138-155; submodule.py:56-64).
  * ------------------------------------------------------------------------- */
 /* scatter != 0: dst[n, d*sd, h*s, w*s, :] = src[n,d,h,w,:] into a zeroed (here) dense tensor of extent

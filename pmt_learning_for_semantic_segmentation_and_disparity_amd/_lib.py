@@ -93,6 +93,10 @@ SIGNATURES = {
     "sdhip_conv2d_fwd_bnpro": [_p, _p, _p, _p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _d, _f, _f] + [_i] * 15 + [_p],
     "sdhip_conv2d_fwd_add": [_p, _p, _p, _p, _i] + [_i] * 14 + [_p],
     "sdhip_conv2d_fwd_bnbwd": [_p, _p, _p, _p, _i, _i, _p, _i, _p, _p, _p, _i] + [_i] * 17 + [_p],
+    "sdhip_mt_seg_fwd": [_p, _i, _p, _p, _p, _p, _p, _p, _l, _i, _i, _f, _i, _p],
+    "sdhip_mt_seg_bwd": [_p, _i, _p, _p, _p, _p, _l, _p, _f, _p, _i, _p, _l, _i, _i, _i, _p],
+    "sdhip_mt_l1_fwd": [_p, _i, _p, _p, _p, _p, _p, _l, _f, _i, _p],
+    "sdhip_mt_l1_bwd": [_p, _i, _p, _p, _p, _l, _p, _f, _p, _i, _p, _l, _i, _p],
 }
 _lib.sdhip_lovasz_workspace_bytes.argtypes = [_l, _i]
 _lib.sdhip_lovasz_workspace_bytes.restype = _l

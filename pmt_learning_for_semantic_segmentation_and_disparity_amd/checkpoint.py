@@ -94,9 +94,10 @@ def optimizer_state_dict(step):
     state = {}
     slices = _param_slices(step.model)
     t = float(step.steps_done)
+    idle = set(getattr(step, "grad_free", None) or ())
     for i, (_, p, off, n) in enumerate(slices):
-        if t == 0:
-            continue            # torch creates the per-parameter state lazily at the first step
+        if t == 0 or i in idle:
+            continue            # torch creates the per-parameter state lazily at the first step with a gradient
         state[i] = {"step": torch.tensor(t), "exp_avg": step.exp_avg[off:off + n].view(p.shape).clone(),
                     "exp_avg_sq": step.exp_avg_sq[off:off + n].view(p.shape).clone()}
     group = {"lr": step.lr, "betas": tuple(step.betas), "eps": step.eps, "weight_decay": 0, "amsgrad": False,

@@ -217,9 +217,12 @@ __global__ __launch_bounds__(256) void resize_bwd_axis(const T* __restrict__ gy,
     float acc[N];
 #pragma unroll
     for (int e = 0; e < N; ++e) acc[e] = 0.f;
-    // destination candidates: d*scale within (i-1-eps, i+1+eps)
+    // destination candidates: source coordinate within [i-1, i+1) (+-2 destinations of slack).  align_corners=False samples
+    // at (d + 0.5) * scale - 0.5, so its window is shifted by 0.5 * inv - 0.5 destinations: without the shift an upsampling by
+    // more than ~4x missed the destinations between (i+1) * inv and (i+1.5) * inv (x32: 7 % of the gradient dropped)
     const float inv = a.scale > 0.f ? 1.f / a.scale : 0.f;
-    int lo = (int)floorf(((float)i - 1.f) * inv) - 2, hi = (int)ceilf(((float)i + 1.f) * inv) + 2;
+    const float shift = a.mode == 1 ? 0.5f * inv - 0.5f : 0.f;
+    int lo = (int)floorf(((float)i - 1.f) * inv + shift) - 2, hi = (int)ceilf(((float)i + 1.f) * inv + shift) + 2;
     if (a.scale <= 0.f) { lo = 0; hi = a.out - 1; }
     if (lo < 0) lo = 0;
     if (hi > a.out - 1) hi = a.out - 1;

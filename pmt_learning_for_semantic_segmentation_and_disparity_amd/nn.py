@@ -290,8 +290,11 @@ class minidsnetExt(nn.Module):
 
     def __init__(self, CFG, labels=8, pretrained=False, patch_type='', include_edges=False, backbone='densenet'):
         super().__init__()
-        if backbone != 'densenet' or CFG.multaskloss:
-            raise NotImplementedError("native path: densenet backbone, no multitask loss wrapper (models/dsnet_t2.py:1297) yet")
+        if backbone != 'densenet':
+            raise NotImplementedError("native path: densenet backbone only")
+        if CFG.multaskloss not in (0, 1, 2):
+            raise NotImplementedError("multaskloss %r: the reference defines 1 and 2" % (CFG.multaskloss,))
+        self.multiTaskLoss = CFG.multaskloss
         self.include_edges = include_edges
         self.hanet = CFG.hanet
         dropout = CFG.dropout
@@ -336,6 +339,14 @@ class minidsnetExt(nn.Module):
         else:
             self.Conv2DownUp11 = nn.Sequential(Conv2DownUp(32, 32, 3, lastLayer=False, dropout=dropout),
                                                ConvTranspose2dSame(32, labels, 3, 1, padding='same', init_he=False))
+        if self.multiTaskLoss:   # models/dsnet_t2.py:1126-1133: registered here, so state_dict keys and Adam order follow upstream
+            from .multitask import multiTask_loss
+            self.mtloss = multiTask_loss(self.multiTaskLoss)
+            if self.multiTaskLoss == 2:
+                self.mt_convDisp = nn.Sequential(convbn(1024, 256, 1, 1, 'same', 1), nn.ReLU(inplace=True),
+                                                 conv2dSame(256, 1, 3, 1, padding='same'))
+                self.mt_convSeg = nn.Sequential(convbn(1024, 256, 1, 1, 'same', 1), nn.ReLU(inplace=True),
+                                                conv2dSame(256, labels, 3, 1, padding='same'))
         if self.hanet:   # models/dsnet_t2.py:1135-1150
             from .hanet import HANet_Conv
             self.hanet_last = HANet_Conv(64, labels, pooling='max', pos_rfactor=2, dropout_prob=0.1)
@@ -352,6 +363,8 @@ class minidsnetExt(nn.Module):
         B, _, H, W = input_a.shape
         both, img_a = _stereo_buffer(input_a, input_b, self.include_edges)
         t = self.resnet_features(both, groups=2)          # taps of both towers, batch = [left | right]
+        if self.multiTaskLoss == 2:
+            return self._forward_mt_heads(t, B, H, W, disp_gt, seg_gt)
         halves = [ops.split_batch(u, B) for u in t]   # left / right tower outputs (one gradient buffer per tap in the backward)
         a = [h[0] for h in halves]
         b = [h[1] for h in halves]
@@ -420,7 +433,22 @@ class minidsnetExt(nn.Module):
                 seg2 = self.Conv2DownUp11[1](seg2)
             if self.hanet:   # only on this branch, as upstream (models/dsnet_t2.py:1287-1289): with aspp == 2 the head is built but unused
                 seg2, _ = self.hanet_last(a[0], seg2, pos, attention_loss=True)
+        if self.multiTaskLoss:   # models/dsnet_t2.py:1295-1297
+            loss_disp, loss_seg1, loss_seg2 = self.mtloss(disp, disp_gt, seg1, seg2, seg_gt)
+            return seg1, disp, seg2, disp, loss_disp, loss_seg1, loss_seg2
         return seg1, disp, seg2, disp
+
+    def _forward_mt_heads(self, t, B, H, W, disp_gt, seg_gt):
+        """multaskloss == 2 (models/dsnet_t2.py:1162-1168): both towers and their pyramids have run (their BatchNorm running
+        statistics move in train mode); the two heads read the left tower's 1/32 tap, disparity is upsampled bilinear and
+        segmentation nearest, and the network returns early — nothing else runs or receives a gradient."""
+        a4 = ops.split_batch(t[4], B)[0]
+        d = self.mt_convDisp[2].run(self.mt_convDisp[0].fused(a4, act=1))
+        s = self.mt_convSeg[2].run(self.mt_convSeg[0].fused(a4, act=1))
+        disp = ops.interpolate(d, size=(H, W), mode='bilinear')
+        seg = ops.interpolate(s, size=(H, W), mode='nearest')
+        loss_disp, loss_seg1, loss_seg2 = self.mtloss(disp, disp_gt, seg, seg, seg_gt)
+        return seg, disp, seg, disp, loss_disp, loss_seg1, loss_seg2
 
 
 def _stereo_buffer(input_a, input_b, include_edges=False):

@@ -1323,6 +1323,137 @@ class _TrainLossFn(torch.autograd.Function):
         return g1, gd, g2, None, None, None, None, None   # d(total)/d(total) is 1 in the training step
 
 
+MT_IGNORE_INDEX = 19     # F.cross_entropy(..., ignore_index=19) of util/utilTorchLoss.py:533,535, whatever the class count
+
+
+def _map_grad(g):
+    """(f32 tensor, g_stride) of the upstream gradient of a per-pixel loss map: an expanded scalar (every stride 0, what
+    autograd hands over for `.sum()`) is read in place; anything else as a dense map."""
+    if g is None:
+        return None, 0
+    if all(s == 0 for s in g.stride()):
+        return g.float(), 0
+    return g.float().contiguous(), 1
+
+
+def _log_var_grad(log_var):
+    """(pointer target the kernel accumulates d/d log_var into, gradient to hand back to autograd or None)."""
+    t = _grad_target(log_var)
+    if t is not None:
+        return t, None
+    g, _ = _zeros((1,), torch.float32, log_var.device)
+    return g, g.view(log_var.shape)
+
+
+def _check_log_var(log_var):
+    if log_var.numel() != 1 or log_var.dtype != torch.float32 or not log_var.is_contiguous():
+        raise _lib.SdhipError("log-variance must be one contiguous f32 element (got %s %s)" % (tuple(log_var.shape), log_var.dtype))
+
+
+class _MTSegFn(torch.autograd.Function):
+    """(map, mean): map = exp(-lv) * CE(logits, labels, ignore_index, reduction='none') + lv, (B,H,W) f32, and its mean from
+    the f64 sum the same pass accumulates (util/utilTorchLoss.py:533-536)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, log_var, ignore_index):
+        _require_gpu(logits, labels, log_var)
+        _check_log_var(log_var)
+        B, C, H, W = logits.shape
+        if tuple(labels.shape) != (B, H, W):
+            raise _lib.SdhipError("labels must be (B,H,W) = %s, got %s" % ((B, H, W), tuple(labels.shape)))
+        npix = B * H * W
+        yv, ld = nhwc_view(logits)
+        lab = labels.long().contiguous()
+        m = torch.empty((B, H, W), dtype=torch.float32, device=logits.device)
+        lse = torch.empty((B, H, W), dtype=torch.float32, device=logits.device)
+        mean = torch.empty((), dtype=torch.float32, device=logits.device)
+        s, _ = _zeros((1,), torch.float64, logits.device)
+        call("sdhip_mt_seg_fwd", ptr(yv), ld, ptr(lab), ptr(log_var), ptr(m), ptr(lse), ptr(s), ptr(mean), npix, C, int(ignore_index),
+             1.0 / npix, dtype_code(logits), stream_ptr())
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(yv, lab, lse, log_var)
+        ctx.cfg = (ld, B, C, H, W, int(ignore_index))
+        return m, mean
+
+    @staticmethod
+    def backward(ctx, gmap, gmean):
+        yv, lab, lse, log_var = ctx.saved_tensors
+        ld, B, C, H, W, ign = ctx.cfg
+        npix = B * H * W
+        if gmap is None and gmean is None:
+            return None, None, None, None
+        g, gs = _map_grad(gmap)
+        gm = gmean.float().contiguous() if gmean is not None else None
+        gx = empty_nhwc(B, C, H, W, yv.dtype, yv.device) if ctx.needs_input_grad[0] else None
+        tlv, glv = _log_var_grad(log_var) if ctx.needs_input_grad[2] else (None, None)
+        call("sdhip_mt_seg_bwd", ptr(yv), ld, ptr(lab), ptr(lse), ptr(log_var), ptr(g), gs, ptr(gm), 1.0 / npix, ptr(gx), C,
+             ptr(tlv), npix, C, ign, dtype_code(yv), stream_ptr())
+        return gx, None, glv, None
+
+
+class _MTL1Fn(torch.autograd.Function):
+    """(map, mean): map = exp(-lv) * |pred - target| + lv, (B,1,H,W) f32 (util/utilTorchLoss.py:532; no disp > 0 mask)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, log_var):
+        _require_gpu(pred, target, log_var)
+        _check_log_var(log_var)
+        B, C, H, W = pred.shape
+        if C != 1 or tuple(target.shape) != (B, 1, H, W):
+            raise _lib.SdhipError("disparity and its target must be (B,1,H,W), got %s and %s" % (tuple(pred.shape), tuple(target.shape)))
+        n = B * H * W
+        pv, ldp = nhwc_view(pred)
+        t = target.float().contiguous()
+        m = torch.empty((B, 1, H, W), dtype=torch.float32, device=pred.device)
+        mean = torch.empty((), dtype=torch.float32, device=pred.device)
+        s, _ = _zeros((1,), torch.float64, pred.device)
+        call("sdhip_mt_l1_fwd", ptr(pv), ldp, ptr(t), ptr(log_var), ptr(m), ptr(s), ptr(mean), n, 1.0 / n, dtype_code(pred), stream_ptr())
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(pv, t, log_var)
+        ctx.cfg = (ldp, B, H, W)
+        return m, mean
+
+    @staticmethod
+    def backward(ctx, gmap, gmean):
+        pv, t, log_var = ctx.saved_tensors
+        ldp, B, H, W = ctx.cfg
+        n = B * H * W
+        if gmap is None and gmean is None:
+            return None, None, None
+        g, gs = _map_grad(gmap)
+        gm = gmean.float().contiguous() if gmean is not None else None
+        gp = torch.empty((B, 1, H, W), dtype=pv.dtype, device=pv.device) if ctx.needs_input_grad[0] else None
+        tlv, glv = _log_var_grad(log_var) if ctx.needs_input_grad[2] else (None, None)
+        call("sdhip_mt_l1_bwd", ptr(pv), ldp, ptr(t), ptr(log_var), ptr(g), gs, ptr(gm), 1.0 / n, ptr(gp), 1, ptr(tlv), n,
+             dtype_code(pv), stream_ptr())
+        return gp, None, glv
+
+
+def multitask_seg_loss(logits, labels, log_var, ignore_index=MT_IGNORE_INDEX):
+    """exp(-lv) * F.cross_entropy(logits, labels, ignore_index=ignore_index, reduction='none') + lv, (B,H,W) f32.  A label
+    outside [0, C) counts as ignored (the reference raises).  The returned map carries its mean, computed by the same
+    pass, as `map.sdhip_mean` (loss_map_mean)."""
+    m, mean = _MTSegFn.apply(logits, labels, log_var, ignore_index)
+    m.sdhip_mean = mean
+    return m
+
+
+def multitask_l1_loss(pred, target, log_var):
+    """exp(-lv) * F.l1_loss(pred, target, reduction='none') + lv, (B,1,H,W) f32; `map.sdhip_mean` as multitask_seg_loss."""
+    m, mean = _MTL1Fn.apply(pred, target, log_var)
+    m.sdhip_mean = mean
+    return m
+
+
+def loss_map_mean(m):
+    """mean(m) of a map returned by multitask_seg_loss / multitask_l1_loss: the f32 scalar their forward pass produced from
+    its f64 sum (no reduction kernel); its gradient reaches the map's backward kernel as one uniform term."""
+    mean = getattr(m, "sdhip_mean", None)
+    if mean is None:
+        raise _lib.SdhipError("loss_map_mean: the map was not produced by a multitask loss operator")
+    return mean
+
+
 def train_loss(seg1, disp, seg2, seg_target, disp_target, use_lovasz=True, mask_invalid_disp=False, ignore_void=False):
     """seg_target: one-hot f32 (B,C,H,W); disp_target: f32 (B,1,H,W).  The two dataset rules of losses/multiLosses.py are
     opt-in, both off by default (roses / garden, `ignore=None`, :11-17):

@@ -8,7 +8,7 @@ data-parallel); activations run in `dtype` (bf16 MFMA path or exact f32 path).
 import os
 import torch
 
-from . import _lib, ops, parallel
+from . import _lib, multitask, ops, parallel
 from ._lib import call, ptr, stream_ptr
 
 
@@ -77,6 +77,11 @@ class TrainStep:
         self.steps_done = 0       # optimizer steps actually EXECUTED (eager steps + graph replays; the recording pass of a capture runs nothing)
         self._capture_fault = None   # tests: a callable invoked inside the capture to make it fail
         self.debug_graph = False     # tests: keep the captured hipGraph inspectable (_lib.graph_node_counts)
+        # multitask models: positions (in model.parameters() order) of the parameters the loss never reaches (mode 2's unused
+        # decoder), found on the first step.  torch.optim.Adam keeps no state for them (their .grad stays None), so a saved
+        # optimizer state omits them as well (checkpoint.optimizer_state_dict); here their gradient slice stays 0, their
+        # moments stay 0 and the fused Adam leaves them bit-identical (update 0 / (0 + eps))
+        self.grad_free = None
         # dropout streams differ per rank (the reference's ranks draw from independently seeded generators) and advance
         # once per step on the device, so that graph replays see new masks (ops.rng_seed_tensor)
         # (the tensor belongs to this step's context: creating a second TrainStep does not restart the first one's stream)
@@ -117,11 +122,19 @@ class TrainStep:
         if first:
             self.flat_g.zero_()
         self.pack_all()             # one launch packs every weight (forward and data-grad orientation)
-        outs = self.model(left.to(self.dtype), right.to(self.dtype))
+        mt = getattr(self.model, "multiTaskLoss", 0)
+        if mt:    # the reference harness's call (torch_implementation.py:146-149): labels from the full one-hot (ATen argmax)
+            outs = self.model(left.to(self.dtype), right.to(self.dtype), None, disp, seg.argmax(1))
+        else:
+            outs = self.model(left.to(self.dtype), right.to(self.dtype))
         if self.loss_fn is not None:
             loss = self.loss_fn(outs, seg, disp)
+        elif mt:  # the sum of the three maps' means (torch_implementation.py:173-176,285-325), from the loss kernels' own sums
+            loss = multitask.step_loss(outs[4], outs[5], outs[6])
         else:
             loss = ops.train_loss(outs[0], outs[1], outs[2], seg, disp, self.use_lovasz)
+        if mt and self.grad_free is None:
+            self.grad_free = _unreached_parameters(self.model, loss)
         if self.metrics is not None and self.loss_fn is None:
             self.metrics.update(outs[2].detach(), seg, outs[1].detach(), disp)
         loss.backward()
@@ -295,6 +308,22 @@ class TrainStep:
         if ph[1]:
             self.steps_done += 1
         return loss
+
+
+def _unreached_parameters(model, loss):
+    """Positions of the parameters whose AccumulateGrad node the autograd graph of `loss` does not contain."""
+    reached, seen, keep, stack = set(), set(), [], [loss.grad_fn]
+    while stack:
+        fn = stack.pop()
+        if fn is None or id(fn) in seen:
+            continue
+        seen.add(id(fn))
+        keep.append(fn)            # visited nodes stay alive during the walk, so their ids stay unique
+        v = getattr(fn, "variable", None)
+        if v is not None:
+            reached.add(id(v))
+        stack.extend(f for f, _ in fn.next_functions)
+    return [i for i, p in enumerate(model.parameters()) if id(p) not in reached]
 
 
 def _backend_of(pg):
