@@ -38,6 +38,12 @@ extern "C" {
 #define SDHIP_ERR_LAUNCH (-2)  /* hip launch failure */
 #define SDHIP_ERR_UNSUPPORTED (-3)
 
+/* Activation codes of the elementwise / BatchNorm kernels beyond 0 none, 1 ReLU, 2 sigmoid (4: sigmoid given its output,
+ * backward only): the hard activations of MobileNetV3 (models/mobilenetv3.py:44-61), h_swish = x*relu6(x+3)/6 and
+ * h_sigmoid = relu6(x+3)/6, with torch's gradient of that composite (0 weight on relu6's kinks). */
+#define SDHIP_ACT_HSWISH 5
+#define SDHIP_ACT_HSIGMOID 6
+
 /* ABI version of this header; bumped on any signature change. */
 int sdhip_abi_version(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
@@ -540,6 +546,53 @@ int sdhip_double_left_sample(void* left, void* right, int ld_img, float* seg, in
 long sdhip_flip_sample_workspace_bytes(int H, int W, int n_seg);
 int sdhip_flip_sample(void* left, void* right, int ld_img, float* seg, int ld_seg, int n_seg, float* disp, int H, int W,
                       void* workspace, long workspace_bytes, int dtype, void* stream);
+
+
+/* ---------------------------------------------------------------------------
+ * MobileNetV3-Large backbone (models/mobilenetv3.py, the default backbone of minidsnetExt, models/dsnet_t2.py:942,1935).
+ *
+ * Depthwise convolution nn.Conv2d(C, C, k, stride, (k-1)/2, groups=C, bias=False) of InvertedResidual
+ * (models/mobilenetv3.py:99,110), k in {3, 5}, stride in {1, 2}, any H, W:
+ *   y[b,oh,ow,c] = sum_{kh,kw} w[c][kh*k+kw] * x[b, oh*stride - p + kh, ow*stride - p + kw, c],  p = (k-1)/2.
+ * w: the f32 parameter as stored, (C, 1, k, k).  x / y: NHWC with pixel strides ldx / ldy (channel slices allowed; the
+ * channel tail is masked, pad lanes are never read).  Ho = (H + 2p - k)/stride + 1.
+ * stats (optional, f64 [nrep][groups][2][sld], zeroed by the caller): per statistics group (sum, sum of squares) of the
+ * stored output, for the BatchNorm behind it (sdhip_affine_act_bn).  pool (optional, f32 [B][pool_parts][C], zeroed by the
+ * caller, pool_parts >= sdhip_dw_pool_parts): partial per-image channel sums of the stored output, one slot per workgroup
+ * (slots no workgroup writes stay zero) — the global average pool of SELayer (models/mobilenetv3.py:73), since the
+ * BatchNorm in between is affine per channel; sdhip_se_fwd adds the slots in a fixed order, so the pool is deterministic. */
+int sdhip_dw_conv_fwd(const void* x, int ldx, const float* w, void* y, int ldy, double* stats, int sld, int nrep, float* pool,
+                      int pool_parts, int B, int H, int W, int C, int k, int stride, int groups, int dtype, void* stream);
+/* Pool slots sdhip_dw_conv_fwd needs for an (H, W, C) input (< 0: unsupported k / stride / shape).  Host only. */
+int sdhip_dw_pool_parts(int H, int W, int C, int k, int stride, int dtype);
+/* Data gradient of sdhip_dw_conv_fwd: gx[b,ih,iw,c] = sum over the taps that reach (ih, iw) of gy * w (stride 2: at most
+ * ceil(k/2)^2 taps per input pixel, gathered; no zero-stuffing, no atomics).  gx is overwritten. */
+int sdhip_dw_conv_dgrad(const void* gy, int ldg, const float* w, void* gx, int ldgx,
+                        int B, int H, int W, int C, int k, int stride, int dtype, void* stream);
+/* Weight gradient of sdhip_dw_conv_fwd, ADDED to dw (C, 1, k, k) f32 — a slice of the flat gradient buffer or a zeroed
+ * tensor.  part: f32 workspace of nparts * k*k * C floats (nparts = sdhip_dw_wgrad_parts; no initialisation needed): every
+ * workgroup stores its partial sums there, a second launch adds them in a fixed order — no atomics, deterministic. */
+int sdhip_dw_conv_wgrad(const void* x, int ldx, const void* gy, int ldg, float* dw, float* part, int nparts,
+                        int B, int H, int W, int C, int k, int stride, int dtype, void* stream);
+/* Partial slots of sdhip_dw_conv_wgrad for this shape (< 0: unsupported).  Host only. */
+int sdhip_dw_wgrad_parts(int B, int H, int W, int C, int k, int stride);
+/* SELayer excitation (models/mobilenetv3.py:64-77): v[b,c] = (sum_p pool[b][p][c])*inv_hw*scale[g][c] + shift[g][c]
+ * (pool: the pool_parts slots of sdhip_dw_conv_fwd, added in slot order; scale / shift:
+ * the BatchNorm in front, g = b / (B/groups); NULL: identity), h = relu(w1 v + b1), a = w2 h + b2, s = h_sigmoid(a).
+ * w1 (r, C), b1 (r), w2 (C, r), b2 (C): the two nn.Linear parameters, f32.  Writes s [B][C] and the saved activations
+ * ws = [v (B*C) | h (B*r) | a (B*C)] f32.  One launch; the multiply x * s[b,c] is sdhip_affine_act with groups = B. */
+int sdhip_se_fwd(const float* pool, int pool_parts, float inv_hw, const float* scale, const float* shift, int groups,
+                 const float* w1, const float* b1, const float* w2, const float* b2, float* s, float* ws,
+                 int B, int C, int r, void* stream);
+/* Backward of sdhip_se_fwd given ds = dL/ds as the f32 replica sums [nrep][B][C] of sdhip_affine_act_bwd (groups = B):
+ * ADDS the four parameter gradients to gw1 / gb1 / gw2 / gb2 (f32 atomics) and writes gpool[b][c] = dL/dv[b,c] * inv_hw,
+ * the term every pixel of image b adds to the gradient of the pooled tensor.  One launch. */
+int sdhip_se_bwd(const float* ds, int nrep, const float* ws, const float* w1, const float* w2,
+                 float* gw1, float* gb1, float* gw2, float* gb2, float* gpool, float inv_hw, int B, int C, int r, void* stream);
+/* gx = gy * act'(x * s[b][c]) * s[b][c] + gadd[b][c]: the data gradient of y = act(x * s) (sdhip_affine_act with
+ * groups = B) plus the pooled path of SELayer.  act: 0, 1, SDHIP_ACT_HSWISH or SDHIP_ACT_HSIGMOID; B images of npix_img. */
+int sdhip_se_scale_bwd(const void* gy, int ldg, const void* x, int ldx, void* gx, int ldgx, const float* s, const float* gadd,
+                       long npix_img, int B, int C, int act, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libsdhip.so")
 
 F32, BF16 = 0, 1
 ERR_ARG, ERR_LAUNCH, ERR_UNSUPPORTED = -1, -2, -3   # include/sdhip.h
+ACT_HSWISH, ACT_HSIGMOID = 5, 6                      # SDHIP_ACT_* of include/sdhip.h (MobileNetV3's hard activations)
 NREP = int(os.environ.get("SDHIP_TUNE_NREP", "32"))   # statistics replicas the kernels spread their atomics over (env: tuning only)
 
 
@@ -97,6 +98,14 @@ SIGNATURES = {
     "sdhip_mt_seg_bwd": [_p, _i, _p, _p, _p, _p, _l, _p, _f, _p, _i, _p, _l, _i, _i, _i, _p],
     "sdhip_mt_l1_fwd": [_p, _i, _p, _p, _p, _p, _p, _l, _f, _i, _p],
     "sdhip_mt_l1_bwd": [_p, _i, _p, _p, _p, _l, _p, _f, _p, _i, _p, _l, _i, _p],
+    "sdhip_dw_conv_fwd": [_p, _i, _p, _p, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "sdhip_dw_pool_parts": [_i] * 6,
+    "sdhip_dw_wgrad_parts": [_i] * 6,
+    "sdhip_dw_conv_dgrad": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "sdhip_dw_conv_wgrad": [_p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "sdhip_se_fwd": [_p, _i, _f, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
+    "sdhip_se_bwd": [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _i, _i, _p],
+    "sdhip_se_scale_bwd": [_p, _i, _p, _i, _p, _i, _p, _p, _l, _i, _i, _i, _i, _p],
 }
 _lib.sdhip_lovasz_workspace_bytes.argtypes = [_l, _i]
 _lib.sdhip_lovasz_workspace_bytes.restype = _l
@@ -121,6 +130,22 @@ class WgradItem(ctypes.Structure):
 
 def lovasz_workspace_bytes(npix, C):
     return _lib.sdhip_lovasz_workspace_bytes(npix, C)
+
+
+def dw_pool_parts(H, W, C, k, stride, dt):
+    """Pool slots of sdhip_dw_conv_fwd for this input (include/sdhip.h)."""
+    n = _lib.sdhip_dw_pool_parts(H, W, C, k, stride, dt)
+    if n <= 0:
+        raise SdhipError("sdhip_dw_pool_parts: unsupported depthwise shape")
+    return n
+
+
+def dw_wgrad_parts(B, H, W, C, k, stride):
+    """Partial slots of sdhip_dw_conv_wgrad for this shape (include/sdhip.h)."""
+    n = _lib.sdhip_dw_wgrad_parts(B, H, W, C, k, stride)
+    if n <= 0:
+        raise SdhipError("sdhip_dw_wgrad_parts: unsupported depthwise shape")
+    return n
 
 
 def packed_elems(M, K, T, dt):

@@ -21,6 +21,10 @@
 
 namespace {
 
+// h-swish / h-sigmoid run in their own instantiations (template flag HS): the kernels every other layer uses keep the
+// code, registers and schedule they had before these codes existed
+inline bool hard_act(int act) { return act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID; }
+
 struct RowGeom {  // how a 256-thread block walks a [npix][C] matrix
   int tx, ty;     // threads across channel units / across pixels
   int units;      // channel units per row (16-byte chunks, or single elements in scalar mode)
@@ -41,7 +45,7 @@ inline RowGeom row_geom(int units) {
                              const int tx = (int)threadIdx.x - ty * (rg).tx
 
 // y = act(x*scale + shift) (+ res);  grid: (pixel slabs, unit groups, stat groups)
-template <typename T, bool VEC>
+template <typename T, bool VEC, bool HS = false>
 __global__ __launch_bounds__(256) void affine_act_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy,
                                                          const T* __restrict__ res, int ldr,
                                                          const float* __restrict__ scale, const float* __restrict__ shift,
@@ -64,6 +68,7 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const T* __restrict__ x
       float v = fmaf(f[e], sc[e], sf[e]);
       if (act == 1) v = fmaxf(v, 0.f);
       else if (act == 2) v = 1.f / (1.f + __expf(-v));
+      else if (HS && (act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID)) v = act_hs(v, act);
       if (res) v += r[e];
       f[e] = v;
     }
@@ -73,7 +78,7 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const T* __restrict__ x
 
 // gx = gy * act'(x*scale+shift) * scale;  dscale += sum gy*act'*x;  dshift += sum gy*act'
 // mode 0: both; mode 1: only the reductions (gx not written)
-template <typename T, bool VEC>
+template <typename T, bool VEC, bool HS = false>
 __global__ __launch_bounds__(256) void affine_act_bwd_kernel(const T* gy, int ldg, const T* __restrict__ x, int ldx,
                                                              T* gx, int ldgx,
                                                              const float* __restrict__ scale, const float* __restrict__ shift,
@@ -117,6 +122,7 @@ __global__ __launch_bounds__(256) void affine_act_bwd_kernel(const T* gy, int ld
             float gm = gv[k][e];
             if (act == 1) gm = z > 0.f ? gm : 0.f;
             else if (act == 2) { const float sg = 1.f / (1.f + __expf(-z)); gm *= sg * (1.f - sg); }
+            else if (HS && (act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID)) gm *= act_hs_d(z, act);
             else if (act == 4) gm *= z * (1.f - z);  // x holds the sigmoid OUTPUT
             a1[e] = fmaf(gm, xv[k][e], a1[e]);
             a2[e] += gm;
@@ -181,7 +187,7 @@ __global__ __launch_bounds__(256) void stats_fix_kernel(const T* gin, int ldgi, 
 // Second phase of the two-phase BatchNorm backward: gx = gy * act'(x*scale+shift) * scale + dS1 + 2 * x * dS2 in ONE pass
 // (the first phase is affine_act_bwd with gx == NULL: reductions only).  10 bytes per element instead of the 12 of
 // "write gx, then read it back for the statistics path".
-template <typename T, bool VEC>
+template <typename T, bool VEC, bool HS = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__ gy, int ldg, const T* __restrict__ x, int ldx,
                                                            T* __restrict__ gx, int ldgx, const float* __restrict__ scale,
                                                            const float* __restrict__ shift, const double* __restrict__ dS, int ldc,
@@ -219,6 +225,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
           float gm = gv[k][e];
           if (act == 1) gm = z > 0.f ? gm : 0.f;
           else if (act == 2) { const float sg = 1.f / (1.f + __expf(-z)); gm *= sg * (1.f - sg); }
+          else if (HS && (act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID)) gm *= act_hs_d(z, act);
           // the first-phase result the one-pass form would have stored is rounded to T before the statistics path is added
           gv[k][e] = Elem<T>::rnd(gm * sc[e]) + fmaf(xv[k][e], b2[e], a[e]);
         }
@@ -235,7 +242,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
 
 // y = act(BatchNorm_train(x)) (+ res) straight from the statistics S (f64 [nrep][G][2][ldc]) of x.
 // Also writes scale/shift/mean/invstd ([G][C], for the backward pass) and updates the running statistics (groups in order).
-template <typename T, bool VEC>
+template <typename T, bool VEC, bool HS = false>
 __global__ __launch_bounds__(256) void affine_act_bn_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy,
                                                             const T* __restrict__ res, int ldr,
                                                             const double* __restrict__ S, int ldc, int nrep,
@@ -318,6 +325,7 @@ __global__ __launch_bounds__(256) void affine_act_bn_kernel(const T* __restrict_
       float v = fmaf(f[e], sc[e], sf[e]);
       if (act == 1) v = fmaxf(v, 0.f);
       else if (act == 2) v = 1.f / (1.f + __expf(-v));
+      else if (HS && (act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID)) v = act_hs(v, act);
       if (res) v += r[e];
       f[e] = v;
     }
@@ -327,7 +335,7 @@ __global__ __launch_bounds__(256) void affine_act_bn_kernel(const T* __restrict_
 
 // gx = gy * act'(x*scale+shift) * scale + dS1 + 2*x*dS2 with dS derived in the kernel from the (dscale, dshift) replica
 // sums of the first phase; the first workgroup of a channel slice also writes dgamma / dbeta (summed over groups).
-template <typename T, bool VEC>
+template <typename T, bool VEC, bool HS = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_fin_kernel(const T* gy, int ldg, const T* __restrict__ x, int ldx,
                                                                T* gx, int ldgx, const float* __restrict__ scale,
                                                                const float* __restrict__ shift, const float* __restrict__ dscale,
@@ -421,6 +429,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fin_kernel(const T* gy, int 
           float gm = gv[k][e];
           if (act == 1) gm = z > 0.f ? gm : 0.f;
           else if (act == 2) { const float sg = 1.f / (1.f + __expf(-z)); gm *= sg * (1.f - sg); }
+          else if (HS && (act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID)) gm *= act_hs_d(z, act);
           gv[k][e] = Elem<T>::rnd(gm * sc[e]) + fmaf(xv[k][e], b2[e], a[e]);
         }
         Unit<T, VEC>::store(gx + (base + pix) * ldgx + c0, gv[k]);
@@ -677,17 +686,24 @@ extern "C" int sdhip_affine_act(const void* x, int ldx, void* y, int ldy, const 
   const int G = groups;
   if (int rc = check_rows("affine_act", npix, C, G, dtype)) return rc;
   SDHIP_CHECK_ARG(x && y && ldx >= C && ldy >= C && (!res || ldr >= C), "affine_act: bad pointers/strides");
+  SDHIP_CHECK_ARG(act == 0 || act == 1 || act == 2 || act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID, "affine_act: activation %d", act);
   hipStream_t s = (hipStream_t)stream;
 #define ARGS(T) (const T*)x, ldx, (T*)y, ldy, (const T*)res, ldr, scale, shift, C, npix / G, act
   if (dtype == SDHIP_F32) {
     const bool v = vec_rows<float>(C, {ldx, ldy, res ? ldr : 0}, {x, y, res});
     Plan pl = plan(v ? C / 4 : C, npix / G, G);
-    if (v) hipLaunchKernelGGL((affine_act_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+    if (hard_act(act)) {
+      if (v) hipLaunchKernelGGL((affine_act_kernel<float, true, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+      else hipLaunchKernelGGL((affine_act_kernel<float, false, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+    } else if (v) hipLaunchKernelGGL((affine_act_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
     else hipLaunchKernelGGL((affine_act_kernel<float, false>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
   } else {
     const bool v = vec_rows<bf16_t>(C, {ldx, ldy, res ? ldr : 0}, {x, y, res});
     Plan pl = plan(v ? C / 8 : C, npix / G, G);
-    if (v) hipLaunchKernelGGL((affine_act_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+    if (hard_act(act)) {
+      if (v) hipLaunchKernelGGL((affine_act_kernel<bf16_t, true, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+      else hipLaunchKernelGGL((affine_act_kernel<bf16_t, false, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+    } else if (v) hipLaunchKernelGGL((affine_act_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
     else hipLaunchKernelGGL((affine_act_kernel<bf16_t, false>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
   }
 #undef ARGS
@@ -703,6 +719,8 @@ extern "C" int sdhip_affine_act_bwd(const void* gy, int ldg, const void* x, int 
   if (int rc = check_rows("affine_act_bwd", npix, C, G, dtype)) return rc;
   SDHIP_CHECK_ARG(gy && x && ldg >= C && ldx >= C && (!gx || ldgx >= C), "affine_act_bwd: bad pointers/strides");
   SDHIP_CHECK_ARG((dscale == nullptr) == (dshift == nullptr), "affine_act_bwd: dscale/dshift must come together");
+  SDHIP_CHECK_ARG(act == 0 || act == 1 || act == 2 || act == 4 || act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID,
+                  "affine_act_bwd: activation %d", act);
   hipStream_t s = (hipStream_t)stream;
   if (dscale && !prezeroed) {
     if (sdhip_zero_async(dscale, sizeof(float) * (size_t)nrep * G * C, s) != hipSuccess ||
@@ -713,12 +731,18 @@ extern "C" int sdhip_affine_act_bwd(const void* gy, int ldg, const void* x, int 
   if (dtype == SDHIP_F32) {
     const bool v = vec_rows<float>(C, {ldg, ldx, gx ? ldgx : 0}, {gy, x, gx});
     Plan pl = plan(v ? C / 4 : C, npix / G, G, 1024);
-    if (v) hipLaunchKernelGGL((affine_act_bwd_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+    if (hard_act(act)) {
+      if (v) hipLaunchKernelGGL((affine_act_bwd_kernel<float, true, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+      else hipLaunchKernelGGL((affine_act_bwd_kernel<float, false, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+    } else if (v) hipLaunchKernelGGL((affine_act_bwd_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
     else hipLaunchKernelGGL((affine_act_bwd_kernel<float, false>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
   } else {
     const bool v = vec_rows<bf16_t>(C, {ldg, ldx, gx ? ldgx : 0}, {gy, x, gx});
     Plan pl = plan(v ? C / 8 : C, npix / G, G, 1024);
-    if (v) hipLaunchKernelGGL((affine_act_bwd_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+    if (hard_act(act)) {
+      if (v) hipLaunchKernelGGL((affine_act_bwd_kernel<bf16_t, true, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+      else hipLaunchKernelGGL((affine_act_bwd_kernel<bf16_t, false, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+    } else if (v) hipLaunchKernelGGL((affine_act_bwd_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
     else hipLaunchKernelGGL((affine_act_bwd_kernel<bf16_t, false>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
   }
 #undef ARGS
@@ -757,18 +781,24 @@ extern "C" int sdhip_bn_bwd_apply(const void* gy, int ldg, const void* x, int ld
   const int G = groups;
   if (int rc = check_rows("bn_bwd_apply", npix, C, G, dtype)) return rc;
   SDHIP_CHECK_ARG(gy && x && gx && scale && shift && dS && ldg >= C && ldx >= C && ldgx >= C, "bn_bwd_apply: bad pointers/strides");
-  SDHIP_CHECK_ARG(act == 0 || act == 1 || act == 2, "bn_bwd_apply: activation %d", act);
+  SDHIP_CHECK_ARG(act == 0 || act == 1 || act == 2 || act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID, "bn_bwd_apply: activation %d", act);
   hipStream_t s = (hipStream_t)stream;
 #define ARGS(T) (const T*)gy, ldg, (const T*)x, ldx, (T*)gx, ldgx, scale, shift, dS, ldc, C, npix / G, act
   if (dtype == SDHIP_F32) {
     const bool v = vec_rows<float>(C, {ldg, ldx, ldgx}, {gy, x, gx});
     Plan pl = plan(v ? C / 4 : C, npix / G, G, 1024);
-    if (v) hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+    if (hard_act(act)) {
+      if (v) hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+      else hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+    } else if (v) hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
     else hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
   } else {
     const bool v = vec_rows<bf16_t>(C, {ldg, ldx, ldgx}, {gy, x, gx});
     Plan pl = plan(v ? C / 8 : C, npix / G, G, 1024);
-    if (v) hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+    if (hard_act(act)) {
+      if (v) hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, true, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+      else hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, false, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+    } else if (v) hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
     else hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, false>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
   }
 #undef ARGS
@@ -788,18 +818,25 @@ extern "C" int sdhip_affine_act_bn(const void* x, int ldx, void* y, int ldy, con
   SDHIP_CHECK_ARG(x && y && stats && scale && shift && mean_out && invstd_out && ldx >= C && ldy >= C && (!res || ldr >= C),
                   "affine_act_bn: bad pointers/strides");
   SDHIP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr) && count > 0., "affine_act_bn: bad statistics arguments");
+  SDHIP_CHECK_ARG(act == 0 || act == 1 || act == 2 || act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID, "affine_act_bn: activation %d", act);
   hipStream_t s = (hipStream_t)stream;
 #define ARGS(T) (const T*)x, ldx, (T*)y, ldy, (const T*)res, ldr, stats, ldc, nrep, gamma, beta, running_mean, running_var, \
                 scale, shift, mean_out, invstd_out, C, npix / G, count, eps, momentum, act
   if (dtype == SDHIP_F32) {
     const bool v = vec_rows<float>(C, {ldx, ldy, res ? ldr : 0}, {x, y, res});
     Plan pl = plan(v ? C / 4 : C, npix / G, G, tune_fused_blocks());
-    if (v) hipLaunchKernelGGL((affine_act_bn_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+    if (hard_act(act)) {
+      if (v) hipLaunchKernelGGL((affine_act_bn_kernel<float, true, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+      else hipLaunchKernelGGL((affine_act_bn_kernel<float, false, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+    } else if (v) hipLaunchKernelGGL((affine_act_bn_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
     else hipLaunchKernelGGL((affine_act_bn_kernel<float, false>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
   } else {
     const bool v = vec_rows<bf16_t>(C, {ldx, ldy, res ? ldr : 0}, {x, y, res});
     Plan pl = plan(v ? C / 8 : C, npix / G, G, tune_fused_blocks());
-    if (v) hipLaunchKernelGGL((affine_act_bn_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+    if (hard_act(act)) {
+      if (v) hipLaunchKernelGGL((affine_act_bn_kernel<bf16_t, true, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+      else hipLaunchKernelGGL((affine_act_bn_kernel<bf16_t, false, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+    } else if (v) hipLaunchKernelGGL((affine_act_bn_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
     else hipLaunchKernelGGL((affine_act_bn_kernel<bf16_t, false>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
   }
 #undef ARGS
@@ -817,7 +854,7 @@ static int bn_bwd_apply_fin_impl(const void* gy, int ldg, const void* x, int ldx
   if (int rc = check_rows("bn_bwd_apply_fin", npix, C, G, dtype)) return rc;
   SDHIP_CHECK_ARG(gy && x && gx && scale && shift && ((dscale && dshift) || dsum) && mean && invstd && ldg >= C && ldx >= C && ldgx >= C,
                   "bn_bwd_apply_fin: bad pointers/strides");
-  SDHIP_CHECK_ARG((act == 0 || act == 1 || act == 2) && count > 0. && (dgamma == nullptr) == (dbeta == nullptr),
+  SDHIP_CHECK_ARG((act == 0 || act == 1 || act == 2 || act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID) && count > 0. && (dgamma == nullptr) == (dbeta == nullptr),
                   "bn_bwd_apply_fin: bad arguments");
   hipStream_t s = (hipStream_t)stream;
 #define ARGS(T) (const T*)gy, ldg, (const T*)x, ldx, (T*)gx, ldgx, scale, shift, dscale, dshift, nrep, gamma, mean, invstd, \
@@ -825,12 +862,18 @@ static int bn_bwd_apply_fin_impl(const void* gy, int ldg, const void* x, int ldx
   if (dtype == SDHIP_F32) {
     const bool v = vec_rows<float>(C, {ldg, ldx, ldgx}, {gy, x, gx});
     Plan pl = plan(v ? C / 4 : C, npix / G, G, tune_fused_blocks());
-    if (v) hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+    if (hard_act(act)) {
+      if (v) hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<float, true, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+      else hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<float, false, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
+    } else if (v) hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
     else hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<float, false>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
   } else {
     const bool v = vec_rows<bf16_t>(C, {ldg, ldx, ldgx}, {gy, x, gx});
     Plan pl = plan(v ? C / 8 : C, npix / G, G, tune_fused_blocks());
-    if (v) hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+    if (hard_act(act)) {
+      if (v) hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<bf16_t, true, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+      else hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<bf16_t, false, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
+    } else if (v) hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
     else hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<bf16_t, false>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
   }
 #undef ARGS

@@ -1,0 +1,670 @@
+// MobileNetV3-Large operators for gfx950: depthwise convolution (forward, data gradient, weight gradient) and the
+// squeeze-excite MLP (models/mobilenetv3.py:64-77,99,110).
+//
+// Depthwise layers are memory / latency bound (k*k FMAs per loaded element): plain VALU FMA in f32, no MFMA.
+//   * a thread owns one 16-byte channel chunk (8 bf16 / 4 f32; element-wise when C, ld or a pointer is not 16-byte
+//     aligned) and R = 4 neighbouring outputs of one row: a source column is loaded once per kernel row and feeds every
+//     output of the strip it reaches (for k = 3 / stride 1: 6 loads per row for 4 outputs instead of 12);
+//   * the block's weights are staged in LDS as [tap][channel] (the parameter is (C, 1, k, k)), so a thread reads the k
+//     weights of a row as 16-byte LDS vectors;
+//   * the data gradient is the same gather with the roles of input and output exchanged: a stride-2 layer reads, per
+//     input pixel, only the ceil(k/2)^2 output pixels whose taps reach it (the column / tap pairing is resolved at
+//     compile time from the strip's parity), without zero-stuffing and without atomics;
+//   * the forward epilogue sums (x, x^2) per statistics group for the BatchNorm behind the layer (a block reduction in LDS,
+//     one f64 atomic per block and channel) and, optionally, x per image for SELayer's average pool: each block stores its
+//     partial sums in a slot of its own, and the SE kernel adds the slots in a fixed order (deterministic);
+//   * the weight gradient stores per-block partials [block][tap][channel] (no atomics) and a second launch sums them in a
+//     fixed order into the (C, 1, k, k) parameter gradient.
+#include "sdhip_common.h"
+
+namespace {
+
+constexpr int DW_R = 4;   // outputs per thread along W
+
+struct DwGeom {
+  int tx, ty, units;      // threads across channel units / across strips; channel units (16-byte chunks or elements)
+};
+
+inline DwGeom dw_geom(int units) {
+  DwGeom g;
+  g.units = units;
+  g.tx = units < 64 ? units : 64;
+  g.ty = 256 / g.tx;
+  return g;
+}
+
+__host__ __device__ constexpr int dw_kw(bool bwd, int K, int S, int d, int r) {
+  // tap column pairing source column d (relative) with strip output r; see dw_gather
+  return bwd ? r + (K - 1) / 2 - S * d : d + (K - 1) / 2 - S * r;
+}
+
+__host__ __device__ constexpr bool dw_col_used(bool bwd, int K, int S, int d) {
+  for (int r = 0; r < DW_R; ++r) {
+    const int kw = dw_kw(bwd, K, S, d, r);
+    if (kw >= 0 && kw < K) return true;
+  }
+  return false;
+}
+
+// Stage w (C, k*k) f32 of channels [cb0, cb0 + nch) as wl[t][nch] (zero beyond C).
+__device__ __forceinline__ void dw_stage_weights(const float* __restrict__ w, float* wl, int cb0, int nch, int C, int KK) {
+  for (int i = threadIdx.x; i < nch * KK; i += blockDim.x) {
+    const int cl = i / KK, t = i - cl * KK;
+    const int c = cb0 + cl;
+    wl[t * nch + cl] = c < C ? w[(long)c * KK + t] : 0.f;
+  }
+}
+
+// One strip of DW_R outputs (row `orow`, columns o0 .. o0+R-1 of an image) gathered from the source image.
+//   forward : out = y (Ho x Wo), src = x (H x W):   src row  = orow*S - P + kh,  src col = o0*S + d,  kw = d + P - S*r
+//   backward: out = gx (H x W), src = gy (Ho x Wo): src row  = (orow + P - kh)/S when integral,  src col = o0/S + d,
+//             kw = r + P - S*d   (o0 is a multiple of R, hence of S)
+template <typename T, bool VEC, int K, int S, bool BWD>
+__device__ __forceinline__ void dw_gather(const T* __restrict__ src, int lds, int SH, int SW, const float* wl, int nch, int cl,
+                                          int orow, int o0, float (&acc)[DW_R][Unit<T, VEC>::N]) {
+  constexpr int N = Unit<T, VEC>::N;
+  constexpr int P = (K - 1) / 2;
+  constexpr int DLO = BWD ? -K : -P;
+  constexpr int DHI = BWD ? DW_R + P : (DW_R - 1) * S + K - 1 - P;
+#pragma unroll
+  for (int r = 0; r < DW_R; ++r)
+#pragma unroll
+    for (int e = 0; e < N; ++e) acc[r][e] = 0.f;
+#pragma unroll
+  for (int kh = 0; kh < K; ++kh) {
+    int srow;
+    if constexpr (BWD) {
+      const int t = orow + P - kh;
+      if (t < 0 || (S == 2 && (t & 1))) continue;
+      srow = t / S;
+    } else {
+      srow = orow * S - P + kh;
+    }
+    if (srow < 0 || srow >= SH) continue;
+    float wr[K][N];
+#pragma unroll
+    for (int kw = 0; kw < K; ++kw)
+#pragma unroll
+      for (int e = 0; e < N; ++e) wr[kw][e] = wl[(kh * K + kw) * nch + cl + e];
+    const T* rowp = src + (long)srow * SW * lds;
+    const int cbase = BWD ? o0 / S : o0 * S;
+#pragma unroll
+    for (int d = DLO; d <= DHI; ++d) {
+      if (!dw_col_used(BWD, K, S, d)) continue;
+      const int scol = cbase + d;
+      if (scol < 0 || scol >= SW) continue;
+      float v[N];
+      Unit<T, VEC>::load(rowp + (long)scol * lds, v);
+#pragma unroll
+      for (int r = 0; r < DW_R; ++r) {
+        const int kw = dw_kw(BWD, K, S, d, r);
+        if (kw >= 0 && kw < K) {
+#pragma unroll
+          for (int e = 0; e < N; ++e) acc[r][e] = fmaf(v[e], wr[kw][e], acc[r][e]);
+        }
+      }
+    }
+  }
+}
+
+// Forward (BWD = false) and data gradient (BWD = true).  grid: (strip blocks, channel-unit groups, images).
+template <typename T, bool VEC, int K, int S, bool BWD>
+__global__ __launch_bounds__(256) void dw_conv_kernel(const T* __restrict__ src, int lds, const float* __restrict__ w,
+                                                      T* __restrict__ out, int ldo, double* __restrict__ stats, int sld, int nrep,
+                                                      float* __restrict__ pool, int pool_parts, int SH, int SW, int OH, int OW, int C,
+                                                      int imgs_per_group, DwGeom dg) {
+  constexpr int N = Unit<T, VEC>::N;
+  constexpr int KK = K * K;
+  constexpr int WL = KK * 64 * N;
+  constexpr int RED = 2 * 256 * N;
+  __shared__ float lds_buf[WL > RED ? WL : RED];
+  const int nch = dg.tx * N;
+  const int cb0 = blockIdx.y * nch;
+  dw_stage_weights(w, lds_buf, cb0, nch, C, KK);
+  __syncthreads();
+  const int tx = threadIdx.x % dg.tx, ty = threadIdx.x / dg.tx;
+  const int u = blockIdx.y * dg.tx + tx;
+  const int b = blockIdx.z;
+  const int nstrip_row = (OW + DW_R - 1) / DW_R;
+  const int q = blockIdx.x * dg.ty + ty;
+  const bool live = ty < dg.ty && u < dg.units && q < OH * nstrip_row;
+  const int c0 = u * N;
+  float s1[N], s2[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
+  if (live) {
+    const int orow = q / nstrip_row;
+    const int o0 = (q - orow * nstrip_row) * DW_R;
+    float acc[DW_R][N];
+    dw_gather<T, VEC, K, S, BWD>(src + (long)b * SH * SW * lds + c0, lds, SH, SW, lds_buf, nch, tx * N, orow, o0, acc);
+    T* op = out + ((long)b * OH + orow) * OW * ldo + c0;
+#pragma unroll
+    for (int r = 0; r < DW_R; ++r) {
+      if (o0 + r < OW) {
+        float f[N];
+#pragma unroll
+        for (int e = 0; e < N; ++e) {
+          f[e] = Elem<T>::rnd(acc[r][e]);
+          s1[e] += f[e];
+          s2[e] = fmaf(f[e], f[e], s2[e]);
+        }
+        Unit<T, VEC>::store(op + (long)(o0 + r) * ldo, f);
+      }
+    }
+  }
+  if (BWD || (!stats && !pool)) return;   // uniform
+  __syncthreads();                         // the weight tile is dead: its LDS takes the block reduction
+  float* r1 = lds_buf;
+  float* r2 = lds_buf + 256 * N;
+#pragma unroll
+  for (int e = 0; e < N; ++e) { r1[threadIdx.x * N + e] = s1[e]; r2[threadIdx.x * N + e] = s2[e]; }
+  __syncthreads();
+  // thread i < nch sums channel cb0 + i over the ty rows
+  for (int i = threadIdx.x; i < nch; i += blockDim.x) {
+    const int c = cb0 + i;
+    if (c >= C) continue;
+    const int txi = i / N, e = i - txi * N;
+    float a = 0.f, q2 = 0.f;
+    for (int y = 0; y < dg.ty; ++y) {
+      a += r1[(y * dg.tx + txi) * N + e];
+      q2 += r2[(y * dg.tx + txi) * N + e];
+    }
+    if (stats) {
+      const int g = b / imgs_per_group;
+      double* sp = stats + ((long)(blockIdx.x % nrep) * (gridDim.z / imgs_per_group) + g) * 2 * sld;
+      atomicAdd(sp + c, (double)a);
+      atomicAdd(sp + sld + c, (double)q2);
+    }
+    if (pool) pool[((long)b * pool_parts + blockIdx.x) * C + c] = a;   // slot blockIdx.x of image b
+  }
+}
+
+// Weight gradient: block (strip blocks, channel-unit groups, kernel row kh); each thread walks strips of the whole batch,
+// accumulating the K taps of row kh for its N channels in registers; LDS reduction over the strip rows, then the block
+// stores its partial sums to part[blockIdx.x][kh*K + kw][c] (channel-contiguous, every element written by one block).
+template <typename T, bool VEC, int K, int S>
+__global__ __launch_bounds__(256) void dw_wgrad_kernel(const T* __restrict__ x, int ldx, const T* __restrict__ gy, int ldg,
+                                                       float* __restrict__ part, int B, int H, int W, int Ho, int Wo, int C, DwGeom dg) {
+  constexpr int N = Unit<T, VEC>::N;
+  constexpr int P = (K - 1) / 2;
+  __shared__ float red[256 * K * N];
+  const int tx = threadIdx.x % dg.tx, ty = threadIdx.x / dg.tx;
+  const int u = blockIdx.y * dg.tx + tx;
+  const int kh = blockIdx.z;
+  const int nstrip_row = (Wo + DW_R - 1) / DW_R;
+  const long nstrip = (long)B * Ho * nstrip_row;
+  const int c0 = u * N;
+  float acc[K][N];
+#pragma unroll
+  for (int kw = 0; kw < K; ++kw)
+#pragma unroll
+    for (int e = 0; e < N; ++e) acc[kw][e] = 0.f;
+  if (ty < dg.ty && u < dg.units) {
+    for (long q = (long)blockIdx.x * dg.ty + ty; q < nstrip; q += (long)gridDim.x * dg.ty) {
+      const int b = (int)(q / ((long)Ho * nstrip_row));
+      const int rem = (int)(q - (long)b * Ho * nstrip_row);
+      const int oh = rem / nstrip_row;
+      const int o0 = (rem - oh * nstrip_row) * DW_R;
+      const int ih = oh * S - P + kh;
+      if (ih < 0 || ih >= H) continue;
+      float g[DW_R][N];
+      const T* gp = gy + ((long)b * Ho + oh) * Wo * ldg + c0;
+#pragma unroll
+      for (int r = 0; r < DW_R; ++r) {
+        if (o0 + r < Wo) Unit<T, VEC>::load(gp + (long)(o0 + r) * ldg, g[r]);
+        else {
+#pragma unroll
+          for (int e = 0; e < N; ++e) g[r][e] = 0.f;
+        }
+      }
+      const T* xr = x + ((long)b * H + ih) * W * ldx + c0;
+#pragma unroll
+      for (int d = -P; d <= (DW_R - 1) * S + K - 1 - P; ++d) {
+        const int col = o0 * S + d;
+        if (col < 0 || col >= W) continue;
+        float v[N];
+        Unit<T, VEC>::load(xr + (long)col * ldx, v);
+#pragma unroll
+        for (int r = 0; r < DW_R; ++r) {
+          const int kw = d + P - S * r;
+          if (kw >= 0 && kw < K) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) acc[kw][e] = fmaf(v[e], g[r][e], acc[kw][e]);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int kw = 0; kw < K; ++kw)
+#pragma unroll
+    for (int e = 0; e < N; ++e) red[(kw * 256 + threadIdx.x) * N + e] = acc[kw][e];
+  __syncthreads();
+  const int nch = dg.tx * N;
+  const int cb0 = blockIdx.y * nch;
+  for (int i = threadIdx.x; i < nch * K; i += blockDim.x) {
+    const int kw = i / nch, cl = i - kw * nch;
+    const int c = cb0 + cl;
+    if (c >= C) continue;
+    const int txi = cl / N, e = cl - txi * N;
+    float a = 0.f;
+    for (int y = 0; y < dg.ty; ++y) a += red[(kw * 256 + y * dg.tx + txi) * N + e];
+    part[((long)blockIdx.x * K * K + kh * K + kw) * C + c] = a;
+  }
+}
+
+// dw[c][t] += sum over the partial slots in a fixed order (deterministic): a block serves 32 consecutive (t, c) outputs with
+// 8 lanes each; lane j sums the slots p = j, j + 8, ... in order, and the 8 lane sums are added in lane order.
+__global__ __launch_bounds__(256) void dw_wgrad_sum_kernel(const float* __restrict__ part, int nparts, float* __restrict__ dw, int KK,
+                                                           int C) {
+  __shared__ float red[8][32];
+  const int o = threadIdx.x & 31, j = threadIdx.x >> 5;
+  const long i = (long)blockIdx.x * 32 + o;
+  const long n = (long)KK * C;
+  float a = 0.f;
+  if (i < n)
+    for (int p = j; p < nparts; p += 8) a += part[(long)p * n + i];
+  red[j][o] = a;
+  __syncthreads();
+  if (j == 0 && i < n) {
+#pragma unroll
+    for (int q = 1; q < 8; ++q) a += red[q][o];
+    const int t = (int)(i / C), c = (int)(i - (long)t * C);
+    dw[(long)c * KK + t] += a;
+  }
+}
+
+template <typename T>
+bool dw_vec(int C, int ld1, int ld2, const void* p1, const void* p2) {
+  constexpr int N = Chunk<T>::N;
+  return C % N == 0 && ld1 % N == 0 && ld2 % N == 0 && ((uintptr_t)p1 & 15) == 0 && ((uintptr_t)p2 & 15) == 0;
+}
+
+template <typename T, bool VEC, int K, int S, bool BWD>
+void dw_launch(const void* src, int lds, const float* w, void* out, int ldo, double* stats, int sld, int nrep, float* pool,
+               int pool_parts, int B, int SH, int SW, int OH, int OW, int C, int ipg, hipStream_t s) {
+  const DwGeom dg = dw_geom(VEC ? C / Unit<T, VEC>::N : C);
+  const int nstrip = OH * ((OW + DW_R - 1) / DW_R);
+  dim3 grid((unsigned)sdhip_cdiv(nstrip, dg.ty), (unsigned)sdhip_cdiv(dg.units, dg.tx), (unsigned)B);
+  hipLaunchKernelGGL((dw_conv_kernel<T, VEC, K, S, BWD>), grid, dim3(256), 0, s, (const T*)src, lds, w, (T*)out, ldo, stats, sld,
+                     nrep, pool, pool_parts, SH, SW, OH, OW, C, ipg, dg);
+}
+
+template <typename T, bool BWD>
+void dw_dispatch(bool vec, int k, int stride, const void* src, int lds, const float* w, void* out, int ldo, double* stats, int sld,
+                 int nrep, float* pool, int pool_parts, int B, int SH, int SW, int OH, int OW, int C, int ipg, hipStream_t s) {
+#define DW_CASE(V, K, S) if (vec == V && k == K && stride == S) \
+    return dw_launch<T, V, K, S, BWD>(src, lds, w, out, ldo, stats, sld, nrep, pool, pool_parts, B, SH, SW, OH, OW, C, ipg, s)
+  DW_CASE(true, 3, 1); DW_CASE(true, 3, 2); DW_CASE(true, 5, 1); DW_CASE(true, 5, 2);
+  DW_CASE(false, 3, 1); DW_CASE(false, 3, 2); DW_CASE(false, 5, 1); DW_CASE(false, 5, 2);
+#undef DW_CASE
+}
+
+inline int dw_out(int n, int k, int s) { return (n + 2 * ((k - 1) / 2) - k) / s + 1; }
+
+// strip blocks of the weight gradient: ~16 K (strip x channel) items each, at most 256 (independent of the vector path, so
+// that the caller can size the partial slab from the shape alone)
+inline int dw_wgrad_parts(int B, int H, int W, int C, int k, int stride) {
+  const long nstrip = (long)B * dw_out(H, k, stride) * ((dw_out(W, k, stride) + DW_R - 1) / DW_R);
+  long bx = (nstrip * C + 16383) / 16384;
+  return (int)(bx < 1 ? 1 : (bx > 256 ? 256 : bx));
+}
+
+template <typename T, bool VEC, int K, int S>
+void dw_wgrad_launch(const void* x, int ldx, const void* gy, int ldg, float* part, int nparts, int B, int H, int W, int Ho, int Wo,
+                     int C, hipStream_t s) {
+  const DwGeom dg = dw_geom(VEC ? C / Unit<T, VEC>::N : C);
+  dim3 grid((unsigned)nparts, (unsigned)sdhip_cdiv(dg.units, dg.tx), (unsigned)K);
+  hipLaunchKernelGGL((dw_wgrad_kernel<T, VEC, K, S>), grid, dim3(256), 0, s, (const T*)x, ldx, (const T*)gy, ldg, part, B, H, W, Ho,
+                     Wo, C, dg);
+}
+
+template <typename T>
+void dw_wgrad_dispatch(bool vec, int k, int stride, const void* x, int ldx, const void* gy, int ldg, float* part, int nparts, int B,
+                       int H, int W, int Ho, int Wo, int C, hipStream_t s) {
+#define DW_CASE(V, K, S) if (vec == V && k == K && stride == S) \
+    return dw_wgrad_launch<T, V, K, S>(x, ldx, gy, ldg, part, nparts, B, H, W, Ho, Wo, C, s)
+  DW_CASE(true, 3, 1); DW_CASE(true, 3, 2); DW_CASE(true, 5, 1); DW_CASE(true, 5, 2);
+  DW_CASE(false, 3, 1); DW_CASE(false, 3, 2); DW_CASE(false, 5, 1); DW_CASE(false, 5, 2);
+#undef DW_CASE
+}
+
+// pool slots of the forward: its strip-block count on the vector or the element-wise path, whichever is larger
+inline int dw_pool_parts(int H, int W, int C, int k, int stride, int dtype) {
+  const int Ho = dw_out(H, k, stride), Wo = dw_out(W, k, stride);
+  const int nstrip = Ho * ((Wo + DW_R - 1) / DW_R);
+  const int N = dtype == SDHIP_F32 ? 4 : 8;
+  int parts = sdhip_cdiv(nstrip, dw_geom(C).ty);
+  if (C % N == 0) {
+    const int pv = sdhip_cdiv(nstrip, dw_geom(C / N).ty);
+    if (pv > parts) parts = pv;
+  }
+  return parts;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- SE MLP
+// One launch per direction; a block serves SE_IMGS images, so each weight row read from L2 feeds SE_IMGS dot products and
+// each parameter-gradient atomic carries the sum of SE_IMGS images.  Rows of w1 (r, C) are read across lanes (coalesced);
+// w2 (C, r) is read with lanes across r.
+constexpr int SE_IMGS = 4;
+constexpr int SE_MAXC = 1024;   // LDS capacity per image (largest SELayer: 960 channels, 240 hidden)
+constexpr int SE_THREADS = 1024;   // 16 waves: the MLP is latency bound (a few rows per wave, unrolled independent loads)
+constexpr int SE_WAVES = SE_THREADS / 64;
+
+__global__ __launch_bounds__(SE_THREADS) void se_fwd_kernel(const float* __restrict__ pool, int parts, float inv_hw,
+                                                     const float* __restrict__ scale,
+                                                     const float* __restrict__ shift, int imgs_per_group,
+                                                     const float* __restrict__ w1, const float* __restrict__ b1,
+                                                     const float* __restrict__ w2, const float* __restrict__ b2,
+                                                     float* __restrict__ s_out, float* __restrict__ ws, int B, int C, int r) {
+  __shared__ float v[SE_IMGS][SE_MAXC];
+  __shared__ float h[SE_IMGS][SE_MAXC / 4];
+  const int b0 = blockIdx.x * SE_IMGS;
+  const int nimg = min(SE_IMGS, B - b0);
+  float* ws_v = ws;
+  float* ws_h = ws + (long)B * C;
+  float* ws_a = ws_h + (long)B * r;
+  for (int i = threadIdx.x; i < SE_IMGS * C; i += blockDim.x) {
+    const int m = i / C, c = i - m * C;
+    float val = 0.f;
+    if (m < nimg) {
+      const int b = b0 + m;
+      for (int p = 0; p < parts; ++p) val += pool[((long)b * parts + p) * C + c];   // slot order: deterministic
+      val *= inv_hw;
+      if (scale) {
+        const int g = b / imgs_per_group;
+        val = fmaf(val, scale[(long)g * C + c], shift[(long)g * C + c]);
+      }
+      ws_v[(long)b * C + c] = val;
+    }
+    v[m][c] = val;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int j = wave; j < r; j += SE_WAVES) {   // fc1: a wave per hidden unit, lanes across C
+    float a[SE_IMGS] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int c = lane; c < C; c += 64) {
+      const float wv = w1[(long)j * C + c];
+#pragma unroll
+      for (int m = 0; m < SE_IMGS; ++m) a[m] = fmaf(wv, v[m][c], a[m]);
+    }
+#pragma unroll
+    for (int m = 0; m < SE_IMGS; ++m) {
+      const float t = fmaxf(wave_sum(a[m]) + b1[j], 0.f);
+      if (lane == 0) {
+        h[m][j] = t;
+        if (m < nimg) ws_h[(long)(b0 + m) * r + j] = t;
+      }
+    }
+  }
+  __syncthreads();
+  for (int c = wave; c < C; c += SE_WAVES) {   // fc2: a wave per channel, lanes across r
+    float a[SE_IMGS] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int j = lane; j < r; j += 64) {
+      const float wv = w2[(long)c * r + j];
+#pragma unroll
+      for (int m = 0; m < SE_IMGS; ++m) a[m] = fmaf(wv, h[m][j], a[m]);
+    }
+#pragma unroll
+    for (int m = 0; m < SE_IMGS; ++m) {
+      const float t = wave_sum(a[m]) + b2[c];
+      if (lane == 0 && m < nimg) {
+        ws_a[(long)(b0 + m) * C + c] = t;
+        s_out[(long)(b0 + m) * C + c] = hsig_f(t);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(SE_THREADS) void se_bwd_kernel(const float* __restrict__ ds, int nrep, const float* __restrict__ ws,
+                                                     const float* __restrict__ w1, const float* __restrict__ w2,
+                                                     float* __restrict__ gw1, float* __restrict__ gb1, float* __restrict__ gw2,
+                                                     float* __restrict__ gb2, float* __restrict__ gpool, float inv_hw,
+                                                     int B, int C, int r) {
+  __shared__ float da2[SE_IMGS][SE_MAXC];
+  __shared__ float hh[SE_IMGS][SE_MAXC / 4];
+  __shared__ float da1[SE_IMGS][SE_MAXC / 4];
+  __shared__ float dhp[SE_THREADS / 256][SE_IMGS][SE_MAXC / 4];   // partial dh of each quarter of the channels
+  const int b0 = blockIdx.x * SE_IMGS;
+  const int nimg = min(SE_IMGS, B - b0);
+  const float* ws_v = ws;
+  const float* ws_h = ws + (long)B * C;
+  const float* ws_a = ws_h + (long)B * r;
+  for (int i = threadIdx.x; i < SE_IMGS * C; i += blockDim.x) {
+    const int m = i / C, c = i - m * C;
+    float g = 0.f;
+    if (m < nimg) {
+      const long bc = (long)(b0 + m) * C + c;
+      float sum = 0.f;
+      for (int k = 0; k < nrep; ++k) sum += ds[(long)k * B * C + bc];
+      g = sum * act_hs_d(ws_a[bc], SDHIP_ACT_HSIGMOID);
+    }
+    da2[m][c] = g;
+  }
+  for (int i = threadIdx.x; i < SE_IMGS * r; i += blockDim.x) {
+    const int m = i / r, j = i - m * r;
+    hh[m][j] = m < nimg ? ws_h[(long)(b0 + m) * r + j] : 0.f;
+  }
+  __syncthreads();
+  // fc2: gb2[c] += sum_m da2, gw2[c][j] += sum_m da2[m][c] h[m][j]; dh[m][j] = sum_c w2[c][j] da2[m][c]  (thread per j)
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    float a = 0.f;
+#pragma unroll
+    for (int m = 0; m < SE_IMGS; ++m) a += da2[m][c];
+    atomicAdd(gb2 + c, a);
+  }
+  {
+    const int j = threadIdx.x % 256, qr = threadIdx.x / 256;     // hidden unit, quarter of the channel range
+    const int cq0 = (int)((long)C * qr / (SE_THREADS / 256)), cq1 = (int)((long)C * (qr + 1) / (SE_THREADS / 256));
+    float dh[SE_IMGS] = {0.f, 0.f, 0.f, 0.f};
+    if (j < r) {
+      float hj[SE_IMGS];
+#pragma unroll
+      for (int m = 0; m < SE_IMGS; ++m) hj[m] = hh[m][j];
+#pragma unroll 4
+      for (int c = cq0; c < cq1; ++c) {
+        const float wv = w2[(long)c * r + j];
+        float gsum = 0.f;
+#pragma unroll
+        for (int m = 0; m < SE_IMGS; ++m) {
+          dh[m] = fmaf(wv, da2[m][c], dh[m]);
+          gsum = fmaf(da2[m][c], hj[m], gsum);
+        }
+        atomicAdd(gw2 + (long)c * r + j, gsum);
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < SE_IMGS; ++m) dhp[qr][m][j] = dh[m];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < SE_IMGS * r; i += blockDim.x) {
+    const int m = i / r, j = i - m * r;
+    float dh = 0.f;
+#pragma unroll
+    for (int q = 0; q < SE_THREADS / 256; ++q) dh += dhp[q][m][j];
+    da1[m][j] = hh[m][j] > 0.f ? dh : 0.f;
+  }
+  __syncthreads();
+  // fc1: gb1[j] += sum_m da1, gw1[j][c] += sum_m da1[m][j] v[m][c]; dv[m][c] = sum_j w1[j][c] da1[m][j]  (thread per c)
+  for (int j = threadIdx.x; j < r; j += blockDim.x) {
+    float a = 0.f;
+#pragma unroll
+    for (int m = 0; m < SE_IMGS; ++m) a += da1[m][j];
+    atomicAdd(gb1 + j, a);
+  }
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    float vc[SE_IMGS], dv[SE_IMGS] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int m = 0; m < SE_IMGS; ++m) vc[m] = m < nimg ? ws_v[(long)(b0 + m) * C + c] : 0.f;
+#pragma unroll 4
+    for (int j = 0; j < r; ++j) {
+      const float wv = w1[(long)j * C + c];
+      float gsum = 0.f;
+#pragma unroll
+      for (int m = 0; m < SE_IMGS; ++m) {
+        dv[m] = fmaf(wv, da1[m][j], dv[m]);
+        gsum = fmaf(da1[m][j], vc[m], gsum);
+      }
+      atomicAdd(gw1 + (long)j * C + c, gsum);
+    }
+#pragma unroll
+    for (int m = 0; m < SE_IMGS; ++m)
+      if (m < nimg) gpool[(long)(b0 + m) * C + c] = dv[m] * inv_hw;
+  }
+}
+
+// gx = gy * act'(x*s) * s + gadd   (per image b = blockIdx.z)
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void se_scale_bwd_kernel(const T* __restrict__ gy, int ldg, const T* __restrict__ x, int ldx,
+                                                           T* __restrict__ gx, int ldgx, const float* __restrict__ s,
+                                                           const float* __restrict__ gadd, long npix, int C, int act, DwGeom dg) {
+  constexpr int N = Unit<T, VEC>::N;
+  const int tx = threadIdx.x % dg.tx, ty = threadIdx.x / dg.tx;
+  const int u = blockIdx.y * dg.tx + tx;
+  if (ty >= dg.ty || u >= dg.units) return;
+  const int b = blockIdx.z, c0 = u * N;
+  float sc[N], ad[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) { sc[e] = s[(long)b * C + c0 + e]; ad[e] = gadd ? gadd[(long)b * C + c0 + e] : 0.f; }
+  const long base = (long)b * npix;
+  for (long p = (long)blockIdx.x * dg.ty + ty; p < npix; p += (long)gridDim.x * dg.ty) {
+    float g[N], xv[N];
+    Unit<T, VEC>::load(gy + (base + p) * ldg + c0, g);
+    Unit<T, VEC>::load(x + (base + p) * ldx + c0, xv);
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+      const float z = xv[e] * sc[e];
+      float gm = g[e];
+      if (act == 1) gm = z > 0.f ? gm : 0.f;
+      else if (act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID) gm *= act_hs_d(z, act);
+      g[e] = fmaf(gm, sc[e], ad[e]);
+    }
+    Unit<T, VEC>::store(gx + (base + p) * ldgx + c0, g);
+  }
+}
+
+}  // namespace
+
+extern "C" int sdhip_dw_pool_parts(int H, int W, int C, int k, int stride, int dtype) {
+  if (H <= 0 || W <= 0 || C <= 0 || (k != 3 && k != 5) || (stride != 1 && stride != 2)) return SDHIP_ERR_ARG;
+  return dw_pool_parts(H, W, C, k, stride, dtype);
+}
+
+extern "C" int sdhip_dw_wgrad_parts(int B, int H, int W, int C, int k, int stride) {
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (k != 3 && k != 5) || (stride != 1 && stride != 2)) return SDHIP_ERR_ARG;
+  return dw_wgrad_parts(B, H, W, C, k, stride);
+}
+
+extern "C" int sdhip_dw_conv_fwd(const void* x, int ldx, const float* w, void* y, int ldy, double* stats, int sld, int nrep, float* pool,
+                                 int pool_parts, int B, int H, int W, int C, int k, int stride, int groups, int dtype, void* stream) {
+  SDHIP_CHECK_ARG(x && w && y, "dw_conv_fwd: null pointer");
+  SDHIP_CHECK_ARG((k == 3 || k == 5) && (stride == 1 || stride == 2), "dw_conv_fwd: k=%d stride=%d (3/5, 1/2 only)", k, stride);
+  SDHIP_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && ldx >= C && ldy >= C, "dw_conv_fwd: bad shape/strides");
+  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "dw_conv_fwd: dtype %d", dtype);
+  SDHIP_CHECK_ARG(groups > 0 && B % groups == 0, "dw_conv_fwd: groups %d does not divide B %d", groups, B);
+  if (nrep < 1) nrep = 1;
+  if (sld <= 0) sld = C;
+  SDHIP_CHECK_ARG(!stats || sld >= C, "dw_conv_fwd: statistics stride");
+  SDHIP_CHECK_ARG(!pool || pool_parts >= dw_pool_parts(H, W, C, k, stride, dtype), "dw_conv_fwd: %d pool slots, %d needed", pool_parts,
+                  dw_pool_parts(H, W, C, k, stride, dtype));
+  const int Ho = dw_out(H, k, stride), Wo = dw_out(W, k, stride);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == SDHIP_F32)
+    dw_dispatch<float, false>(dw_vec<float>(C, ldx, ldy, x, y), k, stride, x, ldx, w, y, ldy, stats, sld, nrep, pool, pool_parts, B, H,
+                              W, Ho, Wo, C, B / groups, s);
+  else
+    dw_dispatch<bf16_t, false>(dw_vec<bf16_t>(C, ldx, ldy, x, y), k, stride, x, ldx, w, y, ldy, stats, sld, nrep, pool, pool_parts, B,
+                               H, W, Ho, Wo, C, B / groups, s);
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}
+
+extern "C" int sdhip_dw_conv_dgrad(const void* gy, int ldg, const float* w, void* gx, int ldgx,
+                                   int B, int H, int W, int C, int k, int stride, int dtype, void* stream) {
+  SDHIP_CHECK_ARG(gy && w && gx, "dw_conv_dgrad: null pointer");
+  SDHIP_CHECK_ARG((k == 3 || k == 5) && (stride == 1 || stride == 2), "dw_conv_dgrad: k=%d stride=%d (3/5, 1/2 only)", k, stride);
+  SDHIP_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && ldg >= C && ldgx >= C, "dw_conv_dgrad: bad shape/strides");
+  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "dw_conv_dgrad: dtype %d", dtype);
+  const int Ho = dw_out(H, k, stride), Wo = dw_out(W, k, stride);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == SDHIP_F32)
+    dw_dispatch<float, true>(dw_vec<float>(C, ldg, ldgx, gy, gx), k, stride, gy, ldg, w, gx, ldgx, nullptr, 0, 1, nullptr, 0, B, Ho,
+                             Wo, H, W, C, 1, s);
+  else
+    dw_dispatch<bf16_t, true>(dw_vec<bf16_t>(C, ldg, ldgx, gy, gx), k, stride, gy, ldg, w, gx, ldgx, nullptr, 0, 1, nullptr, 0, B,
+                              Ho, Wo, H, W, C, 1, s);
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}
+
+extern "C" int sdhip_dw_conv_wgrad(const void* x, int ldx, const void* gy, int ldg, float* dw, float* part, int nparts,
+                                   int B, int H, int W, int C, int k, int stride, int dtype, void* stream) {
+  SDHIP_CHECK_ARG(x && gy && dw && part, "dw_conv_wgrad: null pointer");
+  SDHIP_CHECK_ARG((k == 3 || k == 5) && (stride == 1 || stride == 2), "dw_conv_wgrad: k=%d stride=%d (3/5, 1/2 only)", k, stride);
+  SDHIP_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && ldx >= C && ldg >= C, "dw_conv_wgrad: bad shape/strides");
+  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "dw_conv_wgrad: dtype %d", dtype);
+  SDHIP_CHECK_ARG(nparts == dw_wgrad_parts(B, H, W, C, k, stride), "dw_conv_wgrad: %d partial slots, sdhip_dw_wgrad_parts says %d",
+                  nparts, dw_wgrad_parts(B, H, W, C, k, stride));
+  const int Ho = dw_out(H, k, stride), Wo = dw_out(W, k, stride);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == SDHIP_F32)
+    dw_wgrad_dispatch<float>(dw_vec<float>(C, ldx, ldg, x, gy), k, stride, x, ldx, gy, ldg, part, nparts, B, H, W, Ho, Wo, C, s);
+  else
+    dw_wgrad_dispatch<bf16_t>(dw_vec<bf16_t>(C, ldx, ldg, x, gy), k, stride, x, ldx, gy, ldg, part, nparts, B, H, W, Ho, Wo, C, s);
+  SDHIP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(dw_wgrad_sum_kernel, dim3((unsigned)sdhip_cdiv((long)k * k * C, 32)), dim3(256), 0, s, part, nparts, dw, k * k, C);
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}
+
+extern "C" int sdhip_se_fwd(const float* pool, int pool_parts, float inv_hw, const float* scale, const float* shift, int groups,
+                            const float* w1, const float* b1, const float* w2, const float* b2, float* s, float* ws,
+                            int B, int C, int r, void* stream) {
+  SDHIP_CHECK_ARG(pool && w1 && b1 && w2 && b2 && s && ws, "se_fwd: null pointer");
+  SDHIP_CHECK_ARG((scale == nullptr) == (shift == nullptr), "se_fwd: scale/shift must come together");
+  SDHIP_CHECK_ARG(B > 0 && C > 0 && C <= SE_MAXC && r > 0 && r <= SE_MAXC / 4, "se_fwd: C=%d r=%d (C <= %d, r <= %d)", C, r, SE_MAXC,
+                  SE_MAXC / 4);
+  SDHIP_CHECK_ARG(groups > 0 && B % groups == 0 && pool_parts > 0, "se_fwd: groups %d, B %d, pool slots %d", groups, B, pool_parts);
+  hipLaunchKernelGGL(se_fwd_kernel, dim3((unsigned)sdhip_cdiv(B, SE_IMGS)), dim3(SE_THREADS), 0, (hipStream_t)stream, pool, pool_parts,
+                     inv_hw, scale, shift,
+                     B / groups, w1, b1, w2, b2, s, ws, B, C, r);
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}
+
+extern "C" int sdhip_se_bwd(const float* ds, int nrep, const float* ws, const float* w1, const float* w2,
+                            float* gw1, float* gb1, float* gw2, float* gb2, float* gpool, float inv_hw, int B, int C, int r, void* stream) {
+  SDHIP_CHECK_ARG(ds && ws && w1 && w2 && gw1 && gb1 && gw2 && gb2 && gpool, "se_bwd: null pointer");
+  SDHIP_CHECK_ARG(B > 0 && C > 0 && C <= SE_MAXC && r > 0 && r <= SE_MAXC / 4 && nrep > 0, "se_bwd: C=%d r=%d nrep=%d", C, r, nrep);
+  hipLaunchKernelGGL(se_bwd_kernel, dim3((unsigned)sdhip_cdiv(B, SE_IMGS)), dim3(SE_THREADS), 0, (hipStream_t)stream, ds, nrep, ws, w1, w2,
+                     gw1, gb1, gw2, gb2, gpool, inv_hw, B, C, r);
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}
+
+extern "C" int sdhip_se_scale_bwd(const void* gy, int ldg, const void* x, int ldx, void* gx, int ldgx, const float* s, const float* gadd,
+                                  long npix_img, int B, int C, int act, int dtype, void* stream) {
+  SDHIP_CHECK_ARG(gy && x && gx && s, "se_scale_bwd: null pointer");
+  SDHIP_CHECK_ARG(B > 0 && C > 0 && npix_img > 0 && ldg >= C && ldx >= C && ldgx >= C, "se_scale_bwd: bad shape/strides");
+  SDHIP_CHECK_ARG(act == 0 || act == 1 || act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID, "se_scale_bwd: activation %d", act);
+  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "se_scale_bwd: dtype %d", dtype);
+  hipStream_t st = (hipStream_t)stream;
+#define SE_LAUNCH(T, V) do { \
+    const DwGeom dg = dw_geom(V ? C / Chunk<T>::N : C); \
+    long bx = sdhip_cdiv(npix_img, (long)dg.ty * 4); if (bx > 256) bx = 256; \
+    dim3 grid((unsigned)bx, (unsigned)sdhip_cdiv(dg.units, dg.tx), (unsigned)B); \
+    hipLaunchKernelGGL((se_scale_bwd_kernel<T, V>), grid, dim3(256), 0, st, (const T*)gy, ldg, (const T*)x, ldx, (T*)gx, ldgx, s, gadd, \
+                       npix_img, C, act, dg); } while (0)
+  if (dtype == SDHIP_F32) {
+    const bool v = C % 4 == 0 && ldg % 4 == 0 && ldx % 4 == 0 && ldgx % 4 == 0 && (((uintptr_t)gy | (uintptr_t)x | (uintptr_t)gx) & 15) == 0;
+    if (v) SE_LAUNCH(float, true); else SE_LAUNCH(float, false);
+  } else {
+    const bool v = C % 8 == 0 && ldg % 8 == 0 && ldx % 8 == 0 && ldgx % 8 == 0 && (((uintptr_t)gy | (uintptr_t)x | (uintptr_t)gx) & 15) == 0;
+    if (v) SE_LAUNCH(bf16_t, true); else SE_LAUNCH(bf16_t, false);
+  }
+#undef SE_LAUNCH
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}

@@ -115,6 +115,17 @@ template <typename T, bool VEC> struct Unit {
   }
 };
 
+// ---- hard activations of MobileNetV3 (models/mobilenetv3.py:44-61): act codes SDHIP_ACT_HSWISH / SDHIP_ACT_HSIGMOID ----
+// h_sigmoid = relu6(x + 3) / 6, h_swish = x * h_sigmoid(x).  The derivatives are torch's composite of those ops: relu6' is
+// 0 at both kinks (hardtanh_backward masks x + 3 <= 0 and x + 3 >= 6), so h_swish'(-3) = 0 and h_swish'(3) = 1.
+__device__ __forceinline__ float hsig_f(float v) { return fminf(fmaxf(v + 3.f, 0.f), 6.f) / 6.f; }
+__device__ __forceinline__ float act_hs(float v, int act) { return act == SDHIP_ACT_HSWISH ? v * hsig_f(v) : hsig_f(v); }
+__device__ __forceinline__ float act_hs_d(float v, int act) {
+  const float t = v + 3.f;
+  const float m = (t > 0.f && t < 6.f) ? 1.f / 6.f : 0.f;
+  return act == SDHIP_ACT_HSWISH ? hsig_f(v) + v * m : m;
+}
+
 static inline int sdhip_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- zero fill as a KERNEL ------------------------------------------------------------------------------------------

@@ -205,6 +205,9 @@ class Conv2DownUp(nn.Module):
 
 # --------------------------------------------------------------------------- pyramids, heads, full network
 from .densenet import densenet121  # noqa: E402
+from .mobilenet import mobilenetv3_large  # noqa: E402
+
+BACKBONES = ('densenet', 'mobilenet')
 
 
 def _pool_branch(p, cin):
@@ -229,15 +232,21 @@ def _pyramid(branches, x, groups):
 
 
 class piramidNet2(nn.Module):
-    """models/dsnet_t2.py:1893-2083 (densenet backbone)."""
+    """models/dsnet_t2.py:1893-2083 (densenet and mobilenet backbones)."""
 
     def __init__(self, pretrained=False, backbone='densenet'):
         super().__init__()
-        if backbone != 'densenet':
-            raise NotImplementedError("only the densenet backbone (the shipped recipe) is on the native path")
+        if backbone not in BACKBONES:
+            raise NotImplementedError("backbone %r: only %s are on the native path" % (backbone, " and ".join(BACKBONES)))
         self.backbone = backbone
-        self.resnet_features = densenet121(pretrained)
-        pv, cin = [128, 64, 32, 16, 8], [64, 128, 256]
+        if backbone == 'mobilenet':
+            # the reference calls mobilenetv3_large() without `pretrained` (models/dsnet_t2.py:1935): the flag has no effect
+            self.resnet_features = mobilenetv3_large()
+            cin = [16, 24, 40]
+        else:
+            self.resnet_features = densenet121(pretrained)
+            cin = [64, 128, 256]
+        pv = [128, 64, 32, 16, 8]
         for j in range(5):
             setattr(self, 'branch0_%d' % j, _pool_branch(pv[j], cin[0]))
         for j in range(4):
@@ -284,29 +293,45 @@ class segNet(nn.Module):
 
 
 class minidsnetExt(nn.Module):
-    """models/dsnet_t2.py:941-1299 — the network the shipped scripts train (`-net sdnet_mini_ext`), densenet backbone.
+    """models/dsnet_t2.py:941-1299 — the network the shipped scripts train (`-net sdnet_mini_ext`), densenet or mobilenet
+    (MobileNetV3-Large) backbone; the native default stays 'densenet' (upstream's default is 'mobilenet').
     forward(left, right) -> (seg_branch, disp_out, seg_branch2, disp_out).  Both towers run as one batch of two
     statistics groups (weights are shared; BatchNorm statistics stay per image side, as in the reference)."""
 
     def __init__(self, CFG, labels=8, pretrained=False, patch_type='', include_edges=False, backbone='densenet'):
         super().__init__()
-        if backbone != 'densenet':
-            raise NotImplementedError("native path: densenet backbone only")
+        if backbone not in BACKBONES:
+            raise NotImplementedError("backbone %r: only %s are on the native path" % (backbone, " and ".join(BACKBONES)))
         if CFG.multaskloss not in (0, 1, 2):
             raise NotImplementedError("multaskloss %r: the reference defines 1 and 2" % (CFG.multaskloss,))
+        if backbone == 'mobilenet':
+            # combinations the reference builds but cannot run with this backbone (its forward raises a shape error)
+            if CFG.multaskloss == 2:
+                raise NotImplementedError("multaskloss=2 with the mobilenet backbone: the reference crashes "
+                                          "(mt_convDisp expects 1024 channels, the 1/32 tap has 160)")
+            if 'no_dec1' in CFG.abilation:
+                raise NotImplementedError("'no_dec1' with the mobilenet backbone: the reference crashes "
+                                          "(Conv2DownUp3 expects 352 channels, the 1/8 pyramid has 136)")
+            if CFG.hanet and CFG.aspp != 2:
+                raise NotImplementedError("hanet=1 with aspp != 2 and the mobilenet backbone: the reference crashes "
+                                          "(HANet_Conv(64) receives the 16-channel 1/2 tap)")
         self.multiTaskLoss = CFG.multaskloss
         self.include_edges = include_edges
         self.hanet = CFG.hanet
         dropout = CFG.dropout
         self.aspp_mod, self.use_att, self.convDeconvOut, self.abilation = CFG.aspp, CFG.use_att, CFG.convDeconvOut, CFG.abilation
         self.patch_type, self.backbone = patch_type, backbone
-        feature_channel, inplane_seg2 = 1, 512
+        # channel table of models/dsnet_t2.py:955-1012
+        mobile = backbone == 'mobilenet'
+        segnet_input = 160 * 2 if mobile else 1024 * 2
+        feature_channel, inplane_seg2 = 1, (304 if mobile else 512)
         if self.aspp_mod == 1:
             from .aspp import build_aspp
-            self.aspp, inplane_seg2 = build_aspp('densenet_a1', 32), 256
+            self.aspp, inplane_seg2 = build_aspp('mobilenet_a1' if mobile else 'densenet_a1', 32), 256
         elif self.aspp_mod == 2:
             from .aspp import build_aspp
-            self.aspp, inplane_seg2, feature_channel = build_aspp('densenet_a3', 32), 273, 64
+            self.aspp, inplane_seg2 = build_aspp('mobilenet_a3' if mobile else 'densenet_a3', 32), 273
+            feature_channel = 16 if mobile else 64
         self.resnet_features = piramidNet2(pretrained, backbone)
         for j in range(4):   # the auxiliary image convolutions see the edge map as a 4th channel (models/dsnet_t2.py:1061-1069)
             setattr(self, 'conv2d_ba%d' % j, _img_conv(4 if include_edges else 3))
@@ -316,7 +341,7 @@ class minidsnetExt(nn.Module):
         self.corrConv2d = _c1x1(patch[0] * patch[1], 128)
         self.Conv2DownUp3 = Conv2DownUp(352 if 'no_dec1' in self.abilation else 32, 128, 3, dropout=dropout)
         self.Conv2DownUp4 = Conv2DownUp(256, 64, 3, dropout=dropout)
-        self.segNet = segNet(2048, 1, labels, dropout=dropout)
+        self.segNet = segNet(segnet_input, 1, labels, dropout=dropout)
         self.conv1d_2 = _c1x1(65, 64)
         self.Conv2DownUp5 = Conv2DownUp(64, 64, 5, lastLayer=False, dropout=dropout)
         self.dispoutConv = ConvTranspose2dSame(64, 1, 5, padding='same', init_he=False)

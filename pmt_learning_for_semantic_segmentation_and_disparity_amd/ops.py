@@ -727,6 +727,9 @@ class _ConvFn(torch.autograd.Function):
         return gx, gw, gb, None, None
 
 
+_BN_ACTS = (0, 1, 2, _lib.ACT_HSWISH, _lib.ACT_HSIGMOID)   # activations the two-phase BatchNorm backward kernels take
+
+
 class _ConvBNActFn(torch.autograd.Function):
     """y = act(BatchNorm(conv(x))) (+ residual) as ONE autograd node: the conv epilogue sums the batch statistics,
     a per-channel kernel turns them into scale/shift (and updates the running statistics), one elementwise pass
@@ -796,10 +799,10 @@ class _ConvBNActFn(torch.autograd.Function):
             if direct:
                 dgamma = dbeta = None
             ob.sums, ob.gptr = None, 0
-        elif ctx.train and ctx.act in (0, 1, 2) and _fused_bn():
+        elif ctx.train and ctx.act in _BN_ACTS and _fused_bn():
             dgamma, dbeta = bn_backward_two_phase(g, ldg, yraw, ldraw, graw, ldgr, scale, shift, mean, invstd, gamma, beta, npix,
                                                   Cout, groups, ctx.act, parallel.global_count(ctx.count), dt)
-        elif ctx.train and ctx.act in (0, 1, 2):
+        elif ctx.train and ctx.act in _BN_ACTS:
             # two-phase: reductions only (no gradient written), per-channel finalize, then ONE pass writes the complete
             # gradient of the conv output — 10 bytes per element instead of 12
             dgamma, dbeta, dS = _bn_backward(g, ldg, yraw, ldraw, None, 0, scale, shift, mean, invstd, gamma, npix, Cout,
@@ -2007,3 +2010,164 @@ def deconv2d_strided(x, weight, bias, stride, bn=None, act=0, residual=None, gro
     if bn is None:
         return _ConvFn.apply(xs, weight, bias, spec, act)
     return _ConvBNActFn.apply(xs, weight, bn.weight, bn.bias, residual, spec, bn, act, groups)
+
+
+# ============================================================================ MobileNetV3: depthwise conv, squeeze-excite
+ACT_HSWISH, ACT_HSIGMOID = _lib.ACT_HSWISH, _lib.ACT_HSIGMOID
+
+
+def dw_out_size(n, k, stride):
+    return (n + 2 * ((k - 1) // 2) - k) // stride + 1
+
+
+class SESide:
+    """What the depthwise node hands to the SELayer behind it: the per-image channel sums of the raw convolution output
+    (its epilogue's average pool) and the BatchNorm's (scale, shift) — the pooled BatchNorm output is scale*mean + shift."""
+    __slots__ = ("pool", "scale", "shift", "groups")
+
+    def __init__(self):
+        self.pool = self.scale = self.shift = None
+        self.groups = 1
+
+
+class _DWConvBNActFn(torch.autograd.Function):
+    """y = act(BatchNorm(depthwise_conv(x))) as ONE autograd node (InvertedResidual, models/mobilenetv3.py:97-114):
+    the depthwise kernel's epilogue sums the batch statistics (and, for an SELayer behind it, the per-image pool), one
+    elementwise pass finalizes, normalises and activates.  The weight is the (C, 1, k, k) f32 parameter as stored."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, bn, k, stride, act, groups, side):
+        _require_gpu(x, weight)
+        if weight.dtype != torch.float32 or not weight.is_contiguous():
+            raise _lib.SdhipError("depthwise weight must be a contiguous f32 (C, 1, k, k) tensor")
+        B, C, H, W = x.shape
+        Ho, Wo = dw_out_size(H, k, stride), dw_out_size(W, k, stride)
+        xv, ldx = nhwc_view(x)
+        dt = dtype_code(x)
+        yraw, ldr = alloc_nhwc(B, C, Ho, Wo, x.dtype, x.device)
+        train = bn.training
+        ws = _zeros((NREP, groups, 2, C), torch.float64, x.device)[0] if train else None
+        parts = _lib.dw_pool_parts(H, W, C, k, stride, dt) if side is not None else 0
+        pool = _zeros((B, parts, C), torch.float32, x.device)[0] if side is not None else None   # per-workgroup slots
+        call("sdhip_dw_conv_fwd", ptr(xv), ldx, ptr(weight.detach()), ptr(yraw), ldr, ptr(ws), C, NREP, ptr(pool), parts,
+             B, H, W, C, k, stride, groups, dt, stream_ptr())
+        count = (B // groups) * Ho * Wo
+        y, ldy = alloc_nhwc(B, C, Ho, Wo, x.dtype, x.device)
+        if train and _fused_bn():
+            scale, shift, mean, invstd = [torch.empty((groups, C), dtype=torch.float32, device=x.device) for _ in range(4)]
+            _bn_track(bn, groups)
+            parallel.all_reduce_sum_(ws)         # sync-BN: the epilogue's replica sums become global, in place
+            call("sdhip_affine_act_bn", ptr(yraw), ldr, ptr(y), ldy, None, 0, ptr(ws), ws.stride(-2), NREP, ptr(bn.weight),
+                 ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var), ptr(scale), ptr(shift), ptr(mean), ptr(invstd),
+                 B * Ho * Wo, C, groups, float(parallel.global_count(count)), float(bn.eps),
+                 float(0.1 if bn.momentum is None else bn.momentum), act, dt, stream_ptr())
+        else:
+            scale, shift, mean, invstd = _bn_finalize(ws, NREP, bn, count, groups)
+            call("sdhip_affine_act", ptr(yraw), ldr, ptr(y), ldy, None, 0, ptr(scale), ptr(shift), B * Ho * Wo, C, groups, act,
+                 dt, stream_ptr())
+        if side is not None:
+            side.pool, side.scale, side.shift, side.groups = pool, scale, shift, groups
+        ctx.cfg = (k, stride, act, groups, ldx, ldr, count, train)
+        ctx.save_for_backward(xv, weight, gamma, beta, yraw, scale, shift, mean, invstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xv, weight, gamma, beta, yraw, scale, shift, mean, invstd = ctx.saved_tensors
+        k, stride, act, groups, ldx, ldraw, count, train = ctx.cfg
+        B, C, H, W = xv.shape
+        Ho, Wo = yraw.shape[2], yraw.shape[3]
+        npix = B * Ho * Wo
+        dt = dtype_code(xv)
+        g, ldg = nhwc_view(gy)
+        graw, ldgr = alloc_nhwc(B, C, Ho, Wo, xv.dtype, xv.device)
+        if train and _fused_bn():
+            dgamma, dbeta = bn_backward_two_phase(g, ldg, yraw, ldraw, graw, ldgr, scale, shift, mean, invstd, gamma, beta, npix,
+                                                  C, groups, act, parallel.global_count(count), dt)
+        elif train:
+            dgamma, dbeta, dS = _bn_backward(g, ldg, yraw, ldraw, None, 0, scale, shift, mean, invstd, gamma, npix, C, groups, act,
+                                             count, True, dt, beta=beta)
+            call("sdhip_bn_bwd_apply", ptr(g), ldg, ptr(yraw), ldraw, ptr(graw), ldgr, ptr(scale), ptr(shift), ptr(dS), C,
+                 npix, C, groups, act, dt, stream_ptr())
+        else:
+            dgamma, dbeta, _ = _bn_backward(g, ldg, yraw, ldraw, graw, ldgr, scale, shift, mean, invstd, gamma, npix, C, groups,
+                                            act, count, False, dt, beta=beta)
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gx, ldgx = alloc_nhwc(B, C, H, W, xv.dtype, xv.device)
+            call("sdhip_dw_conv_dgrad", ptr(graw), ldgr, ptr(weight.detach()), ptr(gx), ldgx, B, H, W, C, k, stride, dt,
+                 stream_ptr())
+        gw = None
+        if ctx.needs_input_grad[1]:
+            tw = _grad_target(weight)
+            target = tw if tw is not None else _zeros(tuple(weight.shape), torch.float32, weight.device)[0]
+            nparts = _lib.dw_wgrad_parts(B, H, W, C, k, stride)
+            part = torch.empty((nparts * k * k * C,), dtype=torch.float32, device=weight.device)   # every slot is written
+            call("sdhip_dw_conv_wgrad", ptr(xv), ldx, ptr(graw), ldgr, ptr(target), ptr(part), nparts, B, H, W, C, k, stride, dt,
+                 stream_ptr())
+            gw = None if tw is not None else target
+        return gx, gw, dgamma, dbeta, None, None, None, None, None, None
+
+
+def dw_conv_bn_act(x, weight, bn, stride=1, act=0, groups=1, side=None):
+    """act(bn(nn.Conv2d(C, C, k, stride, (k-1)//2, groups=C, bias=False)(x))); `side` (SESide) receives what an SELayer
+    behind it needs."""
+    k = weight.shape[-1]
+    if weight.shape[1] != 1 or weight.shape[0] != x.shape[1] or weight.shape[-2] != k or k not in (3, 5) or stride not in (1, 2):
+        raise _lib.SdhipError("depthwise convolution: (C, 1, k, k) weights with k 3 / 5 and stride 1 / 2 only")
+    return _DWConvBNActFn.apply(x, weight, bn.weight, bn.bias, bn, k, stride, act, groups, side)
+
+
+class _SEScaleActFn(torch.autograd.Function):
+    """y = act(z * s[b, c]) with s = SELayer's excitation of z (models/mobilenetv3.py:64-77) — one launch for the pooled
+    MLP (the pool comes from the depthwise epilogue, SESide), one elementwise pass (sdhip_affine_act with a group per
+    image).  Backward: the reductions ds, one launch for the MLP's backward (parameter gradients and the pooled-path term),
+    one elementwise pass writing dL/dz."""
+
+    @staticmethod
+    def forward(ctx, z, w1, b1, w2, b2, side, act):
+        _require_gpu(z, w1)
+        B, C, H, W = z.shape
+        r = w1.shape[0]
+        zv, ldz = nhwc_view(z)
+        dev = z.device
+        inv_hw = 1.0 / (H * W)
+        s = torch.empty((B, C), dtype=torch.float32, device=dev)
+        ws = torch.empty((B * (2 * C + r),), dtype=torch.float32, device=dev)
+        call("sdhip_se_fwd", ptr(side.pool), side.pool.shape[1], inv_hw, ptr(side.scale), ptr(side.shift), side.groups, ptr(w1.detach()),
+             ptr(b1.detach()), ptr(w2.detach()), ptr(b2.detach()), ptr(s), ptr(ws), B, C, r, stream_ptr())
+        y, ldy = alloc_nhwc(B, C, H, W, z.dtype, dev)
+        call("sdhip_affine_act", ptr(zv), ldz, ptr(y), ldy, None, 0, ptr(s), None, B * H * W, C, B, act, dtype_code(z), stream_ptr())
+        ctx.cfg = (ldz, act, r, inv_hw)
+        ctx.save_for_backward(zv, w1, b1, w2, b2, s, ws)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        zv, w1, b1, w2, b2, s, ws = ctx.saved_tensors
+        ldz, act, r, inv_hw = ctx.cfg
+        B, C, H, W = zv.shape
+        dev = zv.device
+        dt = dtype_code(zv)
+        g, ldg = nhwc_view(gy)
+        both, pz = _zeros((2, NREP, B, C), torch.float32, dev)
+        call("sdhip_affine_act_bwd", ptr(g), ldg, ptr(zv), ldz, None, 0, ptr(s), None, ptr(both[0]), ptr(both[1]), NREP,
+             B * H * W, C, B, act, 0, int(pz), dt, stream_ptr())
+        outs = []
+        for prm in (w1, b1, w2, b2):
+            t = _grad_target(prm)
+            outs.append((t, False) if t is not None else (_zeros(tuple(prm.shape), torch.float32, dev)[0], True))
+        gpool = torch.empty((B, C), dtype=torch.float32, device=dev)
+        call("sdhip_se_bwd", ptr(both[0]), NREP, ptr(ws), ptr(w1.detach()), ptr(w2.detach()), ptr(outs[0][0]), ptr(outs[1][0]),
+             ptr(outs[2][0]), ptr(outs[3][0]), ptr(gpool), inv_hw, B, C, r, stream_ptr())
+        gz, ldgz = alloc_nhwc(B, C, H, W, zv.dtype, dev)
+        call("sdhip_se_scale_bwd", ptr(g), ldg, ptr(zv), ldz, ptr(gz), ldgz, ptr(s), ptr(gpool), H * W, B, C, act, dt, stream_ptr())
+        grads = [t if ret else None for t, ret in outs]
+        return (gz, *grads, None, None)
+
+
+def se_scale_act(z, fc1, fc2, side, act=0):
+    """act(SELayer(z)) given the SESide the depthwise node behind z filled (fc1 / fc2: the two nn.Linear)."""
+    if side is None or side.pool is None:
+        raise _lib.SdhipError("se_scale_act needs the pool of the depthwise node in front of it (SESide)")
+    return _SEScaleActFn.apply(z, fc1.weight, fc1.bias, fc2.weight, fc2.bias, side, act)
