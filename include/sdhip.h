@@ -594,6 +594,40 @@ int sdhip_se_bwd(const float* ds, int nrep, const float* ws, const float* w1, co
 int sdhip_se_scale_bwd(const void* gy, int ldg, const void* x, int ldx, void* gx, int ldgx, const float* s, const float* gadd,
                        long npix_img, int B, int C, int act, int dtype, void* stream);
 
+
+/* ---------------------------------------------------------------------------
+ * Disparity warp and gated blend of the warp networks (models/torch_dsnet.py:10-86 apply_disparity, wrap_mode='edge';
+ * models/dsnet_t2_warp.py minidsnetDivide / minidsnetDivideSoftmax).  For output pixel (b, y, j), all in f32:
+ *   x = clamp(j + offset_sign * disp[b,y,j], 0, W-1),  x0 = floor(x),  x1 = min(x0 + 1, W-1)
+ *   warped[b,y,j,c] = (x1 - x) * seg_right[b,y,x0,c] + (x - x0) * seg_right[b,y,x1,c]
+ *   both[b,y,j,c]   = (1 - a) * seg_left[b,y,j,c] + a * warped[b,y,j,c]
+ * As in the reference, x == W-1 makes both weights 0: the right edge (and every pixel clamped to it) is 0; a pixel clamped
+ * on the left copies column 0.  All maps are NHWC with a pixel stride ld* >= their channel count (pad lanes are never
+ * touched); disp is one channel of `dtype` with pixel stride ldd, widened to f32; offset_sign is +1 (apply_disparity) or
+ * -1 (the networks warp with -disp).
+ * gate (optional): NULL = plain apply_disparity, seg_left / both / prob must be NULL and gate_ch 0.  Otherwise gate_ch is 1
+ * (one blend weight per pixel) or C (one per channel); with gate_softmax != 0 (gate_ch == C) `gate` holds RAW scores, the
+ * kernel takes their softmax over the channels, writes it to prob and blends with it.  One launch. */
+int sdhip_warp_blend_fwd(const void* seg_left, int ldl, const void* seg_right, int ldr, const void* disp, int ldd,
+                         float offset_sign, const void* gate, int ldgt, int gate_ch, int gate_softmax, void* warped, int ldw,
+                         void* both, int ldb, void* prob, int ldp, int B, int H, int W, int C, int dtype, void* stream);
+/* Backward of sdhip_warp_blend_fwd from g_both and / or g_warped (either may be NULL; g_both needs a gate).  `gate` holds
+ * the blend weights the forward pass used: its gate input, or its prob output when gate_softmax != 0.  Outputs, each
+ * optional and overwritten:
+ *   g_left  = (1 - a) * g_both
+ *   g_gate  = g_both * (warped - seg_left), summed over the channels for gate_ch == 1; with gate_softmax the gradient
+ *             w.r.t. the raw scores, p_c * (g_c - sum_k g_k p_k)
+ *   g_disp  = offset_sign * sum_c gw_c * (seg_right[x1] - seg_right[x0]) where 0 <= j + offset <= W-1 (bounds included),
+ *             0 where the clamp is active;  gw = g_warped + a * g_both
+ *   g_right = the adjoint of the row gather: gw * (x1 - x) added at x0, gw * (x - x0) added at x1.
+ * Two launches: the per-pixel pass, then one workgroup per image row and channel group that accumulates g_right in LDS
+ * (float LDS atomics in an 80 KB accumulator, W <= 20480) and stores it once — no global atomics, no workspace.  The order of the LDS adds is not
+ * fixed: g_right repeats to f32 rounding, not bit for bit; everything else is deterministic. */
+int sdhip_warp_blend_bwd(const void* g_both, int ldgb, const void* g_warped, int ldgw, const void* seg_left, int ldl,
+                         const void* seg_right, int ldr, const void* disp, int ldd, float offset_sign, const void* gate, int ldgt,
+                         int gate_ch, int gate_softmax, void* g_left, int ldgl, void* g_right, int ldgr, void* g_disp, int ldgd,
+                         void* g_gate, int ldgg, int B, int H, int W, int C, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

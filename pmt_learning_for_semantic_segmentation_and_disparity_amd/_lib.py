@@ -106,6 +106,9 @@ SIGNATURES = {
     "sdhip_se_fwd": [_p, _i, _f, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
     "sdhip_se_bwd": [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _i, _i, _p],
     "sdhip_se_scale_bwd": [_p, _i, _p, _i, _p, _i, _p, _p, _l, _i, _i, _i, _i, _p],
+    "sdhip_warp_blend_fwd": [_p, _i, _p, _i, _p, _i, _f, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
+    "sdhip_warp_blend_bwd": [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _f, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _i,
+                             _i, _i, _i, _i, _i, _p],
 }
 _lib.sdhip_lovasz_workspace_bytes.argtypes = [_l, _i]
 _lib.sdhip_lovasz_workspace_bytes.restype = _l

@@ -214,8 +214,8 @@ def _pool_branch(p, cin):
     return nn.Sequential(nn.AvgPool2d(p, p), convbn(cin, 32, 3, 1, 'same', 1), nn.ReLU(inplace=True))
 
 
-def _pyramid(branches, x, groups):
-    """cat([x] + [bilinear_up(relu(bn(conv3x3(avgpool_p(x))))) for each branch]) (models/dsnet_t2.py:2037-2081).
+def _pyramid_branches(branches, x, groups):
+    """[bilinear_up(relu(bn(conv3x3(avgpool_p(x))))) for each branch] (models/dsnet_t2.py:2037-2081).
     The pools share work: pool_2p = 2x2 pool of pool_p (identical windows, mean of equal-size means)."""
     order = sorted(range(len(branches)), key=lambda j: branches[j][0].kernel_size)
     outs, pooled, prev_p = [None] * len(branches), x, 1
@@ -228,7 +228,12 @@ def _pyramid(branches, x, groups):
         prev_p = p
         y = branches[j][1].fused(pooled, act=1, groups=groups)
         outs[j] = ops.interpolate(y, size=x.shape[2:], mode='bilinear')
-    return ops.concat([x] + outs)
+    return outs
+
+
+def _pyramid(branches, x, groups):
+    """cat([x] + the branches of _pyramid_branches)."""
+    return ops.concat([x] + _pyramid_branches(branches, x, groups))
 
 
 class piramidNet2(nn.Module):

@@ -1245,6 +1245,32 @@ def concat(xs):
     return _ConcatFn.apply(*xs)
 
 
+class _RepeatBatchFn(torch.autograd.Function):
+    """x -> [x | x] along the batch (one tower's map fed to both halves of a batched pass): two copies into one NHWC
+    buffer; the backward adds the two halves of the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _require_gpu(x)
+        B, C, H, W = x.shape
+        xv, ldx = nhwc_view(x)
+        out, ldo = alloc_nhwc(2 * B, C, H, W, x.dtype, x.device)
+        for lo in (0, B):
+            call("sdhip_affine_act", ptr(xv), ldx, ptr(out[lo:lo + B]), ldo, None, 0, None, None, B * H * W, C, 1, 0, dtype_code(x),
+                 stream_ptr())
+        ctx.B = B
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        with torch.no_grad():
+            return add(g[:ctx.B], g[ctx.B:])
+
+
+def repeat_batch(x):
+    return _RepeatBatchFn.apply(x)
+
+
 class _MulBcastFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, m):
@@ -1276,25 +1302,112 @@ def mul_bcast(a, m):
     return _MulBcastFn.apply(a, m)
 
 
+# ============================================================================ disparity warp and gated blend
+def _warp_check(right, disp, left=None, gate=None, softmax_gate=False):
+    _require_gpu(right, disp, left, gate)
+    if right.dim() != 4 or disp.dim() != 4:
+        raise _lib.SdhipError("warp: maps must be (B,C,H,W), got %s and %s" % (tuple(right.shape), tuple(disp.shape)))
+    B, C, H, W = right.shape
+    if tuple(disp.shape) != (B, 1, H, W):
+        raise _lib.SdhipError("warp: the offset must be (B,1,H,W) = %s, got %s" % ((B, 1, H, W), tuple(disp.shape)))
+    if disp.dtype != right.dtype:
+        raise _lib.SdhipError("warp: the offset's dtype %s differs from the map's %s" % (disp.dtype, right.dtype))
+    if gate is not None:
+        if tuple(left.shape) != (B, C, H, W) or left.dtype != right.dtype or gate.dtype != right.dtype:
+            raise _lib.SdhipError("warp_blend: seg_left %s / seg_right %s / gate differ in shape or dtype" % (tuple(left.shape), (B, C, H, W)))
+        if tuple(gate.shape) not in ((B, 1, H, W), (B, C, H, W)) or (softmax_gate and gate.shape[1] != C):
+            raise _lib.SdhipError("warp_blend: the gate must be (B,1,H,W) or (B,C,H,W) (softmax: C channels), got %s" % (tuple(gate.shape),))
+
+
+class _WarpBlendFn(torch.autograd.Function):
+    """sdhip_warp_blend_fwd / _bwd.  gate None: (warped,) = apply_disparity(right, sign * disp).  Otherwise
+    (both, warped[, prob]) with both = (1 - a) * left + a * warped; prob (softmax gate only) is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, left, right, disp, gate, sign, softmax_gate):
+        _warp_check(right, disp, left, gate, softmax_gate)
+        B, C, H, W = right.shape
+        rv, ldr = nhwc_view(right)
+        dv, ldd = nhwc_view(disp)
+        warped = empty_nhwc(B, C, H, W, right.dtype, right.device)
+        lv = gv = both = prob = None
+        ldl = ldgt = gch = 0
+        if gate is not None:
+            lv, ldl = nhwc_view(left)
+            gv, ldgt = nhwc_view(gate)
+            gch = gate.shape[1]
+            both = empty_nhwc(B, C, H, W, right.dtype, right.device)
+            if softmax_gate:
+                prob = empty_nhwc(B, C, H, W, right.dtype, right.device)
+        call("sdhip_warp_blend_fwd", ptr(lv), ldl, ptr(rv), ldr, ptr(dv), ldd, float(sign), ptr(gv), ldgt, gch, int(softmax_gate),
+             ptr(warped), C, ptr(both), C, ptr(prob), C, B, H, W, C, dtype_code(right), stream_ptr())
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(lv, rv, dv, prob if softmax_gate else gv)
+        ctx.cfg = (ldl, ldr, ldd, C if softmax_gate else ldgt, gch, float(sign), bool(softmax_gate))
+        if gate is None:
+            return warped
+        if softmax_gate:
+            ctx.mark_non_differentiable(prob)
+            return both, warped, prob
+        return both, warped
+
+    @staticmethod
+    def backward(ctx, *gs):
+        lv, rv, dv, av = ctx.saved_tensors
+        ldl, ldr, ldd, lda, gch, sign, softmax_gate = ctx.cfg
+        B, C, H, W = rv.shape
+        g_both, g_warped = (None, gs[0]) if av is None else (gs[0], gs[1])
+        if g_both is None and g_warped is None:
+            return None, None, None, None, None, None
+        gb, ldgb = nhwc_view(g_both) if g_both is not None else (None, 0)
+        gw, ldgw = nhwc_view(g_warped) if g_warped is not None else (None, 0)
+        need = ctx.needs_input_grad
+        dev, dt = rv.device, rv.dtype
+        g_left = empty_nhwc(B, C, H, W, dt, dev) if av is not None and need[0] else None
+        g_right = empty_nhwc(B, C, H, W, dt, dev) if need[1] else None
+        g_disp = torch.empty((B, 1, H, W), dtype=dt, device=dev) if need[2] else None
+        g_gate = empty_nhwc(B, gch, H, W, dt, dev) if av is not None and need[3] else None
+        call("sdhip_warp_blend_bwd", ptr(gb), ldgb, ptr(gw), ldgw, ptr(lv), ldl, ptr(rv), ldr, ptr(dv), ldd, sign, ptr(av), lda, gch,
+             int(softmax_gate), ptr(g_left), C, ptr(g_right), C, ptr(g_disp), 1, ptr(g_gate), gch, B, H, W, C, dtype_code(rv),
+             stream_ptr())
+        return g_left, g_right, g_disp, g_gate, None, None
+
+
+def apply_disparity(img, x_offset):
+    """models/torch_dsnet.py apply_disparity(img, x_offset) with wrap_mode='edge': img (B,C,H,W) sampled at column
+    j + x_offset[b,0,y,j] with linear interpolation, differentiable in both arguments.  The reference's edge rules hold:
+    a sample at or beyond the right edge is 0, one beyond the left edge copies column 0, and a clamped offset gets no gradient."""
+    return _WarpBlendFn.apply(None, img, x_offset, None, 1.0, False)
+
+
+def warp_blend(seg_left, seg_right, disp, gate, softmax_gate=False):
+    """(both, warped_right[, gate_probabilities]): warped_right = apply_disparity(seg_right, -disp) and
+    both = (1 - a) * seg_left + a * warped_right in one pass.  gate: (B,1,H,W) or (B,C,H,W) blend weights a; with
+    softmax_gate the gate holds raw (B,C,H,W) scores, a is their softmax over the channels and is returned third."""
+    if gate is None:
+        raise _lib.SdhipError("warp_blend needs a gate; the plain warp is apply_disparity")
+    return _WarpBlendFn.apply(seg_left, seg_right, disp, gate, -1.0, softmax_gate)
+
+
 # ============================================================================ losses of the timed step
 _lovasz_ws = {}
 
 
 class _TrainLossFn(torch.autograd.Function):
-    """total = CE(seg1) + CE(seg2) [+ Lovasz(seg2)] + L1(disp)  — the loss of the reference's training step
-    (torch_implementation.py:279,293,304,325 with `-loss cross_entropy lovasz_loss`).  The gradients w.r.t. the
-    three network outputs are produced in the same pass."""
+    """total = CE(seg1) + CE(seg2) [+ Lovasz(seg2)] + L1(disp) [+ CE(seg3)]  — the loss of the reference's training step
+    (torch_implementation.py:279,293,304,325 with `-loss cross_entropy lovasz_loss`; seg3: the third segmentation output of
+    the `ThreeOutPuts` networks, :157-158,298).  The gradients w.r.t. the network outputs are produced in the same pass."""
 
     @staticmethod
-    def forward(ctx, seg1, disp, seg2, seg_t, disp_t, use_lovasz, mask_invalid_disp=False, ignore_void=False):
-        _require_gpu(seg1, disp, seg2, seg_t, disp_t)
+    def forward(ctx, seg1, disp, seg2, seg_t, disp_t, use_lovasz, mask_invalid_disp=False, ignore_void=False, seg3=None):
+        _require_gpu(seg1, disp, seg2, seg_t, disp_t, seg3)
         B, C, H, W = seg1.shape
         npix = B * H * W
         dt = dtype_code(seg1)
         loss = torch.zeros(1, dtype=torch.float64, device=seg1.device)
         tv, ldt = nhwc_view(seg_t)
         grads = []
-        for s in (seg1, seg2):
+        for s in (seg1, seg2) if seg3 is None else (seg1, seg2, seg3):
             sv, ld = nhwc_view(s)
             g = empty_nhwc(B, C, H, W, s.dtype, s.device)
             call("sdhip_ce_loss", ptr(sv), ld, ptr(tv), ldt, ptr(g), C, ptr(loss), npix, C, 1.0, dt, stream_ptr())
@@ -1317,13 +1430,13 @@ class _TrainLossFn(torch.autograd.Function):
             call("sdhip_lovasz_softmax", ptr(s2), ld2, ptr(tv), ldt, ptr(grads[1]), C, ptr(loss), npix, C, 1.0, ptr(ws),
                  ws.numel(), int(ignore_void), dt, stream_ptr())
         total = loss
-        ctx.save_for_backward(grads[0], gd, grads[1])
+        ctx.save_for_backward(grads[0], gd, grads[1], grads[2] if seg3 is not None else None)
         return total.float()
 
     @staticmethod
     def backward(ctx, g):
-        g1, gd, g2 = ctx.saved_tensors
-        return g1, gd, g2, None, None, None, None, None   # d(total)/d(total) is 1 in the training step
+        g1, gd, g2, g3 = ctx.saved_tensors
+        return g1, gd, g2, None, None, None, None, None, g3   # d(total)/d(total) is 1 in the training step
 
 
 MT_IGNORE_INDEX = 19     # F.cross_entropy(..., ignore_index=19) of util/utilTorchLoss.py:533,535, whatever the class count
@@ -1457,14 +1570,15 @@ def loss_map_mean(m):
     return mean
 
 
-def train_loss(seg1, disp, seg2, seg_target, disp_target, use_lovasz=True, mask_invalid_disp=False, ignore_void=False):
-    """seg_target: one-hot f32 (B,C,H,W); disp_target: f32 (B,1,H,W).  The two dataset rules of losses/multiLosses.py are
+def train_loss(seg1, disp, seg2, seg_target, disp_target, use_lovasz=True, mask_invalid_disp=False, ignore_void=False, seg3=None):
+    """seg_target: one-hot f32 (B,C,H,W); disp_target: f32 (B,1,H,W); seg3 (optional): a third segmentation output that adds
+    its cross-entropy (the warp networks).  The two dataset rules of losses/multiLosses.py are
     opt-in, both off by default (roses / garden, `ignore=None`, :11-17):
       ignore_void       — cityscapes / kitti (:19-21, the 20th one-hot channel dropped, `ignore=19`): an all-zero target row
                           marks a void pixel, removed from the Lovasz term.  Off: its label is argmax = class 0 and it counts.
                           (Its cross-entropy term is zero under either rule: sum(-t * log_softmax) over a zero row.)
       mask_invalid_disp — disparities <= 0 are invalid (:134-141)."""
-    return _TrainLossFn.apply(seg1, disp, seg2, seg_target, disp_target, use_lovasz, mask_invalid_disp, ignore_void)
+    return _TrainLossFn.apply(seg1, disp, seg2, seg_target, disp_target, use_lovasz, mask_invalid_disp, ignore_void, seg3)
 
 
 # ============================================================================ dropout / global average pool

@@ -1,7 +1,7 @@
 """Training step of the hot path: forward + loss + backward + Adam, optionally captured as ONE hipGraph.
 
 Counterpart of train_model's inner loop (torch_implementation.py:350-397) without its host-side metric /
-JPEG work: model(left, right) -> CE(seg1) + CE(seg2) + Lovasz(seg2) + L1(disp) -> backward -> Adam.
+JPEG work: model(left, right) -> CE(seg1) + CE(seg2) + Lovasz(seg2) + L1(disp) [+ CE(seg3)] -> backward -> Adam.
 Parameters live in one flat f32 buffer (one fused Adam launch, one gradient all-reduce over RCCL when
 data-parallel); activations run in `dtype` (bf16 MFMA path or exact f32 path).
 """
@@ -77,10 +77,11 @@ class TrainStep:
         self.steps_done = 0       # optimizer steps actually EXECUTED (eager steps + graph replays; the recording pass of a capture runs nothing)
         self._capture_fault = None   # tests: a callable invoked inside the capture to make it fail
         self.debug_graph = False     # tests: keep the captured hipGraph inspectable (_lib.graph_node_counts)
-        # multitask models: positions (in model.parameters() order) of the parameters the loss never reaches (mode 2's unused
-        # decoder), found on the first step.  torch.optim.Adam keeps no state for them (their .grad stays None), so a saved
-        # optimizer state omits them as well (checkpoint.optimizer_state_dict); here their gradient slice stays 0, their
-        # moments stay 0 and the fused Adam leaves them bit-identical (update 0 / (0 + eps))
+        # multitask and warp models: positions (in model.parameters() order) of the parameters the loss never reaches (mode
+        # 2's unused decoder; the warp networks' key-only members), found on the first step.  torch.optim.Adam keeps no
+        # state for them (their .grad stays None), so a saved optimizer state omits them as well
+        # (checkpoint.optimizer_state_dict); here their gradient slice stays 0, their moments stay 0 and the fused Adam
+        # leaves them bit-identical (update 0 / (0 + eps))
         self.grad_free = None
         # dropout streams differ per rank (the reference's ranks draw from independently seeded generators) and advance
         # once per step on the device, so that graph replays see new masks (ops.rng_seed_tensor)
@@ -123,6 +124,7 @@ class TrainStep:
             self.flat_g.zero_()
         self.pack_all()             # one launch packs every weight (forward and data-grad orientation)
         mt = getattr(self.model, "multiTaskLoss", 0)
+        three = getattr(self.model, "three_outputs", False)
         if mt:    # the reference harness's call (torch_implementation.py:146-149): labels from the full one-hot (ATen argmax)
             outs = self.model(left.to(self.dtype), right.to(self.dtype), None, disp, seg.argmax(1))
         else:
@@ -132,8 +134,10 @@ class TrainStep:
         elif mt:  # the sum of the three maps' means (torch_implementation.py:173-176,285-325), from the loss kernels' own sums
             loss = multitask.step_loss(outs[4], outs[5], outs[6])
         else:
-            loss = ops.train_loss(outs[0], outs[1], outs[2], seg, disp, self.use_lovasz)
-        if mt and self.grad_free is None:
+            # the `ThreeOutPuts` networks (warp.minidsnetDivide*) add the cross-entropy of their third segmentation map, outs[4]
+            # (torch_implementation.py:157-158,298); Lovasz stays on outs[2], which the metrics score as well
+            loss = ops.train_loss(outs[0], outs[1], outs[2], seg, disp, self.use_lovasz, seg3=outs[4] if three else None)
+        if (mt or three) and self.grad_free is None:
             self.grad_free = _unreached_parameters(self.model, loss)
         if self.metrics is not None and self.loss_fn is None:
             self.metrics.update(outs[2].detach(), seg, outs[1].detach(), disp)
