@@ -215,11 +215,18 @@ def abi_version():
     return _lib.sdhip_abi_version()
 
 
-def call(name, *args):
+def call(name, *args, unsupported_ok=False):
     """Invoke a C entry point; raise SdhipError with the library's message on failure."""
     rc = getattr(_lib, name)(*args)
-    if rc != 0:
+    if rc != 0 and not (unsupported_ok and rc == ERR_UNSUPPORTED):
         raise SdhipError("%s failed (%d): %s" % (name, rc, _lib.sdhip_last_error().decode()))
+    return rc == 0
+
+
+def try_call(name, *args):
+    """`call` for an entry point that may decline its arguments: True = it ran, False = it answered ERR_UNSUPPORTED
+    (nothing was launched; the caller takes its other route).  Any other failure raises as in `call`."""
+    return call(name, *args, unsupported_ok=True)
 
 
 def dtype_code(t):

@@ -26,7 +26,7 @@ import torch.nn as nn
 
 from . import ops
 from . import _lib as _lib_mod
-from ._lib import call, dtype_code, ptr, stream_ptr
+from ._lib import call, dtype_code, ptr, stream_ptr, try_call
 
 
 NREP = ops.NREP
@@ -48,12 +48,11 @@ def _fold_finalize(ws, c_new0, Cn, S, Ct, bn, C, count, groups, synced=False):
     dev = bn.weight.device
     out = [torch.empty((groups, C), dtype=torch.float32, device=dev) for _ in range(4)]
     ops._bn_track(bn, groups)
-    mom = 0.1 if bn.momentum is None else bn.momentum
     if not synced:
         ops.parallel.all_reduce_sum_(ws)          # sync-BN: the newest channels' replica sums become global in place
     call("sdhip_bn_fold_finalize", ptr(ws), ws.shape[0], ws.stride(-2), c_new0, Cn, ptr(S), Ct, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
          ptr(bn.running_var), ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), C, groups, float(ops.parallel.global_count(count)),
-         float(bn.eps), float(mom), stream_ptr())
+         float(bn.eps), float(ops._bn_momentum(bn)), stream_ptr())
     return out
 
 
@@ -121,17 +120,15 @@ class _DenseBlockFn(torch.autograd.Function):
                 if pw is not None and not pending[2]:
                     ops.parallel.all_reduce_sum_(pw)     # the previous layer's output statistics (folded into the slab's by this launch)
                     pending = (pw, pc0, True)
-                rc = _lib_mod._lib.sdhip_conv2d_fwd_bnpro(
-                    ptr(slab), ptr(w1), ptr(y1), ptr(S2), S2.stride(-2), nrep2, ptr(S), Ct, 1,
+                done1 = try_call(
+                    "sdhip_conv2d_fwd_bnpro", ptr(slab), ptr(w1), ptr(y1), ptr(S2), S2.stride(-2), nrep2, ptr(S), Ct, 1,
                     ptr(pw), pw.stride(-2) if pw is not None else 0, pw.shape[0] if pw is not None else 0, pc0, growth if pw is not None else 0,
                     ptr(bn1.weight), ptr(bn1.bias), ptr(bn1.running_mean), ptr(bn1.running_var), ptr(sc1), ptr(sh1), ptr(mu1), ptr(iv1),
-                    float(gcount), float(bn1.eps), float(0.1 if bn1.momentum is None else bn1.momentum),
+                    float(gcount), float(bn1.eps), float(ops._bn_momentum(bn1)),
                     B, H, W, Cin, Ct, H, W, mid, mid, 1, 1, 0, 0, groups, dt, stream_ptr())
-                if rc == 0:
+                if done1:
                     ops._bn_track(bn1, groups)
-                    done1, pending = True, None
-                elif rc != _lib_mod.ERR_UNSUPPORTED:
-                    raise _lib_mod.SdhipError("sdhip_conv2d_fwd_bnpro failed (%d): %s" % (rc, _lib_mod._lib.sdhip_last_error().decode()))
+                    pending = None
             if not done1:
                 if pending is not None:
                     # ONE launch: fold the previous layer's statistics into the slab AND finalize this layer's norm1
@@ -149,16 +146,13 @@ class _DenseBlockFn(torch.autograd.Function):
                 sc2, sh2, mu2, iv2 = [torch.empty((groups, mid), dtype=torch.float32, device=dev) for _ in range(4)]
                 ops.parallel.all_reduce_sum_(S2)         # sync-BN: conv1's epilogue sums, in place, before conv2 finalizes them
                 s2_synced = True
-                rc = _lib_mod._lib.sdhip_conv2d_fwd_bnpro(
-                    ptr(y1), ptr(w2), ptr(slab[:, Cin:Cin + growth]), ptr(S3), S3.stride(-2), nrep3, ptr(S2), S2.stride(-2), nrep2,
+                done2 = try_call(
+                    "sdhip_conv2d_fwd_bnpro", ptr(y1), ptr(w2), ptr(slab[:, Cin:Cin + growth]), ptr(S3), S3.stride(-2), nrep3, ptr(S2), S2.stride(-2), nrep2,
                     None, 0, 0, 0, 0, ptr(bn2.weight), ptr(bn2.bias), ptr(bn2.running_mean), ptr(bn2.running_var), ptr(sc2), ptr(sh2), ptr(mu2), ptr(iv2),
-                    float(gcount), float(bn2.eps), float(0.1 if bn2.momentum is None else bn2.momentum),
+                    float(gcount), float(bn2.eps), float(ops._bn_momentum(bn2)),
                     B, H, W, mid, mid, H, W, growth, Ct, 3, 3, 1, 1, groups, dt, stream_ptr())
-                if rc == 0:
+                if done2:
                     ops._bn_track(bn2, groups)
-                    done2 = True
-                elif rc != _lib_mod.ERR_UNSUPPORTED:
-                    raise _lib_mod.SdhipError("sdhip_conv2d_fwd_bnpro failed (%d): %s" % (rc, _lib_mod._lib.sdhip_last_error().decode()))
             if not done2:
                 sc2, sh2, mu2, iv2 = _finalize(S2, nrep2, layer.norm2, count, groups, training, synced=s2_synced)
                 ops._conv_launch(y1, mid, w2, slab[:, Cin:Cin + growth], Ct, None, sc2, sh2, S3, B, H, W, mid, H, W, growth,
@@ -225,16 +219,8 @@ class _DenseBlockFn(torch.autograd.Function):
             gw2 = _wgrad(y1, mid, dy2, growth, layer.conv2.weight, B, H, W, mid, growth, 3, 1, sc2, sh2, groups, dt)
             # (3) through relu + norm2's affine, (4) norm2's statistics, (5) into y1
             if fuse2:
-                tg, tb = ops._grad_target(layer.norm2.weight), ops._grad_target(layer.norm2.bias)
-                direct2 = tg is not None and tb is not None
-                dg2 = tg if direct2 else torch.empty(mid, dtype=torch.float32, device=dev)
-                db2 = tb if direct2 else torch.empty(mid, dtype=torch.float32, device=dev)
-                ops.parallel.all_reduce_sum_(sums2)
-                call("sdhip_bn_bwd_apply_fin_d", ptr(gp2), mid, ptr(y1), mid, ptr(gp2), mid, ptr(sc2), ptr(sh2), ptr(sums2), NREP,
-                     ptr(layer.norm2.weight), ptr(mu2), ptr(iv2), ptr(dg2), ptr(db2), int(direct2), pscale, npix, mid, groups, float(gcount),
-                     1, dt, st)
-                if direct2:
-                    dg2 = db2 = None
+                _, _, dg2, db2 = ops._bn_act_backward(gp2, mid, y1, mid, sc2, sh2, mu2, iv2, layer.norm2.weight, layer.norm2.bias,
+                                                      groups, 1, count, True, presummed=sums2, out=(gp2, mid))   # in place: elementwise
             elif training and ops._fused_bn():
                 dg2, db2 = ops.bn_backward_two_phase(gp2, mid, y1, mid, gp2, mid, sc2, sh2, mu2, iv2, layer.norm2.weight,
                                                      layer.norm2.bias, npix, mid, groups, 1, gcount, dt)   # in place: elementwise
@@ -253,13 +239,9 @@ class _DenseBlockFn(torch.autograd.Function):
                 if dtype == torch.bfloat16 and npix <= FUSE1_MAX_PIX and not _lib_mod.DIAG_NO_BNBWD_EPILOGUE:
                     # small maps: the 1x1 data gradient itself masks, scales and accumulates into the slab gradient and takes
                     # the two reductions (mode 1 of sdhip_conv2d_fwd_bnbwd): gp1 is never written, one launch less per layer
-                    rc = _lib_mod._lib.sdhip_conv2d_fwd_bnbwd(ptr(gp2), ptr(wd1), ptr(g_slab), ptr(both), Cin, NREP, ptr(slab), Ct,
-                                                              ptr(sc1), ptr(sh1), ptr(g_slab), Ct, B, H, W, mid, mid, H, W, Cin, Ct,
-                                                              1, 1, 1, 0, 0, groups, 1, dt, st)
-                    if rc == 0:
-                        fused1 = True
-                    elif rc != _lib_mod.ERR_UNSUPPORTED:
-                        raise _lib_mod.SdhipError("sdhip_conv2d_fwd_bnbwd failed (%d): %s" % (rc, _lib_mod._lib.sdhip_last_error().decode()))
+                    fused1 = try_call("sdhip_conv2d_fwd_bnbwd", ptr(gp2), ptr(wd1), ptr(g_slab), ptr(both), Cin, NREP, ptr(slab), Ct,
+                                      ptr(sc1), ptr(sh1), ptr(g_slab), Ct, B, H, W, mid, mid, H, W, Cin, Ct, 1, 1, 1, 0, 0, groups, 1,
+                                      dt, st)
             if not fused1:
                 gp1 = ops.empty_nhwc(B, Cin, H, W, dtype, dev)
                 ops._conv_launch(gp2, mid, wd1, gp1, Cin, None, None, None, None, B, H, W, mid, H, W, Cin, 1, 1, 1, 1, 0, 0,
@@ -270,12 +252,8 @@ class _DenseBlockFn(torch.autograd.Function):
                     call("sdhip_affine_act_bwd", ptr(gp1), Cin, ptr(slab), Ct, ptr(g_slab), Ct, ptr(sc1), ptr(sh1), ptr(both[0]), ptr(both[1]),
                          NREP, npix, Cin, groups, 1, 1, int(pz), dt, st)
                 ops.parallel.all_reduce_sum_(both)        # norm1's two reductions [2][NREP][groups][Cin]: global before the finalize
-                tg, tb = ops._grad_target(layer.norm1.weight), ops._grad_target(layer.norm1.bias)
-                direct = tg is not None and tb is not None
-                dgam = tg if direct else torch.empty(Cin, dtype=torch.float32, device=dev)
-                dbet = tb if direct else torch.empty(Cin, dtype=torch.float32, device=dev)
+                dgam, dbet, direct, (dg1, db1) = ops._bn_param_grads(layer.norm1.weight, layer.norm1.bias, Cin, dev)
                 pend = (both[0], both[1], (layer.norm1.weight, mu1, iv1), dgam, dbet, direct, Cin)
-                dg1, db1 = (None, None) if direct else (dgam, dbet)
             else:
                 dg1, db1, _ = ops._bn_backward(gp1, Cin, slab, Ct, g_slab, Ct, sc1, sh1, mu1, iv1, layer.norm1.weight, npix, Cin,
                                                groups, 1, count, training, dt, accumulate_gx=True, dstats=dS[:, :, :Cin],

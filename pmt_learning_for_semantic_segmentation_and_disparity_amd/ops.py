@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import call, dtype_code, ptr, stream_ptr
+from ._lib import call, dtype_code, ptr, stream_ptr, try_call
 
 
 def _require_gpu(*ts):
@@ -367,6 +367,10 @@ class ConvSpec:
     def depth(self):
         return (self.D, self.Do, self.kd, self.sd, self.pad_d)
 
+    def cout(self, weight):
+        """Output channels of `weight`: (Cout, Cin, ..) for a convolution, (Cin, Cout, ..) for a transposed one."""
+        return weight.shape[0 if self.kind == 'conv' else 1]
+
 
 def _conv_launch(x, ldx, wp, y, ldy, bias, in_scale, in_shift, stats, B, H, W, Cin, Ho, Wo, Cout,
                  kh, kw, stride, dil, pad_t, pad_l, in_relu, groups, act, accumulate, nrep=1, depth=(1, 1, 1, 1, 0)):
@@ -411,18 +415,10 @@ def _bn_finalize(stats, nrep, bn, count, groups, synced=False):
     count = parallel.global_count(count)
     out = [torch.empty((groups, C), dtype=torch.float32, device=dev) for _ in range(4)]
     if stats is not None:
-        mom = 0.1 if bn.momentum is None else bn.momentum
-        if bn.num_batches_tracked is not None:
-            c = _ctx[0]
-            if c is not None and c.nbt is not None and c.arena is not None:
-                pass                                                  # applied by one multi-tensor add per step (train.TrainStep)
-            else:
-                if c is not None and c.nbt is not None:
-                    c.nbt.append((bn.num_batches_tracked, groups))   # recorded during the measuring step
-                bn.num_batches_tracked += groups
+        _bn_track(bn, groups)
         call("sdhip_bn_finalize", ptr(stats), stats.stride(-2), nrep, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
              ptr(bn.running_var), ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), C, groups, float(count),
-             float(bn.eps), float(mom), stream_ptr())
+             float(bn.eps), float(_bn_momentum(bn)), stream_ptr())
     else:
         call("sdhip_bn_finalize", None, 0, 1, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
              ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), C, groups, float(count), float(bn.eps), 0.0, stream_ptr())
@@ -435,8 +431,12 @@ def _fused_bn():
     return not _lib.DIAG_NO_FUSED_BN
 
 
+def _bn_momentum(bn):
+    return 0.1 if bn.momentum is None else bn.momentum
+
+
 def _bn_track(bn, groups):
-    """BatchNorm.num_batches_tracked bookkeeping of one train-mode normalisation (see _bn_finalize)."""
+    """BatchNorm.num_batches_tracked bookkeeping of one train-mode normalisation."""
     if bn.num_batches_tracked is None:
         return
     c = _ctx[0]
@@ -445,6 +445,17 @@ def _bn_track(bn, groups):
     if c is not None and c.nbt is not None:
         c.nbt.append((bn.num_batches_tracked, groups))           # recorded during the measuring step
     bn.num_batches_tracked += groups
+
+
+def _bn_param_grads(gamma, beta, C, device):
+    """Where a BatchNorm backward kernel puts dgamma / dbeta: (dgamma, dbeta, direct, returned).  direct: the two buffers
+    are the parameters' slices of the flat gradient buffer and the kernel accumulates into them — the autograd node then
+    returns `returned` = (None, None); otherwise they are fresh f32 [C] tensors and `returned` is the pair itself."""
+    tg, tb = _grad_target(gamma), _grad_target(beta)
+    if tg is not None and tb is not None:
+        return tg, tb, True, (None, None)
+    dgamma, dbeta = (torch.empty(C, dtype=torch.float32, device=device) for _ in range(2))
+    return dgamma, dbeta, False, (dgamma, dbeta)
 
 
 def bn_backward_two_phase(gy, ldg, x, ldx, gx, ldgx, scale, shift, mean, invstd, gamma, beta, npix, C, groups, act, count, dt):
@@ -458,14 +469,11 @@ def bn_backward_two_phase(gy, ldg, x, ldx, gx, ldgx, scale, shift, mean, invstd,
     call("sdhip_affine_act_bwd", ptr(gy), ldg, ptr(x), ldx, None, 0, ptr(scale), ptr(shift), ptr(dsc), ptr(dsh), NREP,
          npix, C, groups, act, 0, int(pz), dt, stream_ptr())
     parallel.all_reduce_sum_(both)            # sync-BN: the replica sums become global in place (`count` is the global count)
-    tg, tb = _grad_target(gamma), _grad_target(beta)
-    direct = tg is not None and tb is not None
-    dgamma = tg if direct else torch.empty(C, dtype=torch.float32, device=dev)
-    dbeta = tb if direct else torch.empty(C, dtype=torch.float32, device=dev)
+    dgamma, dbeta, direct, returned = _bn_param_grads(gamma, beta, C, dev)
     call("sdhip_bn_bwd_apply_fin", ptr(gy), ldg, ptr(x), ldx, ptr(gx), ldgx, ptr(scale), ptr(shift), ptr(dsc), ptr(dsh), NREP,
          ptr(gamma), ptr(mean), ptr(invstd), ptr(dgamma), ptr(dbeta), int(direct), parallel.param_scale(), npix, C, groups,
          float(count), act, dt, stream_ptr())
-    return (None, None) if direct else (dgamma, dbeta)
+    return returned
 
 
 def _bn_backward(gy, ldg, x, ldx, gx, ldgx, scale, shift, mean, invstd, gamma, npix, C, groups, act, count, train,
@@ -478,10 +486,7 @@ def _bn_backward(gy, ldg, x, ldx, gx, ldgx, scale, shift, mean, invstd, gamma, n
     dsc, dsh = both[0], both[1]
     call("sdhip_affine_act_bwd", ptr(gy), ldg, ptr(x), ldx, ptr(gx), ldgx, ptr(scale), ptr(shift), ptr(dsc), ptr(dsh), NREP,
          npix, C, groups, act, int(accumulate_gx), int(pz), dt, stream_ptr())
-    tg, tb = _grad_target(gamma), _grad_target(beta)
-    direct = tg is not None and tb is not None
-    dgamma = tg if direct else torch.empty(C, dtype=torch.float32, device=dev)
-    dbeta = tb if direct else torch.empty(C, dtype=torch.float32, device=dev)
+    dgamma, dbeta, direct, returned = _bn_param_grads(gamma, beta, C, dev)
     par_flag = 2 if direct else 0
     if dstats is None:
         dstats = torch.empty((groups, 2, C), dtype=torch.float64, device=dev)
@@ -494,10 +499,72 @@ def _bn_backward(gy, ldg, x, ldx, gx, ldgx, scale, shift, mean, invstd, gamma, n
         call("sdhip_bn_finalize_bwd", ptr(dsc), ptr(dsh), NREP, ptr(gamma), ptr(mean), ptr(invstd), None, None,
              ptr(dstats), dstats.stride(-2), int(accumulate_dstats), C, groups, float(parallel.global_count(count)), 1,
              stream_ptr())
-        return (None, None, dstats) if direct else (dgamma, dbeta, dstats)
-    call("sdhip_bn_finalize_bwd", ptr(dsc), ptr(dsh), NREP, ptr(gamma), ptr(mean), ptr(invstd), ptr(dgamma), ptr(dbeta),
-         ptr(dstats), dstats.stride(-2), int(accumulate_dstats) | par_flag, C, groups, float(count), int(train), stream_ptr())
-    return (None, None, dstats) if direct else (dgamma, dbeta, dstats)
+    else:
+        call("sdhip_bn_finalize_bwd", ptr(dsc), ptr(dsh), NREP, ptr(gamma), ptr(mean), ptr(invstd), ptr(dgamma), ptr(dbeta),
+             ptr(dstats), dstats.stride(-2), int(accumulate_dstats) | par_flag, C, groups, float(count), int(train), stream_ptr())
+    return (*returned, dstats)
+
+
+_BN_ACTS = (0, 1, 2, _lib.ACT_HSWISH, _lib.ACT_HSIGMOID)   # activations the two-phase BatchNorm backward kernels take
+
+
+def _bn_act_forward(yraw, ldr, bn, ws, count, groups, act, residual=None):
+    """The tail of a convolution-like node: y = act(BatchNorm(yraw)) (+ residual) from the raw output and the statistics
+    replicas `ws` (f64 [NREP][groups][2][C]) its epilogue summed; ws None => eval mode (running statistics).  `count`: the
+    LOCAL element count per group.  Returns (y, scale, shift, mean, invstd)."""
+    B, C, Ho, Wo = yraw.shape
+    npix, dt = B * Ho * Wo, dtype_code(yraw)
+    rv, ldres = nhwc_view(residual) if residual is not None else (None, 0)
+    y, ldy = alloc_nhwc(B, C, Ho, Wo, yraw.dtype, yraw.device)
+    if ws is not None and _fused_bn():
+        # one launch: every workgroup derives scale/shift of its channels from the statistics the conv just wrote
+        scale, shift, mean, invstd = [torch.empty((groups, C), dtype=torch.float32, device=yraw.device) for _ in range(4)]
+        _bn_track(bn, groups)
+        parallel.all_reduce_sum_(ws)         # sync-BN: the epilogue's replica sums become global, in place
+        call("sdhip_affine_act_bn", ptr(yraw), ldr, ptr(y), ldy, ptr(rv), ldres, ptr(ws), ws.stride(-2), NREP, ptr(bn.weight),
+             ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var), ptr(scale), ptr(shift), ptr(mean), ptr(invstd),
+             npix, C, groups, float(parallel.global_count(count)), float(bn.eps), float(_bn_momentum(bn)), act, dt, stream_ptr())
+    else:
+        scale, shift, mean, invstd = _bn_finalize(ws, NREP, bn, count, groups)
+        call("sdhip_affine_act", ptr(yraw), ldr, ptr(y), ldy, ptr(rv), ldres, ptr(scale), ptr(shift), npix, C, groups, act, dt,
+             stream_ptr())
+    return y, scale, shift, mean, invstd
+
+
+def _bn_act_backward(g, ldg, yraw, ldraw, scale, shift, mean, invstd, gamma, beta, groups, act, count, train, presummed=None,
+                     out=None):
+    """Backward of _bn_act_forward w.r.t. yraw, the statistics path included: (graw, ldgr, dgamma, dbeta), dgamma / dbeta
+    None when accumulated straight into the flat gradient buffer.  `count`: the LOCAL element count per group.
+    presummed: f64 [NREP][groups][2][C] sums the producer of g already took against yraw (BNSlot, the DenseNet block's
+    conv2 data gradient) — the reduction pass is skipped.  out: (tensor, ld) to write graw into (may be g itself: the
+    kernels are elementwise) instead of a fresh tensor."""
+    B, C, Ho, Wo = yraw.shape
+    npix, dt = B * Ho * Wo, dtype_code(yraw)
+    graw, ldgr = out if out is not None else alloc_nhwc(B, C, Ho, Wo, yraw.dtype, yraw.device)
+    if presummed is not None:
+        dgamma, dbeta, direct, returned = _bn_param_grads(gamma, beta, C, yraw.device)
+        parallel.all_reduce_sum_(presummed)
+        call("sdhip_bn_bwd_apply_fin_d", ptr(g), ldg, ptr(yraw), ldraw, ptr(graw), ldgr, ptr(scale), ptr(shift), ptr(presummed), NREP,
+             ptr(gamma), ptr(mean), ptr(invstd), ptr(dgamma), ptr(dbeta), int(direct), parallel.param_scale(), npix, C, groups,
+             float(parallel.global_count(count)), act, dt, stream_ptr())
+        return graw, ldgr, *returned
+    if train and act not in _BN_ACTS:
+        # the one-pass form below leaves the statistics path to its caller, and there is no kernel for it here
+        raise _lib.SdhipError("train-mode BatchNorm backward: activation %d is not one the two-phase kernels take" % act)
+    if train and _fused_bn():
+        dgamma, dbeta = bn_backward_two_phase(g, ldg, yraw, ldraw, graw, ldgr, scale, shift, mean, invstd, gamma, beta, npix, C,
+                                              groups, act, parallel.global_count(count), dt)
+    elif train:
+        # two-phase: reductions only (no gradient written), per-channel finalize, then ONE pass writes the complete
+        # gradient of the conv output — 10 bytes per element instead of 12
+        dgamma, dbeta, dS = _bn_backward(g, ldg, yraw, ldraw, None, 0, scale, shift, mean, invstd, gamma, npix, C, groups, act,
+                                         count, True, dt, beta=beta)
+        call("sdhip_bn_bwd_apply", ptr(g), ldg, ptr(yraw), ldraw, ptr(graw), ldgr, ptr(scale), ptr(shift), ptr(dS), C, npix, C,
+             groups, act, dt, stream_ptr())
+    else:
+        dgamma, dbeta, _ = _bn_backward(g, ldg, yraw, ldraw, graw, ldgr, scale, shift, mean, invstd, gamma, npix, C, groups, act,
+                                        count, False, dt, beta=beta)
+    return graw, ldgr, dgamma, dbeta
 
 
 class GradSlot:
@@ -536,12 +603,11 @@ class BNSlot:
 
 def _conv_backward(ctx_spec, xv, ldx, weight, g, ldg, in_scale, in_shift, in_relu, groups, need_x, need_w, bias=None, acc_into=None,
                    addend=None, bn_slot=None):
-    has_bias = bias is not None
     """dgrad (w.r.t. the post-prologue input) and wgrad of one conv; returns (g_post, gw, gb)."""
     spec = ctx_spec
     Bimg, Cin, H, W = xv.shape
     B = Bimg // spec.D
-    Cout = weight.shape[0] if spec.kind == 'conv' else weight.shape[1]
+    Cout = spec.cout(weight)
     dt = dtype_code(xv)
     gpost = gw = gb = None
     if need_x:
@@ -560,15 +626,12 @@ def _conv_backward(ctx_spec, xv, ldx, weight, g, ldg, in_scale, in_shift, in_rel
             gpost, ldgp = alloc_nhwc(Bimg, Cin, H, W, xv.dtype, xv.device)
             sums = _zeros((NREP, bn_slot.groups, 2, Cin), torch.float64, xv.device)[0]
             ov, ldo = nhwc_view(other) if other is not None else (None, 0)
-            rc = _lib._lib.sdhip_conv2d_fwd_bnbwd(ptr(g), ptr(wd), ptr(gpost), ptr(sums), Cin, NREP, ptr(bn_slot.u), bn_slot.ldu,
-                                                  ptr(bn_slot.scale), ptr(bn_slot.shift), ptr(ov), ldo, B, spec.Ho, spec.Wo, Cout, ldg,
-                                                  H, W, Cin, ldgp, spec.kh, spec.kw, spec.dil, spec.dil * (spec.kh - 1) - spec.pad_t,
-                                                  spec.dil * (spec.kw - 1) - spec.pad_l, bn_slot.groups, 0, dtype_code(xv), stream_ptr())
-            if rc == 0:
+            fused_bn = try_call("sdhip_conv2d_fwd_bnbwd", ptr(g), ptr(wd), ptr(gpost), ptr(sums), Cin, NREP, ptr(bn_slot.u), bn_slot.ldu,
+                                ptr(bn_slot.scale), ptr(bn_slot.shift), ptr(ov), ldo, B, spec.Ho, spec.Wo, Cout, ldg, H, W, Cin, ldgp,
+                                spec.kh, spec.kw, spec.dil, spec.dil * (spec.kh - 1) - spec.pad_t,
+                                spec.dil * (spec.kw - 1) - spec.pad_l, bn_slot.groups, 0, dt, stream_ptr())
+            if fused_bn:
                 bn_slot.sums, bn_slot.gptr = sums, gpost.data_ptr()
-                fused_bn = True
-            elif rc != _lib.ERR_UNSUPPORTED:
-                raise _lib.SdhipError("sdhip_conv2d_fwd_bnbwd failed (%d): %s" % (rc, _lib._lib.sdhip_last_error().decode()))
         # Conv3d(k=3, stride 2, padding 1) over even extents (hourglass conv1 / conv3, stackhourglass.py:13-19): its data gradient is
         # the transposed convolution that doubles every extent — eight sub-pixel phases of 1..8 taps over dY itself (27 taps per dY
         # voxel), not a stride-1 correlation over the zero-stuffed dY (8 x 27: seven of eight products are zeros)
@@ -603,11 +666,8 @@ def _conv_backward(ctx_spec, xv, ldx, weight, g, ldg, in_scale, in_shift, in_rel
         fused_add = fused_bn
         if not fused_bn and addend is not None and spec.kd == 1 and spec.D == 1 and spec.dil == 1 and gsrc is g:
             av, lda = nhwc_view(addend)
-            rc = _lib._lib.sdhip_conv2d_fwd_add(ptr(gsrc), ptr(wd), ptr(gpost), ptr(av), lda, B, Hg, Wg, Cout, ldsrc, H, W, Cin, ldgp,
-                                                spec.kh, spec.kw, pt, pl, dtype_code(xv), stream_ptr())
-            if rc not in (0, _lib.ERR_UNSUPPORTED):
-                raise _lib.SdhipError("sdhip_conv2d_fwd_add failed (%d): %s" % (rc, _lib._lib.sdhip_last_error().decode()))
-            fused_add = rc == 0
+            fused_add = try_call("sdhip_conv2d_fwd_add", ptr(gsrc), ptr(wd), ptr(gpost), ptr(av), lda, B, Hg, Wg, Cout, ldsrc, H, W, Cin,
+                                 ldgp, spec.kh, spec.kw, pt, pl, dt, stream_ptr())
         if not fused_add:
             _conv_launch(gsrc, ldsrc, wd, gpost, ldgp, None, None, None, None, B, Hg, Wg, Cout, H, W, Cin,
                          spec.kh, spec.kw, 1, spec.dil, pt, pl, False, 1, 0, acc_into is not None, 1, (Dg, spec.D, spec.kd, 1, pd))
@@ -636,7 +696,7 @@ def wgrad(xv, ldx, g, ldg, weight, bias, spec, in_scale=None, in_shift=None, in_
 def _wgrad_impl(xv, ldx, g, ldg, weight, bias, spec, in_scale, in_shift, in_relu, groups):
     Bimg, Cin, H, W = xv.shape
     B = Bimg // spec.D
-    Cout = weight.shape[0] if spec.kind == 'conv' else weight.shape[1]
+    Cout = spec.cout(weight)
     dt = dtype_code(xv)
     T = spec.kh * spec.kw
     per = _lib.packed_elems(Cout, Cin, T, dt)
@@ -700,7 +760,7 @@ class _ConvFn(torch.autograd.Function):
         Bimg, Cin, H, W = x.shape
         B = Bimg // spec.D
         xv, ldx = aligned_view(x)
-        Cout = weight.shape[0] if spec.kind == 'conv' else weight.shape[1]
+        Cout = spec.cout(weight)
         wp = packed_weight(weight, spec.kind, 'fwd', x.dtype)
         y, ldy = alloc_nhwc(B * spec.Do, Cout, spec.Ho, spec.Wo, x.dtype, x.device)
         _conv_launch(xv, ldx, wp, y, ldy, bias.detach() if bias is not None else None, None, None, None, B, H, W, Cin,
@@ -715,7 +775,7 @@ class _ConvFn(torch.autograd.Function):
         xv, weight, bias, ysaved = ctx.saved_tensors
         spec, act = ctx.spec, ctx.act
         B = xv.shape[0] // spec.D * spec.Do      # output images
-        Cout = weight.shape[0] if spec.kind == 'conv' else weight.shape[1]
+        Cout = spec.cout(weight)
         g, ldg = aligned_view(gy)
         if act:   # activation fused in the epilogue: derivative from the stored output
             g2, ldg2 = alloc_nhwc(B, Cout, spec.Ho, spec.Wo, xv.dtype, xv.device)
@@ -725,9 +785,6 @@ class _ConvFn(torch.autograd.Function):
         gx, gw, gb = _conv_backward(spec, xv, ctx.ldx, weight, g, ldg, None, None, False, 1, ctx.needs_input_grad[0],
                                     ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2]), bias)
         return gx, gw, gb, None, None
-
-
-_BN_ACTS = (0, 1, 2, _lib.ACT_HSWISH, _lib.ACT_HSIGMOID)   # activations the two-phase BatchNorm backward kernels take
 
 
 class _ConvBNActFn(torch.autograd.Function):
@@ -743,7 +800,7 @@ class _ConvBNActFn(torch.autograd.Function):
         Btrue = Bimg // spec.D
         B = Btrue * spec.Do                      # output images
         xv, ldx = aligned_view(x)
-        Cout = weight.shape[0] if spec.kind == 'conv' else weight.shape[1]
+        Cout = spec.cout(weight)
         wp = packed_weight(weight, spec.kind, 'fwd', x.dtype)
         yraw, ldr_ = alloc_nhwc(B, Cout, spec.Ho, spec.Wo, x.dtype, x.device)
         train = bn.training
@@ -751,21 +808,7 @@ class _ConvBNActFn(torch.autograd.Function):
         _conv_launch(xv, ldx, wp, yraw, ldr_, None, None, None, ws, Btrue, H, W, Cin, spec.Ho, spec.Wo, Cout,
                      spec.kh, spec.kw, spec.stride, spec.dil, spec.pad_t, spec.pad_l, False, groups, 0, False, NREP, spec.depth())
         count = (B // groups) * spec.Ho * spec.Wo
-        rv, ldr = nhwc_view(residual) if residual is not None else (None, 0)
-        y, ldy = alloc_nhwc(B, Cout, spec.Ho, spec.Wo, x.dtype, x.device)
-        if train and _fused_bn():
-            # one launch: every workgroup derives scale/shift of its channels from the statistics the conv just wrote
-            scale, shift, mean, invstd = [torch.empty((groups, Cout), dtype=torch.float32, device=x.device) for _ in range(4)]
-            _bn_track(bn, groups)
-            parallel.all_reduce_sum_(ws)         # sync-BN: the conv epilogue's replica sums become global, in place
-            call("sdhip_affine_act_bn", ptr(yraw), ldr_, ptr(y), ldy, ptr(rv), ldr, ptr(ws), ws.stride(-2), NREP, ptr(bn.weight),
-                 ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var), ptr(scale), ptr(shift), ptr(mean), ptr(invstd),
-                 B * spec.Ho * spec.Wo, Cout, groups, float(parallel.global_count(count)), float(bn.eps),
-                 float(0.1 if bn.momentum is None else bn.momentum), act, dtype_code(x), stream_ptr())
-        else:
-            scale, shift, mean, invstd = _bn_finalize(ws, NREP, bn, count, groups)
-            call("sdhip_affine_act", ptr(yraw), ldr_, ptr(y), ldy, ptr(rv), ldr, ptr(scale), ptr(shift), B * spec.Ho * spec.Wo,
-                 Cout, groups, act, dtype_code(x), stream_ptr())
+        y, scale, shift, mean, invstd = _bn_act_forward(yraw, ldr_, bn, ws, count, groups, act, residual)
         ctx.spec, ctx.act, ctx.groups, ctx.ldx, ctx.count, ctx.train = spec, act, groups, ldx, count, train
         ctx.ldraw = ldr_
         ctx.has_res = residual is not None
@@ -778,40 +821,13 @@ class _ConvBNActFn(torch.autograd.Function):
     def backward(ctx, gy):
         xv, weight, gamma, beta, yraw, scale, shift, mean, invstd = ctx.saved_tensors
         spec, groups = ctx.spec, ctx.groups
-        B = yraw.shape[0]
-        Cout = yraw.shape[1]
-        npix = B * spec.Ho * spec.Wo
-        dt = dtype_code(xv)
         g, ldg = nhwc_view(gy)
-        graw, ldgr = alloc_nhwc(B, Cout, spec.Ho, spec.Wo, xv.dtype, xv.device)
-        ldraw = ctx.ldraw
-        ob = ctx.out_bn
+        ob, sums = ctx.out_bn, None
         if ob is not None and ob.sums is not None and ob.gptr == g.data_ptr() and ctx.train and _fused_bn():
             # the node that produced gy already summed it against yraw (BNSlot): straight to the second phase
-            tg, tb = _grad_target(gamma), _grad_target(beta)
-            direct = tg is not None and tb is not None
-            dgamma = tg if direct else torch.empty(Cout, dtype=torch.float32, device=xv.device)
-            dbeta = tb if direct else torch.empty(Cout, dtype=torch.float32, device=xv.device)
-            parallel.all_reduce_sum_(ob.sums)
-            call("sdhip_bn_bwd_apply_fin_d", ptr(g), ldg, ptr(yraw), ldraw, ptr(graw), ldgr, ptr(scale), ptr(shift), ptr(ob.sums), NREP,
-                 ptr(gamma), ptr(mean), ptr(invstd), ptr(dgamma), ptr(dbeta), int(direct), parallel.param_scale(), npix, Cout, groups,
-                 float(parallel.global_count(ctx.count)), ctx.act, dt, stream_ptr())
-            if direct:
-                dgamma = dbeta = None
-            ob.sums, ob.gptr = None, 0
-        elif ctx.train and ctx.act in _BN_ACTS and _fused_bn():
-            dgamma, dbeta = bn_backward_two_phase(g, ldg, yraw, ldraw, graw, ldgr, scale, shift, mean, invstd, gamma, beta, npix,
-                                                  Cout, groups, ctx.act, parallel.global_count(ctx.count), dt)
-        elif ctx.train and ctx.act in _BN_ACTS:
-            # two-phase: reductions only (no gradient written), per-channel finalize, then ONE pass writes the complete
-            # gradient of the conv output — 10 bytes per element instead of 12
-            dgamma, dbeta, dS = _bn_backward(g, ldg, yraw, ldraw, None, 0, scale, shift, mean, invstd, gamma, npix, Cout,
-                                             groups, ctx.act, ctx.count, True, dt, beta=beta)
-            call("sdhip_bn_bwd_apply", ptr(g), ldg, ptr(yraw), ldraw, ptr(graw), ldgr, ptr(scale), ptr(shift), ptr(dS), Cout,
-                 npix, Cout, groups, ctx.act, dt, stream_ptr())
-        else:
-            dgamma, dbeta, dS = _bn_backward(g, ldg, yraw, ldraw, graw, ldgr, scale, shift, mean, invstd, gamma, npix, Cout,
-                                             groups, ctx.act, ctx.count, ctx.train, dt, beta=beta)
+            sums, ob.sums, ob.gptr = ob.sums, None, 0
+        graw, ldgr, dgamma, dbeta = _bn_act_backward(g, ldg, yraw, ctx.ldraw, scale, shift, mean, invstd, gamma, beta, groups,
+                                                     ctx.act, ctx.count, ctx.train, presummed=sums)
         acc = addend = None
         if ctx.in_slot is not None and ctx.in_slot.g is not None and ctx.needs_input_grad[0]:
             parked, ctx.in_slot.g = ctx.in_slot.g, None       # the skip consumer of x already ran: add to its contribution
@@ -1895,20 +1911,7 @@ class _Deconv3dS2BNActFn(torch.autograd.Function):
             call("sdhip_conv2d_fwd_phase", ptr(xv), ptr(wp), ptr(yraw), ptr(ws), ws.stride(-2) if ws is not None else 0, NREP if ws is not None else 1,
                  Btrue, H, W, Cin, ldx, Cout, ldr_, 1 + ph, 1 + pw, D, 1 + pd, groups, pd, ph, pw, dtype_code(x), stream_ptr())
         count = (Bo // groups) * 4 * H * W
-        rv, ldr = nhwc_view(residual) if residual is not None else (None, 0)
-        y, ldy = alloc_nhwc(Bo, Cout, 2 * H, 2 * W, x.dtype, x.device)
-        if train and _fused_bn():
-            scale, shift, mean, invstd = [torch.empty((groups, Cout), dtype=torch.float32, device=x.device) for _ in range(4)]
-            _bn_track(bn, groups)
-            parallel.all_reduce_sum_(ws)
-            call("sdhip_affine_act_bn", ptr(yraw), ldr_, ptr(y), ldy, ptr(rv), ldr, ptr(ws), ws.stride(-2), NREP, ptr(bn.weight),
-                 ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var), ptr(scale), ptr(shift), ptr(mean), ptr(invstd),
-                 Bo * 4 * H * W, Cout, groups, float(parallel.global_count(count)), float(bn.eps),
-                 float(0.1 if bn.momentum is None else bn.momentum), act, dtype_code(x), stream_ptr())
-        else:
-            scale, shift, mean, invstd = _bn_finalize(ws, NREP, bn, count, groups)
-            call("sdhip_affine_act", ptr(yraw), ldr_, ptr(y), ldy, ptr(rv), ldr, ptr(scale), ptr(shift), Bo * 4 * H * W,
-                 Cout, groups, act, dtype_code(x), stream_ptr())
+        y, scale, shift, mean, invstd = _bn_act_forward(yraw, ldr_, bn, ws, count, groups, act, residual)
         ctx.cfg = (D, act, groups, ldx, ldr_, count, train, residual is not None)
         ctx.save_for_backward(xv, weight, gamma, beta, yraw, scale, shift, mean, invstd)
         return y
@@ -1919,23 +1922,11 @@ class _Deconv3dS2BNActFn(torch.autograd.Function):
         D, act, groups, ldx, ldraw, count, train, has_res = ctx.cfg
         Bimg, Cin, H, W = xv.shape
         Btrue = Bimg // D
-        Bo, Cout = yraw.shape[0], yraw.shape[1]
+        Cout = yraw.shape[1]
         Ho, Wo = 2 * H, 2 * W
-        npix = Bo * Ho * Wo
-        dt = dtype_code(xv)
         g, ldg = nhwc_view(gy)
-        graw, ldgr = alloc_nhwc(Bo, Cout, Ho, Wo, xv.dtype, xv.device)
-        if train and act in (0, 1, 2) and _fused_bn():
-            dgamma, dbeta = bn_backward_two_phase(g, ldg, yraw, ldraw, graw, ldgr, scale, shift, mean, invstd, gamma, beta, npix,
-                                                  Cout, groups, act, parallel.global_count(count), dt)
-        elif train and act in (0, 1, 2):
-            dgamma, dbeta, dS = _bn_backward(g, ldg, yraw, ldraw, None, 0, scale, shift, mean, invstd, gamma, npix, Cout,
-                                             groups, act, count, True, dt, beta=beta)
-            call("sdhip_bn_bwd_apply", ptr(g), ldg, ptr(yraw), ldraw, ptr(graw), ldgr, ptr(scale), ptr(shift), ptr(dS), Cout,
-                 npix, Cout, groups, act, dt, stream_ptr())
-        else:
-            dgamma, dbeta, dS = _bn_backward(g, ldg, yraw, ldraw, graw, ldgr, scale, shift, mean, invstd, gamma, npix, Cout,
-                                             groups, act, count, train, dt, beta=beta)
+        graw, ldgr, dgamma, dbeta = _bn_act_backward(g, ldg, yraw, ldraw, scale, shift, mean, invstd, gamma, beta, groups, act,
+                                                     count, train)
         # adjoint of the transposed convolution: Conv3d(weight viewed as (out = Cin, in = Cout), stride 2, padding 1) of graw
         spec = ConvSpec('conv', 3, 3, 2, 1, 1, 1, H, W, 2 * D, D, 3, 2, 1)
         gx = None
@@ -2166,19 +2157,7 @@ class _DWConvBNActFn(torch.autograd.Function):
         call("sdhip_dw_conv_fwd", ptr(xv), ldx, ptr(weight.detach()), ptr(yraw), ldr, ptr(ws), C, NREP, ptr(pool), parts,
              B, H, W, C, k, stride, groups, dt, stream_ptr())
         count = (B // groups) * Ho * Wo
-        y, ldy = alloc_nhwc(B, C, Ho, Wo, x.dtype, x.device)
-        if train and _fused_bn():
-            scale, shift, mean, invstd = [torch.empty((groups, C), dtype=torch.float32, device=x.device) for _ in range(4)]
-            _bn_track(bn, groups)
-            parallel.all_reduce_sum_(ws)         # sync-BN: the epilogue's replica sums become global, in place
-            call("sdhip_affine_act_bn", ptr(yraw), ldr, ptr(y), ldy, None, 0, ptr(ws), ws.stride(-2), NREP, ptr(bn.weight),
-                 ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var), ptr(scale), ptr(shift), ptr(mean), ptr(invstd),
-                 B * Ho * Wo, C, groups, float(parallel.global_count(count)), float(bn.eps),
-                 float(0.1 if bn.momentum is None else bn.momentum), act, dt, stream_ptr())
-        else:
-            scale, shift, mean, invstd = _bn_finalize(ws, NREP, bn, count, groups)
-            call("sdhip_affine_act", ptr(yraw), ldr, ptr(y), ldy, None, 0, ptr(scale), ptr(shift), B * Ho * Wo, C, groups, act,
-                 dt, stream_ptr())
+        y, scale, shift, mean, invstd = _bn_act_forward(yraw, ldr, bn, ws, count, groups, act)
         if side is not None:
             side.pool, side.scale, side.shift, side.groups = pool, scale, shift, groups
         ctx.cfg = (k, stride, act, groups, ldx, ldr, count, train)
@@ -2190,22 +2169,10 @@ class _DWConvBNActFn(torch.autograd.Function):
         xv, weight, gamma, beta, yraw, scale, shift, mean, invstd = ctx.saved_tensors
         k, stride, act, groups, ldx, ldraw, count, train = ctx.cfg
         B, C, H, W = xv.shape
-        Ho, Wo = yraw.shape[2], yraw.shape[3]
-        npix = B * Ho * Wo
         dt = dtype_code(xv)
         g, ldg = nhwc_view(gy)
-        graw, ldgr = alloc_nhwc(B, C, Ho, Wo, xv.dtype, xv.device)
-        if train and _fused_bn():
-            dgamma, dbeta = bn_backward_two_phase(g, ldg, yraw, ldraw, graw, ldgr, scale, shift, mean, invstd, gamma, beta, npix,
-                                                  C, groups, act, parallel.global_count(count), dt)
-        elif train:
-            dgamma, dbeta, dS = _bn_backward(g, ldg, yraw, ldraw, None, 0, scale, shift, mean, invstd, gamma, npix, C, groups, act,
-                                             count, True, dt, beta=beta)
-            call("sdhip_bn_bwd_apply", ptr(g), ldg, ptr(yraw), ldraw, ptr(graw), ldgr, ptr(scale), ptr(shift), ptr(dS), C,
-                 npix, C, groups, act, dt, stream_ptr())
-        else:
-            dgamma, dbeta, _ = _bn_backward(g, ldg, yraw, ldraw, graw, ldgr, scale, shift, mean, invstd, gamma, npix, C, groups,
-                                            act, count, False, dt, beta=beta)
+        graw, ldgr, dgamma, dbeta = _bn_act_backward(g, ldg, yraw, ldraw, scale, shift, mean, invstd, gamma, beta, groups, act,
+                                                     count, train)
         gx = None
         if ctx.needs_input_grad[0]:
             gx, ldgx = alloc_nhwc(B, C, H, W, xv.dtype, xv.device)
