@@ -385,6 +385,31 @@ long sdhip_lovasz_workspace_bytes(long npix, int C);
 int sdhip_lovasz_softmax(const void* logits, int ldy, const float* target, int ldt, void* grad, int ldg,
                          double* loss, long npix, int C, float weight, void* workspace, long workspace_bytes,
                          int ignore_void, int dtype, void* stream);
+/* The other terms lossSeg_fn puts on a segmentation head (`-loss`, `-segWeight`: losses/multiLosses.py:44-115), all of them
+ * functions of four sums per (image b, class c) over the image's H*W = hw pixels, with p = softmax(logits), lp = log_softmax,
+ * T = target (one-hot f32, a void pixel is an all-zero row): TP = sum T*p, P = sum p, G = sum T, Q = sum T*lp.  N = B*hw.
+ *   cross-entropy with class weights w_c   ce_weight * (1/N) sum_b sum_c -w_c*Q            (util/utilTorchLoss.py:373-378)
+ *   SDHIP_SEG_TVERSKY       1.5 * mean_c(w_c * mean_b(1 - TP / (TP + (G-TP) + 0.3*(P-TP) + 1e-6)))     (tversky_loss2, :407-426)
+ *   SDHIP_SEG_DICE          mean_{b,c}([G > 1] - 2*TP / (P + G + 1))                                   (dice_loss, :429-436)
+ *   SDHIP_SEG_DICE_ENTROPY  (1/N) sum_b sum_c -D*Q, D = 10*([G > 1] - 2*TP/(P+G+1)), differentiated through D (diceEntropy, :439-448)
+ * Three calls on one stream, sharing a caller-owned workspace of sdhip_seg_terms_workspace_bytes(B, hw, C) bytes (16-byte
+ * aligned; < 0 for an unsupported shape; C <= 32), none of whose bytes need initialising:
+ *   sdhip_seg_sums       one pass over logits and target; every workgroup STORES its partial sums into a slot of its own;
+ *   sdhip_seg_finish     folds the slots in a fixed order in f64, does loss += the value of the active terms (ce_weight = 0:
+ *                        no cross-entropy; terms: SDHIP_SEG_* bits; class_weights: C f32 on the device or NULL = all 1) and
+ *                        writes the per-(b,c) gradient coefficients into the workspace;
+ *   sdhip_seg_terms_bwd  WRITES grad = d(those terms)/d logits (grad != NULL; channels >= C of its pixel stride untouched).
+ * No float atomics anywhere: value and gradient are bitwise reproducible. */
+#define SDHIP_SEG_TVERSKY 1
+#define SDHIP_SEG_DICE 2
+#define SDHIP_SEG_DICE_ENTROPY 4
+int sdhip_seg_terms_workspace_bytes(int B, long hw, int C);
+int sdhip_seg_sums(const void* logits, int ldy, const float* target, int ldt, int B, long hw, int C, void* workspace,
+                   long workspace_bytes, int dtype, void* stream);
+int sdhip_seg_finish(void* workspace, long workspace_bytes, const float* class_weights, double* loss, int B, long hw, int C,
+                     float ce_weight, int terms, void* stream);
+int sdhip_seg_terms_bwd(const void* logits, int ldy, const float* target, int ldt, void* grad, int ldg, const void* workspace,
+                        long workspace_bytes, int B, long hw, int C, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Uncertainty-weighted multitask loss (`-multaskloss 1|2`: multiTask_loss, util/utilTorchLoss.py:521-540, called at

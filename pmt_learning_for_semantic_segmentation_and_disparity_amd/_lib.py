@@ -109,6 +109,10 @@ SIGNATURES = {
     "sdhip_warp_blend_fwd": [_p, _i, _p, _i, _p, _i, _f, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
     "sdhip_warp_blend_bwd": [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _f, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _i,
                              _i, _i, _i, _i, _i, _p],
+    "sdhip_seg_terms_workspace_bytes": [_i, _l, _i],
+    "sdhip_seg_sums": [_p, _i, _p, _i, _i, _l, _i, _p, _l, _i, _p],
+    "sdhip_seg_finish": [_p, _l, _p, _p, _i, _l, _i, _f, _i, _p],
+    "sdhip_seg_terms_bwd": [_p, _i, _p, _i, _p, _i, _p, _l, _i, _l, _i, _i, _p],
 }
 _lib.sdhip_lovasz_workspace_bytes.argtypes = [_l, _i]
 _lib.sdhip_lovasz_workspace_bytes.restype = _l
@@ -133,6 +137,17 @@ class WgradItem(ctypes.Structure):
 
 def lovasz_workspace_bytes(npix, C):
     return _lib.sdhip_lovasz_workspace_bytes(npix, C)
+
+
+SEG_TVERSKY, SEG_DICE, SEG_DICE_ENTROPY = 1, 2, 4    # SDHIP_SEG_* of include/sdhip.h
+
+
+def seg_terms_workspace_bytes(B, hw, C):
+    """Workspace of sdhip_seg_sums / sdhip_seg_finish / sdhip_seg_terms_bwd for this shape (include/sdhip.h)."""
+    n = _lib.sdhip_seg_terms_workspace_bytes(B, hw, C)
+    if n <= 0:
+        raise SdhipError("sdhip_seg_terms_workspace_bytes: unsupported shape (B %d, %d pixels, C %d; C <= 32)" % (B, hw, C))
+    return n
 
 
 def dw_pool_parts(H, W, C, k, stride, dt):

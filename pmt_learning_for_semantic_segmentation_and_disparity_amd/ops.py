@@ -1407,6 +1407,139 @@ def warp_blend(seg_left, seg_right, disp, gate, softmax_gate=False):
 
 # ============================================================================ losses of the timed step
 _lovasz_ws = {}
+_seg_ws = {}
+
+# entries of the reference's `-loss` list (losses/multiLosses.py:8-128) built here / defined upstream but not built
+SEG_LOSS_TERMS = ("cross_entropy", "lovasz_loss", "tversky_loss2", "dice_loss", "diceEntropy")
+SEG_LOSS_NOT_BUILT = ("tversky_loss", "area_ce", "area_hinge", "binary_ce", "categoricalNlll", "ohm_loss", "dual_edge_reg")
+SEG_MAX_CLASSES = 32
+
+
+def seg_loss_plan(loss):
+    """(ce_weight, lovasz_weight, term bits) of a `-loss` list as lossSeg_fn reads it: cross-entropy and the Lovasz term that
+    follows it are halved when the list has more than two entries (losses/multiLosses.py:64-72), Lovasz without
+    cross-entropy has factor 1 (:80-81), diceEntropy counts only when dice_loss is absent (:107-115).  A name the reference
+    defines but this package does not build raises NotImplementedError; any other string raises ValueError (the reference
+    ignores it silently)."""
+    names = [loss] if isinstance(loss, str) else list(loss)
+    for n in names:
+        if n in SEG_LOSS_NOT_BUILT:
+            raise NotImplementedError("segmentation loss term %r is not built (built: %s)" % (n, ", ".join(SEG_LOSS_TERMS)))
+        if n not in SEG_LOSS_TERMS:
+            raise ValueError("unknown segmentation loss term %r (known: %s)" % (n, ", ".join(SEG_LOSS_TERMS + SEG_LOSS_NOT_BUILT)))
+    ce = "cross_entropy" in names
+    w1 = 0.5 if ce and len(names) > 2 else 1.0
+    terms = 0
+    if "tversky_loss2" in names:
+        terms |= _lib.SEG_TVERSKY
+    if "dice_loss" in names:
+        terms |= _lib.SEG_DICE
+    elif "diceEntropy" in names:
+        terms |= _lib.SEG_DICE_ENTROPY
+    return (w1 if ce else 0.0), (w1 if "lovasz_loss" in names else 0.0), terms
+
+
+def seg_class_weights(class_weights, C=None, device=None):
+    """The `-segWeight` table as the kernels read it: C f32 on the GPU (None stays None = no weights).  A sequence is uploaded
+    (do this once, before a step is captured); a tensor must already be f32 on the GPU."""
+    if class_weights is None:
+        return None
+    n = class_weights.numel() if isinstance(class_weights, torch.Tensor) else len(class_weights)
+    if C is not None and n != C:
+        raise _lib.SdhipError("class_weights has %d entries for %d classes" % (n, C))
+    if isinstance(class_weights, torch.Tensor):
+        _require_gpu(class_weights)
+        if class_weights.dtype != torch.float32 or class_weights.dim() != 1 or not class_weights.is_contiguous():
+            raise _lib.SdhipError("class_weights must be a contiguous 1-D f32 tensor")
+        return class_weights
+    if device is None or torch.device(device).type != "cuda":
+        raise _lib.SdhipError("sdhip ops need a GPU (got %s for class_weights); there is no CPU path" % device)
+    return torch.tensor([float(v) for v in class_weights], dtype=torch.float32, device=device)
+
+
+def _seg_terms(s, tv, ldt, grad, loss, ce_weight, terms, cw):
+    """loss += the sum-based terms of one segmentation head, grad = their gradient: the three launches of csrc/segloss.hip.
+    (tv, ldt): nhwc_view of the one-hot target."""
+    B, C, H, W = s.shape
+    sv, ld = nhwc_view(s)
+    nbytes = _lib.seg_terms_workspace_bytes(B, H * W, C)
+    key = (B, H * W, C, str(s.device))
+    ws = _seg_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+        _seg_ws[key] = ws
+    dt, st = dtype_code(s), stream_ptr()
+    call("sdhip_seg_sums", ptr(sv), ld, ptr(tv), ldt, B, H * W, C, ptr(ws), ws.numel(), dt, st)
+    call("sdhip_seg_finish", ptr(ws), ws.numel(), ptr(cw), ptr(loss), B, H * W, C, ce_weight, terms, st)
+    call("sdhip_seg_terms_bwd", ptr(sv), ld, ptr(tv), ldt, ptr(grad), C, ptr(ws), ws.numel(), B, H * W, C, dt, st)
+
+
+def _lovasz_term(s, tv, ldt, grad, loss, weight, ignore_void):
+    """loss += weight * Lovasz-softmax, grad += its gradient (in place, onto what the other terms left there)."""
+    B, C, H, W = s.shape
+    npix = B * H * W
+    sv, ld = nhwc_view(s)
+    nbytes = _lib.lovasz_workspace_bytes(npix, C)
+    key = (npix, C, str(s.device))
+    ws = _lovasz_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+        _lovasz_ws[key] = ws
+    call("sdhip_lovasz_softmax", ptr(sv), ld, ptr(tv), ldt, ptr(grad), C, ptr(loss), npix, C, weight, ptr(ws),
+         ws.numel(), int(ignore_void), dtype_code(s), stream_ptr())
+
+
+def _check_seg_args(logits, seg_t, class_weights):
+    if logits.dim() != 4 or tuple(seg_t.shape) != tuple(logits.shape):
+        raise _lib.SdhipError("segmentation logits and one-hot target must both be (B,C,H,W), got %s and %s"
+                              % (tuple(logits.shape), tuple(seg_t.shape)))
+    C = logits.shape[1]
+    if C > SEG_MAX_CLASSES:
+        raise _lib.SdhipError("the segmentation loss terms serve at most %d classes (got %d)" % (SEG_MAX_CLASSES, C))
+    if seg_t.dtype != torch.float32:
+        raise _lib.SdhipError("the one-hot segmentation target must be f32 (got %s)" % seg_t.dtype)
+    if class_weights is not None:
+        n = class_weights.numel() if isinstance(class_weights, torch.Tensor) else len(class_weights)
+        if n != C:
+            raise _lib.SdhipError("class_weights has %d entries for %d classes" % (n, C))
+
+
+class _SegLossFn(torch.autograd.Function):
+    """lossSeg_fn(loss, ...)[2] on one segmentation head (losses/multiLosses.py:8-128): value and gradient in one node."""
+
+    @staticmethod
+    def forward(ctx, logits, seg_t, plan, cw, ignore_void):
+        ce_weight, lovasz_weight, terms = plan
+        B, C, H, W = logits.shape
+        loss = torch.zeros(1, dtype=torch.float64, device=logits.device)
+        g = empty_nhwc(B, C, H, W, logits.dtype, logits.device)
+        tv, ldt = nhwc_view(seg_t)
+        _seg_terms(logits, tv, ldt, g, loss, ce_weight, terms, cw)
+        if lovasz_weight:
+            _lovasz_term(logits, tv, ldt, g, loss, lovasz_weight, ignore_void)
+        ctx.save_for_backward(g)
+        return loss.float().reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        g, = ctx.saved_tensors
+        return g * gout.to(g.dtype), None, None, None, None
+
+
+def seg_loss(logits, seg_target, loss=("cross_entropy",), class_weights=None, ignore_void=False):
+    """The segmentation loss of one head as the reference's lossSeg_fn(loss, seg_target, logits, CFG, ...)[2] adds it up.
+    logits (B,C,H,W) f32 / bf16, C <= 32; seg_target: one-hot f32 (B,C,H,W), a void pixel is an all-zero row (cityscapes /
+    kitti: the 20th channel already dropped).
+      loss          — the `-loss` list: cross_entropy, lovasz_loss, tversky_loss2, dice_loss, diceEntropy (seg_loss_plan)
+      class_weights — the `-segWeight 1` table of the dataset, supplied by the caller (length C): multiplies the
+                      cross-entropy and the Tversky term per class; never the dice terms or Lovasz
+      ignore_void   — the Lovasz term's rule for void pixels (train_loss)
+    Returns an f32 scalar; value and gradient are reproducible bit for bit except for the Lovasz term."""
+    plan = seg_loss_plan(loss)
+    _check_seg_args(logits, seg_target, class_weights)
+    _require_gpu(logits, seg_target)
+    cw = seg_class_weights(class_weights, logits.shape[1], logits.device)
+    return _SegLossFn.apply(logits, seg_target, plan, cw, bool(ignore_void))
 
 
 class _TrainLossFn(torch.autograd.Function):
@@ -1415,7 +1548,8 @@ class _TrainLossFn(torch.autograd.Function):
     the `ThreeOutPuts` networks, :157-158,298).  The gradients w.r.t. the network outputs are produced in the same pass."""
 
     @staticmethod
-    def forward(ctx, seg1, disp, seg2, seg_t, disp_t, use_lovasz, mask_invalid_disp=False, ignore_void=False, seg3=None):
+    def forward(ctx, seg1, disp, seg2, seg_t, disp_t, use_lovasz, mask_invalid_disp=False, ignore_void=False, seg3=None,
+                plan=None, cw=None):
         _require_gpu(seg1, disp, seg2, seg_t, disp_t, seg3)
         B, C, H, W = seg1.shape
         npix = B * H * W
@@ -1423,10 +1557,18 @@ class _TrainLossFn(torch.autograd.Function):
         loss = torch.zeros(1, dtype=torch.float64, device=seg1.device)
         tv, ldt = nhwc_view(seg_t)
         grads = []
-        for s in (seg1, seg2) if seg3 is None else (seg1, seg2, seg3):
+        lovasz_weight = 1.0
+        for i, s in enumerate((seg1, seg2) if seg3 is None else (seg1, seg2, seg3)):
             sv, ld = nhwc_view(s)
             g = empty_nhwc(B, C, H, W, s.dtype, s.device)
-            call("sdhip_ce_loss", ptr(sv), ld, ptr(tv), ldt, ptr(g), C, ptr(loss), npix, C, 1.0, dt, stream_ptr())
+            if plan is None:
+                call("sdhip_ce_loss", ptr(sv), ld, ptr(tv), ldt, ptr(g), C, ptr(loss), npix, C, 1.0, dt, stream_ptr())
+            elif i == 1 and plan is not None:      # seg2 takes the `-loss` list (torch_implementation.py:293)
+                ce_weight, lovasz_weight, terms = plan
+                use_lovasz = lovasz_weight != 0.0
+                _seg_terms(s, tv, ldt, g, loss, ce_weight, terms, cw)
+            else:                                   # seg1 / seg3: ['cross_entropy'] with the class weights (:279,297)
+                _seg_terms(s, tv, ldt, g, loss, 1.0, 0, cw)
             grads.append(g)
         dv, ldd = nhwc_view(disp)
         if ldd != 1:      # 1-channel map inside a padded pixel stride (direct conv output): densify
@@ -1435,16 +1577,8 @@ class _TrainLossFn(torch.autograd.Function):
             raise _lib.SdhipError("disparity target must be a dense (B,1,H,W) tensor")
         gd = torch.empty_like(dv)
         call("sdhip_l1_loss", ptr(dv), ptr(disp_t), ptr(gd), ptr(loss), npix, 1.0, int(mask_invalid_disp), dt, stream_ptr())
-        if use_lovasz:   # added onto the CE gradient of seg2 in place
-            s2, ld2 = nhwc_view(seg2)
-            nbytes = _lib.lovasz_workspace_bytes(npix, C)
-            key = (npix, C, str(seg1.device))
-            ws = _lovasz_ws.get(key)
-            if ws is None or ws.numel() < nbytes:
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=seg1.device)
-                _lovasz_ws[key] = ws
-            call("sdhip_lovasz_softmax", ptr(s2), ld2, ptr(tv), ldt, ptr(grads[1]), C, ptr(loss), npix, C, 1.0, ptr(ws),
-                 ws.numel(), int(ignore_void), dt, stream_ptr())
+        if use_lovasz:   # added onto the gradient of seg2's other terms in place
+            _lovasz_term(seg2, tv, ldt, grads[1], loss, lovasz_weight, ignore_void)
         total = loss
         ctx.save_for_backward(grads[0], gd, grads[1], grads[2] if seg3 is not None else None)
         return total.float()
@@ -1452,7 +1586,7 @@ class _TrainLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         g1, gd, g2, g3 = ctx.saved_tensors
-        return g1, gd, g2, None, None, None, None, None, g3   # d(total)/d(total) is 1 in the training step
+        return g1, gd, g2, None, None, None, None, None, g3, None, None   # d(total)/d(total) is 1 in the training step
 
 
 MT_IGNORE_INDEX = 19     # F.cross_entropy(..., ignore_index=19) of util/utilTorchLoss.py:533,535, whatever the class count
@@ -1586,15 +1720,26 @@ def loss_map_mean(m):
     return mean
 
 
-def train_loss(seg1, disp, seg2, seg_target, disp_target, use_lovasz=True, mask_invalid_disp=False, ignore_void=False, seg3=None):
+def train_loss(seg1, disp, seg2, seg_target, disp_target, use_lovasz=True, mask_invalid_disp=False, ignore_void=False, seg3=None,
+               loss=None, class_weights=None):
     """seg_target: one-hot f32 (B,C,H,W); disp_target: f32 (B,1,H,W); seg3 (optional): a third segmentation output that adds
     its cross-entropy (the warp networks).  The two dataset rules of losses/multiLosses.py are
     opt-in, both off by default (roses / garden, `ignore=None`, :11-17):
       ignore_void       — cityscapes / kitti (:19-21, the 20th one-hot channel dropped, `ignore=19`): an all-zero target row
                           marks a void pixel, removed from the Lovasz term.  Off: its label is argmax = class 0 and it counts.
                           (Its cross-entropy term is zero under either rule: sum(-t * log_softmax) over a zero row.)
-      mask_invalid_disp — disparities <= 0 are invalid (:134-141)."""
-    return _TrainLossFn.apply(seg1, disp, seg2, seg_target, disp_target, use_lovasz, mask_invalid_disp, ignore_void, seg3)
+      mask_invalid_disp — disparities <= 0 are invalid (:134-141).
+    loss (the reference's `-loss` list, seg_loss_plan) replaces `CE(seg2) [+ Lovasz(seg2)]` by the list's terms on seg2 and
+    then decides about Lovasz instead of use_lovasz; class_weights (`-segWeight 1`: the dataset's table, length C, from the
+    caller) multiplies the cross-entropy of seg1, seg2 and seg3 and the Tversky term.  With one of them given and the other
+    None, the list is what use_lovasz says and the weights are 1.  Both None: the step's original launches."""
+    if loss is None and class_weights is None:
+        return _TrainLossFn.apply(seg1, disp, seg2, seg_target, disp_target, use_lovasz, mask_invalid_disp, ignore_void, seg3)
+    plan = seg_loss_plan(loss if loss is not None else (("cross_entropy", "lovasz_loss") if use_lovasz else ("cross_entropy",)))
+    _check_seg_args(seg2, seg_target, class_weights)
+    _require_gpu(seg1, disp, seg2, seg_target, disp_target, seg3)
+    cw = seg_class_weights(class_weights, seg2.shape[1], seg2.device)
+    return _TrainLossFn.apply(seg1, disp, seg2, seg_target, disp_target, use_lovasz, mask_invalid_disp, ignore_void, seg3, plan, cw)
 
 
 # ============================================================================ dropout / global average pool

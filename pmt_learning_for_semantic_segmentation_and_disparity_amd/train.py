@@ -32,8 +32,19 @@ def flatten_parameters(model):
 
 class TrainStep:
     def __init__(self, model, dtype=torch.bfloat16, lr=0.0015, betas=(0.9, 0.999), eps=1e-7, use_lovasz=True,
-                 use_graph=True, world_size=1, process_group=None, use_side_stream=None, loss_fn=None, metrics=None, accumulate=1):
+                 use_graph=True, world_size=1, process_group=None, use_side_stream=None, loss_fn=None, metrics=None, accumulate=1,
+                 loss=None, class_weights=None):
         self.model, self.dtype, self.use_lovasz = model, dtype, use_lovasz
+        # `-loss` list of the second segmentation head and the `-segWeight 1` class table (ops.train_loss); both None: the
+        # default step.  The list is checked and the table uploaded here, once, so that the step captures into the hipGraph
+        if loss_fn is not None and (loss is not None or class_weights is not None):
+            raise _lib.SdhipError("TrainStep: a custom loss_fn computes the whole loss; loss / class_weights do not apply to it")
+        if getattr(model, "multiTaskLoss", 0) and (loss is not None or class_weights is not None):
+            raise _lib.SdhipError("TrainStep: the multitask modes have their own loss; loss / class_weights do not apply to them")
+        self.seg_loss = None if loss is None else tuple([loss] if isinstance(loss, str) else loss)
+        if self.seg_loss is not None:
+            ops.seg_loss_plan(self.seg_loss)
+        self.class_weights = ops.seg_class_weights(class_weights, device=next(model.parameters()).device)
         # metrics.StepMetrics (or None): scored inside the step on the second segmentation head and the disparity, as the
         # reference's lossSeg_fn(seg2) / lossDisp_fn calls do (torch_implementation.py:293,304) — one extra launch, graph-safe
         self.metrics = metrics
@@ -136,7 +147,8 @@ class TrainStep:
         else:
             # the `ThreeOutPuts` networks (warp.minidsnetDivide*) add the cross-entropy of their third segmentation map, outs[4]
             # (torch_implementation.py:157-158,298); Lovasz stays on outs[2], which the metrics score as well
-            loss = ops.train_loss(outs[0], outs[1], outs[2], seg, disp, self.use_lovasz, seg3=outs[4] if three else None)
+            loss = ops.train_loss(outs[0], outs[1], outs[2], seg, disp, self.use_lovasz, seg3=outs[4] if three else None,
+                                  loss=self.seg_loss, class_weights=self.class_weights)
         if (mt or three) and self.grad_free is None:
             self.grad_free = _unreached_parameters(self.model, loss)
         if self.metrics is not None and self.loss_fn is None:
