@@ -5,18 +5,22 @@ fails to load, importing this module raises.  `import torch` happens first on
 purpose: libsdhip.so needs `libamdhip64.so.7` by soname and must bind to the HIP
 runtime PyTorch-ROCm has already mapped, so that stream handles and device
 pointers are shared between the two.
+
+include/sdhip.h is the only copy of the ABI: the argument and return types of every
+entry point (`SIGNATURES`) and the numeric constants (`CONSTANTS`) are read from it at
+import.  A new entry point is declared there, defined in csrc/ and called; nothing is
+added here.
 """
 import ctypes
 import os
+import re
 
 import torch  # noqa: F401  (must precede the dlopen below)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsdhip.so")
+HEADER_PATH = os.path.join(_HERE, "..", "include", "sdhip.h")
 
-F32, BF16 = 0, 1
-ERR_ARG, ERR_LAUNCH, ERR_UNSUPPORTED = -1, -2, -3   # include/sdhip.h
-ACT_HSWISH, ACT_HSIGMOID = 5, 6                      # SDHIP_ACT_* of include/sdhip.h (MobileNetV3's hard activations)
 NREP = int(os.environ.get("SDHIP_TUNE_NREP", "32"))   # statistics replicas the kernels spread their atomics over (env: tuning only)
 
 
@@ -24,122 +28,65 @@ class SdhipError(RuntimeError):
     pass
 
 
+_ARG_TYPES = {"*": ctypes.c_void_p, "int": ctypes.c_int, "long": ctypes.c_long, "int64_t": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double}
+_RET_TYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "void": None, "const char*": ctypes.c_char_p}
+
+
+def parse_header(text):
+    """(signatures, constants) of the text of include/sdhip.h: {name: (restype, [argtypes])} of every
+    `<ret> sdhip_<name>(<params>);` and {name: value} of every `#define SDHIP_<NAME> <integer>`.  A parameter is mapped by
+    its type alone (any pointer is a c_void_p); a type this does not know raises — ctypes' silent `int` is never assumed."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    consts = {n: int(v) for n, v in re.findall(r"^[ \t]*#define[ \t]+(SDHIP_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, flags=re.M)}
+    sigs = {}
+    for ret, name, params in re.findall(r"^([\w \t*]+?)\s*\b(sdhip_\w+)\s*\(([^()]*)\)\s*;", text, flags=re.M):
+        ret = re.sub(r"\s*\*\s*", "*", " ".join(ret.split()))
+        if ret not in _RET_TYPES:
+            raise SdhipError("sdhip.h: %s has return type '%s', which the binding cannot classify" % (name, ret))
+        args = []
+        for par in ([] if params.strip() == "void" else params.split(",")):
+            ctype = "*" if "*" in par else " ".join(w for w in par.split()[:-1] if w != "const")
+            if ctype not in _ARG_TYPES:
+                raise SdhipError("sdhip.h: %s has parameter '%s', which the binding cannot classify" % (name, " ".join(par.split())))
+            args.append(_ARG_TYPES[ctype])
+        sigs[name] = (_RET_TYPES[ret], args)
+    return sigs, consts
+
+
 if not os.path.exists(LIB_PATH):
     raise ImportError(
         "libsdhip.so not found at %s — run `python -c 'import __graft_entry__ as g; g.build()'` "
         "(hipcc, gfx950). This package has no fallback path." % LIB_PATH)
+if not os.path.exists(HEADER_PATH):
+    raise ImportError(
+        "sdhip.h not found at %s — the binding reads every signature and constant of libsdhip.so from it. "
+        "This package has no fallback path." % HEADER_PATH)
 
 _lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
 
-_p, _i, _f, _d, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_long
-_lib.sdhip_last_error.restype = ctypes.c_char_p
-_lib.sdhip_abi_version.restype = _i
-
-# name -> argtypes; every entry of include/sdhip.h is listed here (tests/test_abi.py checks).
-SIGNATURES = {
-    "sdhip_corr_fwd": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_corr_bwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_conv_pack_weights": [_p, _p, _i, _i, _i, _l, _l, _i, _i, _p],
-    "sdhip_conv_unpack_wgrad": [_p, _p, _i, _i, _i, _l, _l, _i, _i, _i, _p],
-    "sdhip_conv2d_fwd": [_p, _p, _p, _p, _p, _p, _p] + [_i] * 27 + [_p],
-    "sdhip_conv2d_fwd_phase": [_p, _p, _p, _p, _i, _i] + [_i] * 16 + [_p],
-    "sdhip_conv2d_wgrad": [_p, _p, _p, _p, _p, _p] + [_i] * 24 + [_p],
-    "sdhip_conv2d_wgrad_group": [_p, _i, _i, _i, _p],
-    "sdhip_conv1x1_cat_fwd": [_p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_conv_pack_batch": [_p, _i, _i, _p],
-    "sdhip_conv_unpack_batch": [_p, _i, _i, _p],
-    "sdhip_rowpool_max_fwd": [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_rowpool_max_bwd": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_mul_rows_fwd": [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_mul_rows_bwd": [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_dropout_channels": [_p, _i, _p, _i, _p, _l, _i, _i, _i, _f, _i, _p],
-    "sdhip_channel_stats": [_p, _i, _p, _i, _i, _l, _i, _i, _i, _i, _p],
-    "sdhip_stats_replica_sum": [_p, _p, _i, _i, _i, _i, _i, _p],
-    "sdhip_bn_fold_finalize": [_p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _d, _f, _f, _p],
-    "sdhip_bn_finalize": [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _d, _f, _f, _p],
-    "sdhip_stats_fix_fin": [_p, _i, _p, _i, _p, _i, _l, _p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i, _f, _i, _i, _d, _i, _p],
-    "sdhip_bn_finalize_bwd": [_p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _d, _i, _p],
-    "sdhip_affine_act": [_p, _i, _p, _i, _p, _i, _p, _p, _l, _i, _i, _i, _i, _p],
-    "sdhip_affine_act_bwd": [_p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _i, _l, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_maxpool3s2_fwd": [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p],
-    "sdhip_maxpool3s2_bwd": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_avgpool_fwd": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_avgpool_bwd": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_resize_fwd": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _p],
-    "sdhip_resize_bwd": [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _p],
-    "sdhip_mul_bcast_fwd": [_p, _i, _p, _i, _p, _i, _l, _i, _i, _p],
-    "sdhip_mul_bcast_bwd": [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _l, _i, _i, _p],
-    "sdhip_adam_step": [_p, _p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _p],
-    "sdhip_ce_loss": [_p, _i, _p, _i, _p, _i, _p, _l, _i, _f, _i, _p],
-    "sdhip_dropout": [_p, _p, _p, _l, _l, _f, _i, _p],
-    "sdhip_lovasz_softmax": [_p, _i, _p, _i, _p, _i, _p, _l, _i, _f, _p, _l, _i, _i, _p],
-    "sdhip_stuff": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_cost_volume_fwd": [_p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_cost_volume_bwd": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_softargmin_fwd": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_softargmin_bwd": [_p, _p, _p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_log_softmax_fwd": [_p, _i, _p, _i, _l, _i, _i, _p],
-    "sdhip_log_softmax_bwd": [_p, _i, _p, _i, _p, _i, _l, _i, _i, _p],
-    "sdhip_l1_loss": [_p, _p, _p, _p, _l, _f, _i, _i, _p],
-    "sdhip_stats_fix": [_p, _i, _p, _i, _p, _i, _p, _i, _l, _i, _i, _i, _p],
-    "sdhip_bn_bwd_apply": [_p, _i, _p, _i, _p, _i, _p, _p, _p, _i, _l, _i, _i, _i, _i, _p],
-    "sdhip_affine_act_bn": [_p, _i, _p, _i, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _l, _i, _i, _d, _f, _f, _i, _i, _p],
-    "sdhip_step_metrics": [_p, _i, _p, _i, _i, _p, _p, _p, _p, _i, _i, _i, _l, _i, _f, _i, _i, _p],
-    "sdhip_double_left_sample": [_p, _p, _i, _p, _i, _i, _p, _i, _i, _i, _p],
-    "sdhip_prepare_sample": [_p, _p, _l, _i, _p, _l, _i, _i, _i, _i, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _p, _p,
-                             _p, _p, _i, _p, _i, _i, _p, _i, _p],
-    "sdhip_flip_sample": [_p, _p, _i, _p, _i, _i, _p, _i, _i, _p, _l, _i, _p],
-    "sdhip_bn_bwd_apply_fin": [_p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _f, _l, _i, _i, _d, _i, _i, _p],
-    "sdhip_bn_bwd_apply_fin_d": [_p, _i, _p, _i, _p, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _f, _l, _i, _i, _d, _i, _i, _p],
-    "sdhip_conv2d_fwd_bnpro": [_p, _p, _p, _p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _d, _f, _f] + [_i] * 15 + [_p],
-    "sdhip_conv2d_fwd_add": [_p, _p, _p, _p, _i] + [_i] * 14 + [_p],
-    "sdhip_conv2d_fwd_bnbwd": [_p, _p, _p, _p, _i, _i, _p, _i, _p, _p, _p, _i] + [_i] * 17 + [_p],
-    "sdhip_mt_seg_fwd": [_p, _i, _p, _p, _p, _p, _p, _p, _l, _i, _i, _f, _i, _p],
-    "sdhip_mt_seg_bwd": [_p, _i, _p, _p, _p, _p, _l, _p, _f, _p, _i, _p, _l, _i, _i, _i, _p],
-    "sdhip_mt_l1_fwd": [_p, _i, _p, _p, _p, _p, _p, _l, _f, _i, _p],
-    "sdhip_mt_l1_bwd": [_p, _i, _p, _p, _p, _l, _p, _f, _p, _i, _p, _l, _i, _p],
-    "sdhip_dw_conv_fwd": [_p, _i, _p, _p, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_dw_pool_parts": [_i] * 6,
-    "sdhip_dw_wgrad_parts": [_i] * 6,
-    "sdhip_dw_conv_dgrad": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_dw_conv_wgrad": [_p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_se_fwd": [_p, _i, _f, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
-    "sdhip_se_bwd": [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _i, _i, _p],
-    "sdhip_se_scale_bwd": [_p, _i, _p, _i, _p, _i, _p, _p, _l, _i, _i, _i, _i, _p],
-    "sdhip_warp_blend_fwd": [_p, _i, _p, _i, _p, _i, _f, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
-    "sdhip_warp_blend_bwd": [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _f, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _i,
-                             _i, _i, _i, _i, _i, _p],
-    "sdhip_seg_terms_workspace_bytes": [_i, _l, _i],
-    "sdhip_seg_sums": [_p, _i, _p, _i, _i, _l, _i, _p, _l, _i, _p],
-    "sdhip_seg_finish": [_p, _l, _p, _p, _i, _l, _i, _f, _i, _p],
-    "sdhip_seg_terms_bwd": [_p, _i, _p, _i, _p, _i, _p, _l, _i, _l, _i, _i, _p],
-}
-_lib.sdhip_lovasz_workspace_bytes.argtypes = [_l, _i]
-_lib.sdhip_lovasz_workspace_bytes.restype = _l
-_lib.sdhip_flip_sample_workspace_bytes.argtypes = [_i, _i, _i]
-_lib.sdhip_flip_sample_workspace_bytes.restype = _l
-_lib.sdhip_softargmin_bwd_workspace_floats.argtypes = [_i] * 7
-_lib.sdhip_softargmin_bwd_workspace_floats.restype = _l
-_lib.sdhip_conv_packed_elems.argtypes = [_i, _i, _i, _i]
-_lib.sdhip_conv_packed_elems.restype = _l
-for _name, _args in SIGNATURES.items():
+with open(HEADER_PATH) as _f:
+    _SIGS, CONSTANTS = parse_header(_f.read())
+SIGNATURES = {_name: _args for _name, (_ret, _args) in _SIGS.items()}    # name -> argtypes of every declared entry point
+for _name, (_ret, _args) in _SIGS.items():
     _fn = getattr(_lib, _name)
     _fn.argtypes = _args
-    _fn.restype = _i
+    _fn.restype = _ret
+
+F32, BF16 = CONSTANTS["SDHIP_F32"], CONSTANTS["SDHIP_BF16"]
+ERR_ARG, ERR_LAUNCH, ERR_UNSUPPORTED = CONSTANTS["SDHIP_ERR_ARG"], CONSTANTS["SDHIP_ERR_LAUNCH"], CONSTANTS["SDHIP_ERR_UNSUPPORTED"]
+ACT_HSWISH, ACT_HSIGMOID = CONSTANTS["SDHIP_ACT_HSWISH"], CONSTANTS["SDHIP_ACT_HSIGMOID"]    # MobileNetV3's hard activations
+SEG_TVERSKY, SEG_DICE, SEG_DICE_ENTROPY = CONSTANTS["SDHIP_SEG_TVERSKY"], CONSTANTS["SDHIP_SEG_DICE"], CONSTANTS["SDHIP_SEG_DICE_ENTROPY"]
 
 
 class WgradItem(ctypes.Structure):
-    """SdhipWgradItem of include/sdhip.h."""
-    _fields_ = [(n, _p) for n in ("x", "dy", "dw_packed", "dbias", "in_scale", "in_shift")] + \
-               [(n, _i) for n in ("B", "H", "W", "Cin", "ldx", "Ho", "Wo", "Cout", "lddy", "kh", "kw", "stride", "dil", "pad_t", "pad_l",
-                                  "D", "Do", "kd", "sd", "pad_d", "in_relu", "groups")]
+    """SdhipWgradItem of include/sdhip.h: written out here (tests/test_abi.py holds the field order against the typedef)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("x", "dy", "dw_packed", "dbias", "in_scale", "in_shift")] + \
+               [(n, ctypes.c_int) for n in ("B", "H", "W", "Cin", "ldx", "Ho", "Wo", "Cout", "lddy", "kh", "kw", "stride", "dil", "pad_t",
+                                            "pad_l", "D", "Do", "kd", "sd", "pad_d", "in_relu", "groups")]
 
 
 def lovasz_workspace_bytes(npix, C):
     return _lib.sdhip_lovasz_workspace_bytes(npix, C)
-
-
-SEG_TVERSKY, SEG_DICE, SEG_DICE_ENTROPY = 1, 2, 4    # SDHIP_SEG_* of include/sdhip.h
 
 
 def seg_terms_workspace_bytes(B, hw, C):
@@ -170,18 +117,9 @@ def packed_elems(M, K, T, dt):
     return _lib.sdhip_conv_packed_elems(M, K, T, dt)
 
 
-_lib.sdhip_diag_reload.restype = None
-_lib.sdhip_abort_capture.argtypes = [_p]
-_lib.sdhip_abort_capture.restype = _i
-
-
-_lib.sdhip_graph_node_counts.argtypes = [_p, ctypes.POINTER(_i)]
-_lib.sdhip_graph_node_counts.restype = _i
-
-
 def graph_node_counts(graph):
     """{kernel, memset, memcpy, other, total} of a torch.cuda.CUDAGraph created with keep_graph=True."""
-    c = (_i * 4)()
+    c = (ctypes.c_int * 4)()
     n = _lib.sdhip_graph_node_counts(ctypes.c_void_p(graph.raw_cuda_graph()), c)
     if n < 0:
         raise SdhipError("sdhip_graph_node_counts failed: %s" % _lib.sdhip_last_error().decode())
@@ -232,6 +170,8 @@ def abi_version():
 
 def call(name, *args, unsupported_ok=False):
     """Invoke a C entry point; raise SdhipError with the library's message on failure."""
+    if name not in SIGNATURES:
+        raise SdhipError("%s is not declared in include/sdhip.h" % name)
     rc = getattr(_lib, name)(*args)
     if rc != 0 and not (unsupported_ok and rc == ERR_UNSUPPORTED):
         raise SdhipError("%s failed (%d): %s" % (name, rc, _lib.sdhip_last_error().decode()))

@@ -23,9 +23,10 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream_ptr
 
-SEG_THRESHOLD, SEG_ID_PLUS_ONE, SEG_LUT = 0, 1, 2
-DEPTH_PFM, DEPTH_U16 = 0, 1
-ACTIVATIONS = {"linear": 0, "sigmoid": 1, "tanh": 2}
+_C = _lib.CONSTANTS      # the mode codes of sdhip_prepare_sample
+SEG_THRESHOLD, SEG_ID_PLUS_ONE, SEG_LUT = _C["SDHIP_SEG_THRESHOLD"], _C["SDHIP_SEG_ID_PLUS_ONE"], _C["SDHIP_SEG_LUT"]
+DEPTH_PFM, DEPTH_U16 = _C["SDHIP_DEPTH_PFM"], _C["SDHIP_DEPTH_U16"]
+ACTIVATIONS = {"linear": _C["SDHIP_ACT_LINEAR"], "sigmoid": _C["SDHIP_ACT_SIGMOID"], "tanh": _C["SDHIP_ACT_TANH"]}
 
 # id -> trainId of the public Cityscapes label table (the `id2label[i].trainId` that util/utilCityscape.py:173-186 looks
 # up); ids 0..33, everything else is "ignore" (255).  tests/test_data.py checks it against the reference's table.

@@ -20,7 +20,7 @@ from . import _lib
 from ._lib import call, dtype_code, ptr, stream_ptr
 from .ops import _require_gpu, nhwc_view
 
-N_COUNTS, N_SUMS, SUM_STRIDE = 10, 4, 32      # SDHIP_METRIC_COUNTS / _SUMS / _SUM_STRIDE of include/sdhip.h
+N_COUNTS, N_SUMS, SUM_STRIDE = (_lib.CONSTANTS[n] for n in ("SDHIP_METRIC_COUNTS", "SDHIP_METRIC_SUMS", "SDHIP_METRIC_SUM_STRIDE"))
 NREP = 32                                    # replicas the workgroups spread their closing atomics over
 
 
