@@ -361,6 +361,18 @@ int sdhip_mul_bcast_bwd(const void* g, int ldg, const void* a, int lda, const vo
 int sdhip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* beta_pow,
                     long n, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                     void* stream);
+/* SGD with momentum over ONE flat f32 buffer (torch.optim.SGD semantics with dampening 0 and no Nesterov,
+ * torch_implementation.py:715-716: lr 0.005, momentum 0.9, weight_decay 0.0001):
+ *   d = g*grad_scale + weight_decay*p;  buf = momentum*buf + d;  p -= (*lr)*buf   (a zero buf gives torch's first step).
+ * lr points to one f32 in DEVICE memory that the kernel reads at every launch: a replayed hipGraph steps with whatever
+ * the host wrote there last, which is how adjust_learning_rate (torch_implementation.py:352-353,599-608) reaches a
+ * captured step.  live: NULL, or a DEVICE table of n_live rows (begin, end) in elements - sorted, disjoint,
+ * 0 <= begin < end <= n, every bound a multiple of 4.  Elements outside all rows are neither read-modified nor written,
+ * in params and in momentum_buf (torch skips a parameter without a gradient; weight decay must not reach it).  The table
+ * is the caller's responsibility: only pointers, 16-byte alignment of the three buffers, n > 0 and n_live >= 0 are checked. */
+int sdhip_sgd_step(float* params, const float* grads, float* momentum_buf, const float* lr, long n,
+                   float momentum, float weight_decay, float grad_scale,
+                   const long* live, long n_live, void* stream);
 /* loss += weight * mean_p sum_c -target[p,c]*log_softmax(logits[p,:])_c  and (optionally) its gradient w.r.t. the
  * logits: categoricalCrossEntropy(F.log_softmax(y,1), gt) of util/utilTorchLoss.py:373-378.  target is f32. */
 int sdhip_ce_loss(const void* logits, int ldy, const float* target, int ldt, void* grad, int ldg, double* loss,

@@ -4,10 +4,11 @@ The reference writes `{'epoch', 'state_dict', 'optimizer', 'train_cm', 'test_cm'
 'IoU_history_val', 'disp_history_val', 'loss_history_val', 'IoU_history_train', 'disp_history_train',
 'loss_history_train'[, 'amp']}` with `torch.save` (torch_implementation.py:915-934) and reads it back in
 `load_checkpoint_and_params` (util/utilTorch_loadweight.py:6-115).  `state_dict` is the DistributedDataParallel
-wrapper's, so every key carries a `module.` prefix; `optimizer` is `torch.optim.Adam.state_dict()`, whose per-parameter
-state is indexed by the position of the parameter in `net.parameters()`.
+wrapper's, so every key carries a `module.` prefix; `optimizer` is `torch.optim.Adam.state_dict()` (or, with `-optimType
+sgd`, `torch.optim.SGD.state_dict()`), whose per-parameter state is indexed by the position of the parameter in
+`net.parameters()`.
 
-Here the parameters live in ONE flat f32 buffer with flat Adam moments beside it (train.TrainStep), so this module
+Here the parameters live in ONE flat f32 buffer with flat Adam moments (or the SGD momentum buffer) beside it (train.TrainStep), so this module
 maps between the two layouts.  The networks of this package register their parameters in the reference's order
 (tests/test_checkpoint.py checks that against a key list captured from the reference), which makes the index mapping
 the identity.  Files written here load in the reference and vice versa.
@@ -90,11 +91,20 @@ def _invalidate():
 
 def optimizer_state_dict(step):
     """`torch.optim.Adam.state_dict()` of a TrainStep-like object (attributes model, exp_avg, exp_avg_sq, steps_done, lr,
-    betas, eps): the flat moments are cut back into per-parameter tensors."""
+    betas, eps): the flat moments are cut back into per-parameter tensors.  A step whose `optimizer` is 'sgd' (attributes
+    model, momentum_buf, steps_done, lr, momentum, weight_decay) gives `torch.optim.SGD.state_dict()` instead."""
     state = {}
     slices = _param_slices(step.model)
     t = float(step.steps_done)
     idle = set(getattr(step, "grad_free", None) or ())
+    if getattr(step, "optimizer", "adam") == "sgd":
+        for i, (_, p, off, n) in enumerate(slices):
+            if t == 0 or i in idle:
+                continue        # as below: torch.optim.SGD has no momentum_buffer before a parameter's first gradient
+            state[i] = {"momentum_buffer": step.momentum_buf[off:off + n].view(p.shape).clone()}
+        group = {"lr": step.lr, "momentum": step.momentum, "dampening": 0, "weight_decay": step.weight_decay, "nesterov": False,
+                 "maximize": False, "foreach": None, "differentiable": False, "fused": None, "params": list(range(len(slices)))}
+        return {"state": state, "param_groups": [group]}
     for i, (_, p, off, n) in enumerate(slices):
         if t == 0 or i in idle:
             continue            # torch creates the per-parameter state lazily at the first step with a gradient
@@ -107,13 +117,25 @@ def optimizer_state_dict(step):
 
 
 def load_optimizer_state(step, opt_state):
-    """Inverse of optimizer_state_dict: fills the flat moments, the step count and beta1^t / beta2^t."""
+    """Inverse of optimizer_state_dict: fills the flat moments, the step count and beta1^t / beta2^t.
+
+    The kind of the state is read from its param group (`momentum`: torch.optim.SGD, `betas`: torch.optim.Adam) and has to be
+    the step's own.  An SGD state fills `momentum_buf` (zeros where a parameter has no entry, or a None buffer) and sets the
+    rate (through `set_lr` where the step has it, so that the device copy follows), momentum and weight decay.
+    torch.optim.SGD's state carries no step count, so `steps_done` is left as it is.  Nesterov, dampening and maximize are
+    not implemented and are refused."""
     slices = _param_slices(step.model)
     groups = opt_state["param_groups"]
     order = [i for g in groups for i in g["params"]]
     if len(order) != len(slices):
         raise ValueError("optimizer state holds %d parameters, the model has %d" % (len(order), len(slices)))
     g0 = groups[0]
+    kind = "sgd" if "momentum" in g0 else ("adam" if "betas" in g0 else None)
+    own = getattr(step, "optimizer", "adam")
+    if kind != own:
+        raise ValueError("optimizer state is %s, the step runs %s" % ({"sgd": "torch.optim.SGD's", "adam": "torch.optim.Adam's"}.get(kind, "of an unknown optimizer"), own))
+    if kind == "sgd":
+        return _load_sgd_state(step, opt_state, slices, order)
     step.lr, step.betas, step.eps = float(g0["lr"]), tuple(g0["betas"]), float(g0["eps"])
     t = 0.0
     with torch.no_grad():
@@ -132,6 +154,33 @@ def load_optimizer_state(step, opt_state):
             t = max(t, float(st["step"]))
         step.steps_done = int(t)
         step.beta_pow.copy_(torch.tensor([step.betas[0] ** t, step.betas[1] ** t], dtype=torch.float64).to(step.beta_pow.dtype))
+
+
+def _load_sgd_state(step, opt_state, slices, order):
+    for g in opt_state["param_groups"]:
+        if g.get("nesterov") or g.get("dampening", 0) != 0 or g.get("maximize"):
+            raise ValueError("SGD state with nesterov / dampening / maximize: the fused step implements none of them")
+    g0 = opt_state["param_groups"][0]
+    momentum, weight_decay = float(g0["momentum"]), float(g0.get("weight_decay", 0))
+    if getattr(step, "graph", None) is not None and (momentum, weight_decay) != (step.momentum, step.weight_decay):
+        raise ValueError("momentum and weight decay are part of the captured hipGraph: load the state before the capture")
+    with torch.no_grad():
+        step.momentum_buf.zero_()
+        for pos, idx in enumerate(order):
+            st = opt_state["state"].get(idx)
+            buf = None if st is None else st.get("momentum_buffer")
+            if buf is None:
+                continue
+            _, p, off, n = slices[pos]
+            if tuple(buf.shape) != tuple(p.shape):
+                raise ValueError("optimizer state %d has shape %s, parameter %s has %s" %
+                                 (idx, tuple(buf.shape), slices[pos][0], tuple(p.shape)))
+            step.momentum_buf[off:off + n].copy_(buf.reshape(-1))
+    step.momentum, step.weight_decay = momentum, weight_decay
+    if hasattr(step, "set_lr"):
+        step.set_lr(float(g0["lr"]))
+    else:
+        step.lr = float(g0["lr"])
 
 
 def make_state(step, epoch, histories=None, best_metric=(1, 0), train_cm=None, test_cm=None, ddp_prefix=True):

@@ -1,7 +1,8 @@
-// Training-step tail for gfx950: fused Adam over one flat parameter buffer, and the per-pixel
+// Training-step tail for gfx950: fused Adam or SGD with momentum over one flat parameter buffer, and the per-pixel
 // losses of the timed step (categorical cross-entropy on log-softmax, L1), forward + gradient in one pass.
 //
 // Replaces torch.optim.Adam(lr=0.0015, eps=1e-7) (torch_implementation.py:718-724),
+// torch.optim.SGD(lr=0.005, momentum=0.9, weight_decay=0.0001) (torch_implementation.py:715-716),
 // categoricalCrossEntropy (util/utilTorchLoss.py:373-378, fed by F.log_softmax at
 // losses/multiLosses.py:42) and nn.L1Loss (losses/multiLosses.py:141).
 #include "sdhip_common.h"
@@ -37,6 +38,47 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         m[j] = b1 * m[j] + (1.f - b1) * gr;
         v[j] = b2 * v[j] + (1.f - b2) * gr * gr;
         p[j] -= step * m[j] / (sqrtf(v[j]) * ibc2 + eps);
+      }
+    }
+  }
+}
+
+// Is the 16-byte vector that starts at element i inside a row of the live table?  Rows (begin, end) are sorted and disjoint
+// and every bound is a multiple of 4, so a vector lies wholly inside one row or wholly outside all of them: find the first
+// row that ends after i, then ask whether it has begun.  The table is a few rows (one per run of parameters the loss reaches),
+// read by every lane: it stays in the cache.
+__device__ __forceinline__ bool sgd_live(const long* __restrict__ live, long n_live, long i) {
+  long lo = 0, hi = n_live;
+  while (lo < hi) {
+    const long mid = (lo + hi) >> 1;
+    if (live[2 * mid + 1] > i) hi = mid; else lo = mid + 1;
+  }
+  return lo < n_live && live[2 * lo] <= i;
+}
+
+// torch.optim.SGD with dampening 0, no Nesterov: d = g*gscale + wd*p; buf = mom*buf + d; p -= lr*buf (a zero buf gives torch's
+// first step, buf = d).  The rate is read from device memory at every launch, so a replayed hipGraph sees what the host wrote
+// there last.  TABLE: elements outside every row of `live` are neither read-modified nor written.
+template <bool TABLE>
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                  const float* __restrict__ lr_ptr, long n, float mom, float wd, float gscale,
+                                                  const long* __restrict__ live, long n_live) {
+  const float lr = lr_ptr[0];
+  for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (long)gridDim.x * 1024) {
+    if (TABLE && !sgd_live(live, n_live, i)) continue;
+    if (i + 3 < n) {
+      f32x4 pv = *reinterpret_cast<f32x4*>(p + i), gv = *reinterpret_cast<const f32x4*>(g + i);
+      f32x4 mv = *reinterpret_cast<f32x4*>(m + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        mv[e] = mom * mv[e] + (gv[e] * gscale + wd * pv[e]);
+        pv[e] -= lr * mv[e];
+      }
+      *reinterpret_cast<f32x4*>(p + i) = pv; *reinterpret_cast<f32x4*>(m + i) = mv;
+    } else {    // n % 4 elements; no row reaches them (a row ends at a multiple of 4 <= n), so only the NULL table gets here
+      for (long j = i; j < n; ++j) {
+        m[j] = mom * m[j] + (g[j] * gscale + wd * p[j]);
+        p[j] -= lr * m[j];
       }
     }
   }
@@ -165,6 +207,24 @@ extern "C" int sdhip_adam_step(float* params, const float* grads, float* exp_avg
   hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, s, beta_pow, beta1, beta2);
   hipLaunchKernelGGL(adam_kernel, grid_for((n + 3) / 4), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, n, lr, beta1,
                      beta2, eps, weight_decay, grad_scale, beta_pow);
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}
+
+extern "C" int sdhip_sgd_step(float* params, const float* grads, float* momentum_buf, const float* lr, long n, float momentum,
+                              float weight_decay, float grad_scale, const long* live, long n_live, void* stream) {
+  SDHIP_CHECK_ARG(params && grads && momentum_buf && lr, "sgd_step: null pointer");
+  SDHIP_CHECK_ARG(n > 0 && n_live >= 0, "sgd_step: bad sizes (n %ld, n_live %ld)", n, n_live);
+  SDHIP_CHECK_ARG((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)momentum_buf) & 15) == 0,
+                  "sgd_step: buffers must be 16-byte aligned");
+  SDHIP_CHECK_ARG(((uintptr_t)lr & 3) == 0 && ((uintptr_t)live & 7) == 0, "sgd_step: misaligned learning rate or live table");
+  hipStream_t s = (hipStream_t)stream;
+  if (live)
+    hipLaunchKernelGGL(sgd_kernel<true>, grid_for((n + 3) / 4), dim3(256), 0, s, params, grads, momentum_buf, lr, n, momentum,
+                       weight_decay, grad_scale, live, n_live);
+  else
+    hipLaunchKernelGGL(sgd_kernel<false>, grid_for((n + 3) / 4), dim3(256), 0, s, params, grads, momentum_buf, lr, n, momentum,
+                       weight_decay, grad_scale, live, n_live);
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }

@@ -1,15 +1,48 @@
-"""Training step of the hot path: forward + loss + backward + Adam, optionally captured as ONE hipGraph.
+"""Training step of the hot path: forward + loss + backward + optimizer, optionally captured as ONE hipGraph.
 
 Counterpart of train_model's inner loop (torch_implementation.py:350-397) without its host-side metric /
-JPEG work: model(left, right) -> CE(seg1) + CE(seg2) + Lovasz(seg2) + L1(disp) [+ CE(seg3)] -> backward -> Adam.
-Parameters live in one flat f32 buffer (one fused Adam launch, one gradient all-reduce over RCCL when
+JPEG work: model(left, right) -> CE(seg1) + CE(seg2) + Lovasz(seg2) + L1(disp) [+ CE(seg3)] -> backward -> Adam or SGD.
+Parameters live in one flat f32 buffer (one fused optimizer launch, one gradient all-reduce over RCCL when
 data-parallel); activations run in `dtype` (bf16 MFMA path or exact f32 path).
+
+The optimizer is the reference's `-optimType` (torch_implementation.py:715-724): Adam (lr 0.0015, eps 1e-7), or SGD with
+momentum (lr 0.005, momentum 0.9, weight decay 1e-4).  Adam's rate is a by-value kernel argument, fixed once the step is a
+hipGraph.  SGD's rate lives in device memory (`lr_dev`), which the kernel reads at every launch: `set_lr` between replays is
+what the reference's per-iteration `adjust_learning_rate` (`poly_lr` here) needs.  `flush` closes an accumulation cycle
+early, as the reference does at the last batch of an epoch (torch_implementation.py:390).
 """
 import os
 import torch
 
 from . import _lib, multitask, ops, parallel
 from ._lib import call, ptr, stream_ptr
+
+
+def poly_lr(epoch, itr, total_iter, base_lr=0.005, epoch_total=2400):
+    """The rate adjust_learning_rate sets before every iteration of an SGD run (torch_implementation.py:352-353,599-608):
+    base_lr * (1 - T/N) with T iterations done of N, held at its last value once `epoch_total` epochs have passed.  Host
+    arithmetic in double precision, like the reference's; a loop calls `ts.set_lr(poly_lr(epoch, i, len(loader)))`."""
+    T = epoch * total_iter + itr
+    N = epoch_total * total_iter
+    if epoch >= epoch_total:
+        T = N - 1
+    return base_lr * (1 - T / float(N))
+
+
+def live_ranges(model, idle):
+    """Rows (begin, end) of the flat buffer that cover every parameter whose position in `model.parameters()` is not in
+    `idle`: the complement of the idle parameters' slices, adjacent slices merged.  Every bound is a multiple of 4, as the
+    slices of flatten_parameters are (the `live` table of sdhip_sgd_step)."""
+    rows, off, idle = [], 0, set(idle)
+    for i, p in enumerate(model.parameters()):
+        end = off + ((p.numel() + 3) // 4) * 4
+        if i not in idle:
+            if rows and rows[-1][1] == off:
+                rows[-1][1] = end
+            else:
+                rows.append([off, end])
+        off = end
+    return rows
 
 
 def flatten_parameters(model):
@@ -31,10 +64,24 @@ def flatten_parameters(model):
 
 
 class TrainStep:
-    def __init__(self, model, dtype=torch.bfloat16, lr=0.0015, betas=(0.9, 0.999), eps=1e-7, use_lovasz=True,
+    def __init__(self, model, dtype=torch.bfloat16, lr=None, betas=(0.9, 0.999), eps=1e-7, use_lovasz=True,
                  use_graph=True, world_size=1, process_group=None, use_side_stream=None, loss_fn=None, metrics=None, accumulate=1,
-                 loss=None, class_weights=None):
+                 optimizer='adam', momentum=0.9, weight_decay=None, loss=None, class_weights=None):
         self.model, self.dtype, self.use_lovasz = model, dtype, use_lovasz
+        # `-optimType` (torch_implementation.py:715-724): the defaults of lr and weight_decay are those of the reference's optimizer
+        if optimizer not in ("adam", "sgd"):
+            raise _lib.SdhipError("TrainStep: optimizer %r is not one of 'adam', 'sgd'" % (optimizer,))
+        self.optimizer = optimizer
+        sgd = optimizer == "sgd"
+        if lr is None:
+            lr = 0.005 if sgd else 0.0015
+        if weight_decay is None:
+            weight_decay = 1e-4 if sgd else 0
+        if not sgd and weight_decay != 0:
+            # the fused Adam runs over the whole flat buffer: it would decay the parameters that never receive a gradient, which
+            # torch.optim.Adam skips (sdhip_sgd_step has the `live` table for that; sdhip_adam_step has not)
+            raise _lib.SdhipError("TrainStep: weight_decay is only supported with optimizer='sgd'")
+        self.momentum, self.weight_decay = momentum, weight_decay
         # `-loss` list of the second segmentation head and the `-segWeight 1` class table (ops.train_loss); both None: the
         # default step.  The list is checked and the table uploaded here, once, so that the step captures into the hipGraph
         if loss_fn is not None and (loss is not None or class_weights is not None):
@@ -58,9 +105,19 @@ class TrainStep:
         self.world_size, self.pg = world_size, process_group
         parallel.configure(process_group, world_size)     # sync-BN statistics exchange + gradient all-reduce
         self.flat_p, self.flat_g = flatten_parameters(model)
-        self.exp_avg = torch.zeros_like(self.flat_p)
-        self.exp_avg_sq = torch.zeros_like(self.flat_p)
-        self.beta_pow = torch.ones(2, dtype=torch.float32, device=self.flat_p.device)
+        self.exp_avg = self.exp_avg_sq = self.beta_pow = None
+        self.momentum_buf = self.lr_dev = None
+        if sgd:
+            self.momentum_buf = torch.zeros_like(self.flat_p)
+            # the rate the kernel reads at every launch (set_lr): a captured step follows a schedule
+            self.lr_dev = torch.full((1,), lr, dtype=torch.float32, device=self.flat_p.device)
+        else:
+            self.exp_avg = torch.zeros_like(self.flat_p)
+            self.exp_avg_sq = torch.zeros_like(self.flat_p)
+            self.beta_pow = torch.ones(2, dtype=torch.float32, device=self.flat_p.device)
+        # SGD with weight decay: device table of the flat buffer's rows that belong to parameters the loss reaches, built
+        # before the first optimizer step when there are others (grad_free below); None: every element is stepped
+        self.live = None
         self.use_graph = use_graph
         if use_graph and world_size > 1 and _backend_of(process_group) != "nccl":
             # host-staged collectives (gloo: rehearsals and tests on fewer GPUs than ranks) cannot be part of a hipGraph
@@ -92,7 +149,8 @@ class TrainStep:
         # 2's unused decoder; the warp networks' key-only members), found on the first step.  torch.optim.Adam keeps no
         # state for them (their .grad stays None), so a saved optimizer state omits them as well
         # (checkpoint.optimizer_state_dict); here their gradient slice stays 0, their moments stay 0 and the fused Adam
-        # leaves them bit-identical (update 0 / (0 + eps))
+        # leaves them bit-identical (update 0 / (0 + eps)).  SGD with weight decay would move them (d = wd * p), so it looks
+        # for them in every model and steps only the rows of the others (self.live)
         self.grad_free = None
         # dropout streams differ per rank (the reference's ranks draw from independently seeded generators) and advance
         # once per step on the device, so that graph replays see new masks (ops.rng_seed_tensor)
@@ -149,7 +207,7 @@ class TrainStep:
             # (torch_implementation.py:157-158,298); Lovasz stays on outs[2], which the metrics score as well
             loss = ops.train_loss(outs[0], outs[1], outs[2], seg, disp, self.use_lovasz, seg3=outs[4] if three else None,
                                   loss=self.seg_loss, class_weights=self.class_weights)
-        if (mt or three) and self.grad_free is None:
+        if self.grad_free is None and (mt or three or (self.optimizer == "sgd" and self.weight_decay != 0)):
             self.grad_free = _unreached_parameters(self.model, loss)
         if self.metrics is not None and self.loss_fn is None:
             self.metrics.update(outs[2].detach(), seg, outs[1].detach(), disp)
@@ -161,10 +219,49 @@ class TrainStep:
         parallel.all_reduce_sum_(self.flat_g)   # one RCCL sum over xGMI per step; Adam divides by world_size
 
     def optimizer_step(self):
-        call("sdhip_adam_step", ptr(self.flat_p), ptr(self.flat_g), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(self.beta_pow),
-             self.flat_p.numel(), self.lr, self.betas[0], self.betas[1], self.eps, 0.0, 1.0 / (self.world_size * self.accumulate),
-             stream_ptr())
+        grad_scale = 1.0 / (self.world_size * self.accumulate)
+        if self.optimizer == "sgd":
+            if self.live is None and self.weight_decay != 0 and self.grad_free:
+                # once, on the first (eager) step: the table exists before any capture
+                if torch.cuda.is_current_stream_capturing():
+                    raise _lib.SdhipError("TrainStep: the live table of the SGD step cannot be built inside a capture")
+                self.live = torch.tensor(live_ranges(self.model, self.grad_free), dtype=torch.int64, device=self.flat_p.device)
+            live = self.live if self.weight_decay != 0 else None
+            call("sdhip_sgd_step", ptr(self.flat_p), ptr(self.flat_g), ptr(self.momentum_buf), ptr(self.lr_dev), self.flat_p.numel(),
+                 self.momentum, self.weight_decay, grad_scale, ptr(live), 0 if live is None else live.shape[0], stream_ptr())
+        else:
+            call("sdhip_adam_step", ptr(self.flat_p), ptr(self.flat_g), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(self.beta_pow),
+                 self.flat_p.numel(), self.lr, self.betas[0], self.betas[1], self.eps, 0.0, grad_scale, stream_ptr())
         ops.invalidate_packed_weights()
+
+    def set_lr(self, lr):
+        """Learning rate of the following steps.  SGD: also written to `lr_dev` on the current stream, so it reaches eager
+        steps and replays of a captured step alike - legal before and after the capture and between replays.  Adam's rate
+        is a by-value argument of its kernel, fixed in the hipGraph: after a capture this raises."""
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.SdhipError("TrainStep.set_lr: called while a stream is capturing")
+        if self.optimizer != "sgd" and self.graph is not None:
+            raise _lib.SdhipError("TrainStep.set_lr: Adam's learning rate is part of the captured hipGraph; use optimizer='sgd' "
+                                  "for a schedule, or set the rate before the capture")
+        self.lr = float(lr)
+        if self.optimizer == "sgd":
+            self.lr_dev.fill_(self.lr)
+
+    def flush(self):
+        """Close an open accumulation cycle now: all-reduce and step, eagerly, on what has accumulated - the reference also
+        steps at the last batch of an epoch (torch_implementation.py:390).  The scale stays 1 / (world_size * accumulate): the
+        reference divides every micro-loss by K whatever the length of the tail.  (The loss a call of TrainStep returns is
+        NOT divided by K; the reference logs loss / K.)  Returns True if a step was taken; the next call then opens a
+        cycle, eagerly or by replay.  False, and nothing done, if no cycle was open."""
+        if self._micro == 0:
+            return False
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.SdhipError("TrainStep.flush: called while a stream is capturing")
+        self.all_reduce()
+        self.optimizer_step()
+        self._micro = 0
+        self.steps_done += 1
+        return True
 
     def _phase(self):
         """(first, last) of the call about to run within its accumulation cycle; advances the cycle counter."""
