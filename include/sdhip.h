@@ -613,6 +613,25 @@ int sdhip_dw_conv_wgrad(const void* x, int ldx, const void* gy, int ldg, float* 
                         int B, int H, int W, int C, int k, int stride, int dtype, void* stream);
 /* Partial slots of sdhip_dw_conv_wgrad for this shape (< 0: unsupported).  Host only. */
 int sdhip_dw_wgrad_parts(int B, int H, int W, int C, int k, int stride);
+/* Dilated depthwise 3x3 of DeepLabV3+ / Xception-65 (models_deeplab_mod/common.py:24-50 SeparableConv2d):
+ * nn.Conv2d(C, C, 3, stride, padding=dil, dilation=dil, groups=C, bias=False), stride in {1, 2}, any dil >= 1, any H, W, C:
+ *   y[b,oh,ow,c] = sum_{kh,kw} w[c][kh*3+kw] * f(x[b, oh*stride + (kh-1)*dil, ow*stride + (kw-1)*dil, c]),
+ * f = relu when in_relu != 0 (relu_first: rectified in the load, x itself stays as it is), identity otherwise;
+ * Ho = (H-1)/stride + 1.  Taps outside the map are skipped, not loaded.  Layout, w, stats as sdhip_dw_conv_fwd; the channel
+ * tail is masked on the 16-byte path too (C need not be a multiple of the chunk; pad lanes are never read or written). */
+int sdhip_dw_dil_conv_fwd(const void* x, int ldx, const float* w, void* y, int ldy, double* stats, int sld, int nrep,
+                          int B, int H, int W, int C, int stride, int dil, int in_relu, int groups, int dtype, void* stream);
+/* Data gradient of sdhip_dw_dil_conv_fwd, gathered (no atomics); gx is overwritten.  x (optional): the forward's input when
+ * it ran with in_relu — the gradient is multiplied by [x > 0] in the same launch. */
+int sdhip_dw_dil_conv_dgrad(const void* gy, int ldg, const float* w, const void* x, int ldx, void* gx, int ldgx,
+                            int B, int H, int W, int C, int stride, int dil, int dtype, void* stream);
+/* Weight gradient of sdhip_dw_dil_conv_fwd, ADDED to dw (C, 1, 3, 3) f32; it sees relu(x) when in_relu != 0.  part: f32
+ * workspace of nparts * 9 * C floats (nparts = sdhip_dw_dil_wgrad_parts; no initialisation needed), folded in a fixed
+ * order as in sdhip_dw_conv_wgrad: deterministic. */
+int sdhip_dw_dil_conv_wgrad(const void* x, int ldx, const void* gy, int ldg, float* dw, float* part, int nparts,
+                            int B, int H, int W, int C, int stride, int dil, int in_relu, int dtype, void* stream);
+/* Partial slots of sdhip_dw_dil_conv_wgrad for this shape (< 0: unsupported).  Host only. */
+int sdhip_dw_dil_wgrad_parts(int B, int H, int W, int C, int stride);
 /* SELayer excitation (models/mobilenetv3.py:64-77): v[b,c] = (sum_p pool[b][p][c])*inv_hw*scale[g][c] + shift[g][c]
  * (pool: the pool_parts slots of sdhip_dw_conv_fwd, added in slot order; scale / shift:
  * the BatchNorm in front, g = b / (B/groups); NULL: identity), h = relu(w1 v + b1), a = w2 h + b2, s = h_sigmoid(a).

@@ -545,7 +545,323 @@ __global__ __launch_bounds__(256) void se_scale_bwd_kernel(const T* __restrict__
   }
 }
 
+// ------------------------------------------------------------------------------------------ dilated depthwise 3x3
+// SeparableConv2d of DeepLabV3+ / Xception-65 (models_deeplab_mod/common.py:24-50): nn.Conv2d(C, C, 3, stride, padding=d,
+// dilation=d, groups=C).  With a dilation the neighbouring outputs of a row share no source column, so a thread gathers the
+// nine taps of one output pixel for one 16-byte channel chunk, and walks up to DWD_MAX_PIX pixels so that the weight tile in
+// LDS is staged once for all of them; a tap outside the map costs a compare, no load (for the ASPP dilations 12 / 24 / 36
+// on a 33 x 65 map most taps are outside).  The nine-fold reuse of the source is left to
+// L2 / the Infinity Cache; that HBM then sees the source once is the design's assumption — no counter run has measured it.
+//   * the channel tail is masked: the last chunk of a channel count that is no multiple of the chunk (304, 412 in bf16) is
+//     loaded and stored element by element, so the vector path needs aligned pointers and strides only;
+//   * IN_RELU (relu_first of SeparableConv2d): the forward rectifies in the load; the data gradient multiplies by [x > 0]
+//     read at the pixel it writes; the weight gradient rectifies x in the load — the un-rectified x stays the saved tensor;
+//   * the data gradient is the same gather over gy: tap (kh, kw) of input pixel (ih, iw) reads output pixel
+//     ((ih - (kh-1) d) / s, (iw - (kw-1) d) / s) where that is integral and inside — no zero-stuffing, no atomics.
+constexpr int DWD_MAX_PIX = 16;   // pixels per thread of the forward / data gradient (the statistics add them in f32)
+
+template <typename T, bool VEC>
+__device__ __forceinline__ void dwd_load(const T* p, float* f, int n) {
+  constexpr int N = Unit<T, VEC>::N;
+  if (n >= N) { Unit<T, VEC>::load(p, f); return; }
+#pragma unroll
+  for (int e = 0; e < N; ++e) f[e] = e < n ? Elem<T>::ld(p + e) : 0.f;
+}
+
+template <typename T, bool VEC>
+__device__ __forceinline__ void dwd_store(T* p, const float* f, int n) {
+  constexpr int N = Unit<T, VEC>::N;
+  if (n >= N) { Unit<T, VEC>::store(p, f); return; }
+#pragma unroll
+  for (int e = 0; e < N; ++e)
+    if (e < n) Elem<T>::st(p + e, f[e]);
+}
+
+// source index of tap k (0..2) for output index o: forward o*S + (k-1)*D, backward (o - (k-1)*D) / S when integral; -1: none
+template <bool BWD>
+__device__ __forceinline__ int dwd_src(int o, int k, int S, int D, int n) {
+  int s;
+  if constexpr (BWD) {
+    const int t = o - (k - 1) * D;
+    if (t < 0 || (S == 2 && (t & 1))) return -1;
+    s = S == 2 ? t >> 1 : t;
+  } else {
+    s = o * S + (k - 1) * D;
+  }
+  return (s < 0 || s >= n) ? -1 : s;
+}
+
+// Forward (BWD = false: src = x, out = y) and data gradient (BWD = true: src = gy, out = gx, xm = x or NULL).
+// grid: (pixel blocks, channel-unit groups, images).
+template <typename T, bool VEC, bool BWD>
+__global__ __launch_bounds__(256) void dwd_conv_kernel(const T* __restrict__ src, int lds, const float* __restrict__ w,
+                                                       const T* __restrict__ xm, int ldm, T* __restrict__ out, int ldo,
+                                                       double* __restrict__ stats, int sld, int nrep, int SH, int SW, int OH, int OW,
+                                                       int C, int S, int D, int in_relu, int imgs_per_group, int pix, DwGeom dg) {
+  constexpr int N = Unit<T, VEC>::N;
+  constexpr int WL = 9 * 64 * N;
+  constexpr int RED = 2 * 256 * N;
+  __shared__ float lds_buf[WL > RED ? WL : RED];
+  const int nch = dg.tx * N;
+  const int cb0 = blockIdx.y * nch;
+  dw_stage_weights(w, lds_buf, cb0, nch, C, 9);
+  __syncthreads();
+  const int tx = threadIdx.x % dg.tx, ty = threadIdx.x / dg.tx;
+  const int u = blockIdx.y * dg.tx + tx;
+  const int b = blockIdx.z;
+  const int c0 = u * N;
+  const int nv = C - c0 < N ? C - c0 : N;
+  const T* sp = src + (long)b * SH * SW * lds + c0;
+  float s1[N], s2[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
+  // `pix` pixels per thread (rows of dg.ty pixels, consecutive in the image): the weight tile is staged once for all of them
+  for (int p = 0; p < pix; ++p) {
+    const int q = (blockIdx.x * pix + p) * dg.ty + ty;
+    if (!(ty < dg.ty && u < dg.units && q < OH * OW)) continue;
+    const int orow = q / OW, ocol = q - orow * OW;
+    float acc[N];
+#pragma unroll
+    for (int e = 0; e < N; ++e) acc[e] = 0.f;
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh) {
+      const int srow = dwd_src<BWD>(orow, kh, S, D, SH);
+      if (srow < 0) continue;
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw) {
+        const int scol = dwd_src<BWD>(ocol, kw, S, D, SW);
+        if (scol < 0) continue;
+        float v[N];
+        dwd_load<T, VEC>(sp + ((long)srow * SW + scol) * lds, v, nv);
+        const float* wt = lds_buf + (kh * 3 + kw) * nch + tx * N;
+#pragma unroll
+        for (int e = 0; e < N; ++e) {
+          const float a = (!BWD && in_relu) ? fmaxf(v[e], 0.f) : v[e];
+          acc[e] = fmaf(a, wt[e], acc[e]);
+        }
+      }
+    }
+    if (BWD && xm) {
+      float xv[N];
+      dwd_load<T, VEC>(xm + ((long)b * OH * OW + q) * ldm + c0, xv, nv);
+#pragma unroll
+      for (int e = 0; e < N; ++e) acc[e] = xv[e] > 0.f ? acc[e] : 0.f;
+    }
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+      acc[e] = Elem<T>::rnd(acc[e]);
+      s1[e] += acc[e];
+      s2[e] = fmaf(acc[e], acc[e], s2[e]);
+    }
+    dwd_store<T, VEC>(out + ((long)b * OH * OW + q) * ldo + c0, acc, nv);
+  }
+  if (BWD || !stats) return;   // uniform
+  __syncthreads();             // the weight tile is dead: its LDS takes the block reduction
+  float* r1 = lds_buf;
+  float* r2 = lds_buf + 256 * N;
+#pragma unroll
+  for (int e = 0; e < N; ++e) { r1[threadIdx.x * N + e] = s1[e]; r2[threadIdx.x * N + e] = s2[e]; }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nch; i += blockDim.x) {
+    const int c = cb0 + i;
+    if (c >= C) continue;
+    const int txi = i / N, e = i - txi * N;
+    float a = 0.f, q2 = 0.f;
+    for (int y = 0; y < dg.ty; ++y) {
+      a += r1[(y * dg.tx + txi) * N + e];
+      q2 += r2[(y * dg.tx + txi) * N + e];
+    }
+    const int g = b / imgs_per_group;
+    double* sp = stats + ((long)(blockIdx.x % nrep) * (gridDim.z / imgs_per_group) + g) * 2 * sld;
+    atomicAdd(sp + c, (double)a);
+    atomicAdd(sp + sld + c, (double)q2);
+  }
+}
+
+// Weight gradient: block (pixel blocks, channel-unit groups, kernel row kh); a thread walks output pixels of the whole batch
+// and accumulates the three taps of row kh for its N channels; LDS reduction over the pixel rows of the block, then
+// part[blockIdx.x][kh*3 + kw][c] (every element written by exactly one block; dw_wgrad_sum_kernel folds the slots).
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void dwd_wgrad_kernel(const T* __restrict__ x, int ldx, const T* __restrict__ gy, int ldg,
+                                                        float* __restrict__ part, int B, int H, int W, int Ho, int Wo, int C, int S,
+                                                        int D, int in_relu, DwGeom dg) {
+  constexpr int N = Unit<T, VEC>::N;
+  __shared__ float red[256 * 3 * N];
+  const int tx = threadIdx.x % dg.tx, ty = threadIdx.x / dg.tx;
+  const int u = blockIdx.y * dg.tx + tx;
+  const int kh = blockIdx.z;
+  const int rows = (Ho * Wo + dg.ty - 1) / dg.ty;      // rows of dg.ty pixels per image
+  const int c0 = u * N;
+  float acc[3][N];
+#pragma unroll
+  for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+    for (int e = 0; e < N; ++e) acc[kw][e] = 0.f;
+  if (ty < dg.ty && u < dg.units) {
+    const int nv = C - c0 < N ? C - c0 : N;
+    for (int it = blockIdx.x; it < B * rows; it += gridDim.x) {
+      const int b = it / rows;
+      const int rem = (it - b * rows) * dg.ty + ty;
+      if (rem >= Ho * Wo) continue;
+      const int oh = rem / Wo, ow = rem - oh * Wo;
+      const int ih = dwd_src<false>(oh, kh, S, D, H);
+      if (ih < 0) continue;
+      float g[N];
+      dwd_load<T, VEC>(gy + ((long)b * Ho * Wo + rem) * ldg + c0, g, nv);
+      const T* xr = x + ((long)b * H + ih) * W * ldx + c0;
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw) {
+        const int iw = dwd_src<false>(ow, kw, S, D, W);
+        if (iw < 0) continue;
+        float v[N];
+        dwd_load<T, VEC>(xr + (long)iw * ldx, v, nv);
+#pragma unroll
+        for (int e = 0; e < N; ++e) acc[kw][e] = fmaf(in_relu ? fmaxf(v[e], 0.f) : v[e], g[e], acc[kw][e]);
+      }
+    }
+  }
+#pragma unroll
+  for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+    for (int e = 0; e < N; ++e) red[(kw * 256 + threadIdx.x) * N + e] = acc[kw][e];
+  __syncthreads();
+  const int nch = dg.tx * N;
+  const int cb0 = blockIdx.y * nch;
+  for (int i = threadIdx.x; i < nch * 3; i += blockDim.x) {
+    const int kw = i / nch, cl = i - kw * nch;
+    const int c = cb0 + cl;
+    if (c >= C) continue;
+    const int txi = cl / N, e = cl - txi * N;
+    float a = 0.f;
+    for (int y = 0; y < dg.ty; ++y) a += red[(kw * 256 + y * dg.tx + txi) * N + e];
+    part[((long)blockIdx.x * 9 + kh * 3 + kw) * C + c] = a;
+  }
+}
+
+// the 16-byte path of the dilated kernels needs aligned strides and pointers only (the channel tail is masked)
+template <typename T>
+bool dwd_vec(int ld1, int ld2, int ld3, const void* p1, const void* p2, const void* p3) {
+  constexpr int N = Chunk<T>::N;
+  return ld1 % N == 0 && ld2 % N == 0 && ld3 % N == 0 && (((uintptr_t)p1 | (uintptr_t)p2 | (uintptr_t)p3) & 15) == 0;
+}
+
+template <typename T, bool VEC, bool BWD>
+void dwd_launch(const void* src, int lds, const float* w, const void* xm, int ldm, void* out, int ldo, double* stats, int sld,
+                int nrep, int B, int SH, int SW, int OH, int OW, int C, int S, int D, int in_relu, int ipg, hipStream_t s) {
+  constexpr int N = Unit<T, VEC>::N;
+  const DwGeom dg = dw_geom((C + N - 1) / N);
+  // pixels per thread: as many as leave ~2048 workgroups (8 per CU) to the launch, at most DWD_MAX_PIX
+  const long rows = sdhip_cdiv((long)OH * OW, dg.ty);
+  const long others = (long)sdhip_cdiv(dg.units, dg.tx) * B;
+  long pix = rows * others / 2048;
+  pix = pix < 1 ? 1 : (pix > DWD_MAX_PIX ? DWD_MAX_PIX : pix);
+  dim3 grid((unsigned)sdhip_cdiv(rows, pix), (unsigned)sdhip_cdiv(dg.units, dg.tx), (unsigned)B);
+  hipLaunchKernelGGL((dwd_conv_kernel<T, VEC, BWD>), grid, dim3(256), 0, s, (const T*)src, lds, w, (const T*)xm, ldm, (T*)out, ldo,
+                     stats, sld, nrep, SH, SW, OH, OW, C, S, D, in_relu, ipg, (int)pix, dg);
+}
+
+template <typename T, bool BWD>
+void dwd_dispatch(const void* src, int lds, const float* w, const void* xm, int ldm, void* out, int ldo, double* stats, int sld,
+                  int nrep, int B, int SH, int SW, int OH, int OW, int C, int S, int D, int in_relu, int ipg, hipStream_t s) {
+  if (dwd_vec<T>(lds, ldo, xm ? ldm : 0, src, out, xm))
+    dwd_launch<T, true, BWD>(src, lds, w, xm, ldm, out, ldo, stats, sld, nrep, B, SH, SW, OH, OW, C, S, D, in_relu, ipg, s);
+  else
+    dwd_launch<T, false, BWD>(src, lds, w, xm, ldm, out, ldo, stats, sld, nrep, B, SH, SW, OH, OW, C, S, D, in_relu, ipg, s);
+}
+
+template <typename T>
+void dwd_wgrad_dispatch(const void* x, int ldx, const void* gy, int ldg, float* part, int nparts, int B, int H, int W, int Ho,
+                        int Wo, int C, int S, int D, int in_relu, hipStream_t s) {
+  const bool vec = dwd_vec<T>(ldx, ldg, 0, x, gy, nullptr);
+  const int N = vec ? Chunk<T>::N : 1;
+  const DwGeom dg = dw_geom((C + N - 1) / N);
+  dim3 grid((unsigned)nparts, (unsigned)sdhip_cdiv(dg.units, dg.tx), 3u);
+  if (vec)
+    hipLaunchKernelGGL((dwd_wgrad_kernel<T, true>), grid, dim3(256), 0, s, (const T*)x, ldx, (const T*)gy, ldg, part, B, H, W, Ho, Wo,
+                       C, S, D, in_relu, dg);
+  else
+    hipLaunchKernelGGL((dwd_wgrad_kernel<T, false>), grid, dim3(256), 0, s, (const T*)x, ldx, (const T*)gy, ldg, part, B, H, W, Ho, Wo,
+                       C, S, D, in_relu, dg);
+}
+
+inline int dwd_out(int n, int stride) { return (n - 1) / stride + 1; }
+
+// pixel blocks of the dilated weight gradient: ~64 K (pixel x channel) items each, at most 256
+inline int dwd_wgrad_parts(int B, int H, int W, int C, int stride) {
+  const long npix = (long)B * dwd_out(H, stride) * dwd_out(W, stride);
+  long bx = (npix * C + 65535) / 65536;
+  return (int)(bx < 1 ? 1 : (bx > 256 ? 256 : bx));
+}
+
+inline bool dwd_shape_ok(int B, int H, int W, int C, int stride, int dil) {
+  // 32-bit pixel indices over the batch, and (dil, stride) small enough that tap offsets cannot overflow
+  return B > 0 && B <= 65535 && H > 0 && W > 0 && C > 0 && (long)B * H * W < (1L << 30) && (stride == 1 || stride == 2) && dil >= 1 &&
+         dil <= (1 << 20);
+}
+
 }  // namespace
+
+extern "C" int sdhip_dw_dil_wgrad_parts(int B, int H, int W, int C, int stride) {
+  if (!dwd_shape_ok(B, H, W, C, stride, 1)) return SDHIP_ERR_ARG;
+  return dwd_wgrad_parts(B, H, W, C, stride);
+}
+
+extern "C" int sdhip_dw_dil_conv_fwd(const void* x, int ldx, const float* w, void* y, int ldy, double* stats, int sld, int nrep,
+                                     int B, int H, int W, int C, int stride, int dil, int in_relu, int groups, int dtype,
+                                     void* stream) {
+  SDHIP_CHECK_ARG(x && w && y, "dw_dil_conv_fwd: null pointer");
+  SDHIP_CHECK_ARG(dwd_shape_ok(B, H, W, C, stride, dil) && ldx >= C && ldy >= C, "dw_dil_conv_fwd: bad shape/strides (stride %d, dil %d)",
+                  stride, dil);
+  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "dw_dil_conv_fwd: dtype %d", dtype);
+  SDHIP_CHECK_ARG(groups > 0 && B % groups == 0, "dw_dil_conv_fwd: groups %d does not divide B %d", groups, B);
+  if (nrep < 1) nrep = 1;
+  if (sld <= 0) sld = C;
+  SDHIP_CHECK_ARG(!stats || sld >= C, "dw_dil_conv_fwd: statistics stride");
+  const int Ho = dwd_out(H, stride), Wo = dwd_out(W, stride);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == SDHIP_F32)
+    dwd_dispatch<float, false>(x, ldx, w, nullptr, 0, y, ldy, stats, sld, nrep, B, H, W, Ho, Wo, C, stride, dil, in_relu != 0, B / groups, s);
+  else
+    dwd_dispatch<bf16_t, false>(x, ldx, w, nullptr, 0, y, ldy, stats, sld, nrep, B, H, W, Ho, Wo, C, stride, dil, in_relu != 0, B / groups, s);
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}
+
+extern "C" int sdhip_dw_dil_conv_dgrad(const void* gy, int ldg, const float* w, const void* x, int ldx, void* gx, int ldgx,
+                                       int B, int H, int W, int C, int stride, int dil, int dtype, void* stream) {
+  SDHIP_CHECK_ARG(gy && w && gx, "dw_dil_conv_dgrad: null pointer");
+  SDHIP_CHECK_ARG(dwd_shape_ok(B, H, W, C, stride, dil) && ldg >= C && ldgx >= C && (!x || ldx >= C),
+                  "dw_dil_conv_dgrad: bad shape/strides (stride %d, dil %d)", stride, dil);
+  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "dw_dil_conv_dgrad: dtype %d", dtype);
+  const int Ho = dwd_out(H, stride), Wo = dwd_out(W, stride);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == SDHIP_F32)
+    dwd_dispatch<float, true>(gy, ldg, w, x, ldx, gx, ldgx, nullptr, 0, 1, B, Ho, Wo, H, W, C, stride, dil, 0, 1, s);
+  else
+    dwd_dispatch<bf16_t, true>(gy, ldg, w, x, ldx, gx, ldgx, nullptr, 0, 1, B, Ho, Wo, H, W, C, stride, dil, 0, 1, s);
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}
+
+extern "C" int sdhip_dw_dil_conv_wgrad(const void* x, int ldx, const void* gy, int ldg, float* dw, float* part, int nparts,
+                                       int B, int H, int W, int C, int stride, int dil, int in_relu, int dtype, void* stream) {
+  SDHIP_CHECK_ARG(x && gy && dw && part, "dw_dil_conv_wgrad: null pointer");
+  SDHIP_CHECK_ARG(dwd_shape_ok(B, H, W, C, stride, dil) && ldx >= C && ldg >= C, "dw_dil_conv_wgrad: bad shape/strides (stride %d, dil %d)",
+                  stride, dil);
+  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "dw_dil_conv_wgrad: dtype %d", dtype);
+  SDHIP_CHECK_ARG(nparts == dwd_wgrad_parts(B, H, W, C, stride), "dw_dil_conv_wgrad: %d partial slots, sdhip_dw_dil_wgrad_parts says %d",
+                  nparts, dwd_wgrad_parts(B, H, W, C, stride));
+  const int Ho = dwd_out(H, stride), Wo = dwd_out(W, stride);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == SDHIP_F32)
+    dwd_wgrad_dispatch<float>(x, ldx, gy, ldg, part, nparts, B, H, W, Ho, Wo, C, stride, dil, in_relu != 0, s);
+  else
+    dwd_wgrad_dispatch<bf16_t>(x, ldx, gy, ldg, part, nparts, B, H, W, Ho, Wo, C, stride, dil, in_relu != 0, s);
+  SDHIP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(dw_wgrad_sum_kernel, dim3((unsigned)sdhip_cdiv(9L * C, 32)), dim3(256), 0, s, part, nparts, dw, 9, C);
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}
 
 extern "C" int sdhip_dw_pool_parts(int H, int W, int C, int k, int stride, int dtype) {
   if (H <= 0 || W <= 0 || C <= 0 || (k != 3 && k != 5) || (stride != 1 && stride != 2)) return SDHIP_ERR_ARG;

@@ -2397,3 +2397,71 @@ def se_scale_act(z, fc1, fc2, side, act=0):
     if side is None or side.pool is None:
         raise _lib.SdhipError("se_scale_act needs the pool of the depthwise node in front of it (SESide)")
     return _SEScaleActFn.apply(z, fc1.weight, fc1.bias, fc2.weight, fc2.bias, side, act)
+
+
+# ============================================================================ DeepLabV3+ / Xception-65: dilated depthwise 3x3
+def dw_dil_wgrad_parts(B, H, W, C, stride):
+    """Partial slots of sdhip_dw_dil_conv_wgrad for this shape (include/sdhip.h)."""
+    n = _lib._lib.sdhip_dw_dil_wgrad_parts(B, H, W, C, stride)
+    if n <= 0:
+        raise _lib.SdhipError("sdhip_dw_dil_wgrad_parts: unsupported depthwise shape")
+    return n
+
+
+class _DWDilConvBNActFn(torch.autograd.Function):
+    """y = act(BatchNorm(depthwise_conv3x3(relu?(x), stride, dilation))) as ONE autograd node — depthwise + bn_depth (+ relu1)
+    of SeparableConv2d (models_deeplab_mod/common.py:24-50).  relu_first is applied in the kernel's load: x itself is saved
+    un-rectified (the 'sum' skip of XceptionBlock reads it), the data gradient masks with [x > 0] in its own launch and the
+    weight gradient rectifies in its load."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, bn, stride, dil, in_relu, act, groups):
+        _require_gpu(x, weight)
+        if weight.dtype != torch.float32 or not weight.is_contiguous():
+            raise _lib.SdhipError("depthwise weight must be a contiguous f32 (C, 1, 3, 3) tensor")
+        B, C, H, W = x.shape
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        xv, ldx = nhwc_view(x)
+        dt = dtype_code(x)
+        yraw, ldr = alloc_nhwc(B, C, Ho, Wo, x.dtype, x.device)
+        train = bn.training
+        ws = _zeros((NREP, groups, 2, C), torch.float64, x.device)[0] if train else None
+        call("sdhip_dw_dil_conv_fwd", ptr(xv), ldx, ptr(weight.detach()), ptr(yraw), ldr, ptr(ws), C, NREP, B, H, W, C, stride, dil,
+             int(in_relu), groups, dt, stream_ptr())
+        count = (B // groups) * Ho * Wo
+        y, scale, shift, mean, invstd = _bn_act_forward(yraw, ldr, bn, ws, count, groups, act)
+        ctx.cfg = (stride, dil, in_relu, act, groups, ldx, ldr, count, train)
+        ctx.save_for_backward(xv, weight, gamma, beta, yraw, scale, shift, mean, invstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xv, weight, gamma, beta, yraw, scale, shift, mean, invstd = ctx.saved_tensors
+        stride, dil, in_relu, act, groups, ldx, ldraw, count, train = ctx.cfg
+        B, C, H, W = xv.shape
+        dt = dtype_code(xv)
+        g, ldg = nhwc_view(gy)
+        graw, ldgr, dgamma, dbeta = _bn_act_backward(g, ldg, yraw, ldraw, scale, shift, mean, invstd, gamma, beta, groups, act,
+                                                     count, train)
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gx, ldgx = alloc_nhwc(B, C, H, W, xv.dtype, xv.device)
+            call("sdhip_dw_dil_conv_dgrad", ptr(graw), ldgr, ptr(weight.detach()), ptr(xv) if in_relu else None, ldx, ptr(gx), ldgx,
+                 B, H, W, C, stride, dil, dt, stream_ptr())
+        gw = None
+        if ctx.needs_input_grad[1]:
+            tw = _grad_target(weight)
+            target = tw if tw is not None else _zeros(tuple(weight.shape), torch.float32, weight.device)[0]
+            nparts = dw_dil_wgrad_parts(B, H, W, C, stride)
+            part = torch.empty((nparts * 9 * C,), dtype=torch.float32, device=weight.device)   # every slot is written
+            call("sdhip_dw_dil_conv_wgrad", ptr(xv), ldx, ptr(graw), ldgr, ptr(target), ptr(part), nparts, B, H, W, C, stride, dil,
+                 int(in_relu), dt, stream_ptr())
+            gw = None if tw is not None else target
+        return gx, gw, dgamma, dbeta, None, None, None, None, None, None
+
+
+def dw_dil_conv_bn_act(x, weight, bn, stride=1, dilation=1, in_relu=False, act=0, groups=1):
+    """act(bn(nn.Conv2d(C, C, 3, stride, padding=dilation, dilation=dilation, groups=C, bias=False)(relu(x) if in_relu else x)))."""
+    if tuple(weight.shape) != (x.shape[1], 1, 3, 3) or stride not in (1, 2) or dilation < 1:
+        raise _lib.SdhipError("dilated depthwise convolution: (C, 1, 3, 3) weights, stride 1 / 2, dilation >= 1 only")
+    return _DWDilConvBNActFn.apply(x, weight, bn.weight, bn.bias, bn, stride, int(dilation), bool(in_relu), act, groups)
