@@ -374,7 +374,11 @@ int sdhip_sgd_step(float* params, const float* grads, float* momentum_buf, const
                    float momentum, float weight_decay, float grad_scale,
                    const long* live, long n_live, void* stream);
 /* loss += weight * mean_p sum_c -target[p,c]*log_softmax(logits[p,:])_c  and (optionally) its gradient w.r.t. the
- * logits: categoricalCrossEntropy(F.log_softmax(y,1), gt) of util/utilTorchLoss.py:373-378.  target is f32. */
+ * logits: categoricalCrossEntropy(F.log_softmax(y,1), gt) of util/utilTorchLoss.py:373-378.  target is f32.
+ * grad[p,c] = weight/npix * (softmax(logits[p,:])_c * sum_c target[p,c] - target[p,c]) is written, not accumulated.
+ * logits, target and grad rows may each be channel slices of a wider slab (ldy, ldt, ldg >= C): nothing past the last
+ * pixel's channel C-1 is read or written.  The pad lanes C..ldg-1 of a grad row are unspecified after the call (kept or
+ * overwritten with zeros); everything outside the rows is untouched. */
 int sdhip_ce_loss(const void* logits, int ldy, const float* target, int ldt, void* grad, int ldg, double* loss,
                   long npix, int C, float weight, int dtype, void* stream);
 /* loss += weight * mean |pred - target| (nn.L1Loss, losses/multiLosses.py:141) and its gradient.  mask_nonpositive != 0:
@@ -491,6 +495,8 @@ int sdhip_log_softmax_bwd(const void* gy, int ldg, const void* y, int ldy, void*
  * on (B, C, L, 1) images.
  * rowpool_max: nn.AdaptiveMaxPool2d((OH, 1)) (HANet.py:50-55,84): y[b,i,c] = max over rows [floor(i*H/OH),
  *   ceil((i+1)*H/OH)) and all columns of x[b,:,:,c]; idx[b,i,c] = h*W+w of the first maximum (int32, dense [B][OH][C]).
+ *   A NaN wins as in ATen's scan (`v > best || isnan(v)`): the bin's value is NaN and idx its last NaN.  bwd: gx[b,h,w,c] =
+ *   sum of gy[b,i,c] over the bins i with idx[b,i,c] = h*W+w, written (only the C logical lanes of each gx pixel are touched).
  * mul_rows: torch.mul(out, attention.unsqueeze(3)) (HANet.py:112): y[b,h,w,c] = a[b,h,w,c] * att[b,h,c].
  * dropout_channels: nn.Dropout2d(p) on a (B, C, L) tensor (HANet.py:27-28,90-91): whole (b,c) rows dropped, rest scaled by
  *   1/(1-p); mask from a counter hash of (*seed, layer_id, b*C+c) — the same call on the gradient is the backward.

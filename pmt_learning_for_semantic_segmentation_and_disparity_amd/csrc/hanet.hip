@@ -38,15 +38,24 @@ __global__ __launch_bounds__(256) void rowpool_max_fwd_kernel(const T* __restric
     __syncthreads();
     if (tw == 0 && c < C) {
       float m = sv[tc]; int mi = si[tc];
-      for (int k = 1; k < wl; ++k) {   // the earliest index among equal maxima = the first one in scan order
-        const float v = sv[k * lanes_c + tc]; const int vi = si[k * lanes_c + tc];
-        if (vi == 0x7fffffff) continue;
-        if (v > m || (v == m && vi < mi) || (v != v && m == m)) { m = v; mi = vi; }
+      for (int k = 1; k < wl; ++k) {   // the earliest index among equal maxima = the first one in scan order;
+        const float v = sv[k * lanes_c + tc]; const int vi = si[k * lanes_c + tc];   // among NaNs the LAST one, as a serial scan
+        if (vi == 0x7fffffff) continue;                                              // with `v > best || isnan(v)` ends on it
+        if (v > m || (v == m && vi < mi) || (v != v && (m == m || vi > mi))) { m = v; mi = vi; }
       }
       Elem<T>::st(y + ((long)b * OH + i) * ldy + c, m);
       idx[((long)b * OH + i) * C + c] = mi;
     }
     __syncthreads();
+  }
+}
+
+// gx[pix, 0:C] = 0 of a channel slice (ldgx != C): the other lanes of the pixel stride belong to somebody else
+template <typename T>
+__global__ void zero_rows_kernel(T* __restrict__ gx, int ldgx, int C, long total) {
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+    const long pix = t / C;
+    Elem<T>::st(gx + pix * ldgx + (int)(t - pix * C), 0.f);
   }
 }
 
@@ -149,11 +158,18 @@ extern "C" int sdhip_rowpool_max_fwd(const void* x, int ldx, void* y, int ldy, i
 
 extern "C" int sdhip_rowpool_max_bwd(const void* gy, int ldg, const int* idx, void* gx, int ldgx, int B, int H, int W, int C, int OH,
                                      int dtype, void* stream) {
-  SDHIP_CHECK_ARG(gy && idx && gx && B > 0 && H > 0 && W > 0 && C > 0 && OH > 0, "rowpool_max_bwd: bad arguments");
+  SDHIP_CHECK_ARG(gy && idx && gx && B > 0 && H > 0 && W > 0 && C > 0 && OH > 0 && ldg >= C && ldgx >= C, "rowpool_max_bwd: bad arguments");
   SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "rowpool_max_bwd: unknown dtype %d", dtype);
   hipStream_t s = (hipStream_t)stream;
   const size_t es = dtype == SDHIP_BF16 ? 2 : 4;
-  if (sdhip_zero_async(gx, (size_t)B * H * W * ldgx * es, s) != hipSuccess) SDHIP_FAIL(SDHIP_ERR_LAUNCH, "rowpool_max_bwd: memset failed");
+  const long nz = (long)B * H * W * C;
+  if (ldgx == C) {   // dense: one contiguous clear
+    if (sdhip_zero_async(gx, (size_t)nz * es, s) != hipSuccess) SDHIP_FAIL(SDHIP_ERR_LAUNCH, "rowpool_max_bwd: memset failed");
+  } else if (dtype == SDHIP_F32) {
+    hipLaunchKernelGGL(zero_rows_kernel<float>, dim3(blocks_for(nz)), dim3(256), 0, s, (float*)gx, ldgx, C, nz);
+  } else {
+    hipLaunchKernelGGL(zero_rows_kernel<bf16_t>, dim3(blocks_for(nz)), dim3(256), 0, s, (bf16_t*)gx, ldgx, C, nz);
+  }
   const long total = (long)B * C;
   if (dtype == SDHIP_F32) hipLaunchKernelGGL(rowpool_max_bwd_kernel<float>, dim3(blocks_for(total)), dim3(256), 0, s, (const float*)gy, ldg, idx, (float*)gx, ldgx, H, W, C, OH, total);
   else hipLaunchKernelGGL(rowpool_max_bwd_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, s, (const bf16_t*)gy, ldg, idx, (bf16_t*)gx, ldgx, H, W, C, OH, total);

@@ -121,7 +121,9 @@ __global__ __launch_bounds__(256) void ce_kernel(const T* __restrict__ y, int ld
   if (threadIdx.x == 0) atomicAdd(loss, (double)tot * (double)wnorm);
 }
 
-// The same for many classes (5 <= C <= 64; 19 Cityscapes classes): the workgroup's 256 pixel rows travel through LDS (rows_lds.h)
+// The same for many classes (5 <= C <= 64; 19 Cityscapes classes): the workgroup's 256 pixel rows travel through LDS (rows_lds.h).
+// A tile of n pixels is copied as (n-1)*ld + C elements: the rows may be channel slices of a wider slab, whose allocation ends
+// with the last pixel's channel C-1.  The pad lanes between two pixels of a tile travel along (in grad they come back as zeros).
 template <typename T>
 __global__ __launch_bounds__(256) void ce_rows_kernel(const T* __restrict__ y, int ldy, const float* __restrict__ t, int ldt,
                                                       T* __restrict__ gy, int ldg, double* __restrict__ loss, long npix, int C, float wnorm,
@@ -137,8 +139,8 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const T* __restrict__ y, i
   for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const long p0 = tile * 256;
     const int n = (int)min(256L, npix - p0);
-    rows_to_lds(y + p0 * ldy, ly, n * ldy * (int)sizeof(T), tid);
-    rows_to_lds(t + p0 * ldt, lt, n * ldt * 4, tid);
+    rows_to_lds(y + p0 * ldy, ly, ((n - 1) * ldy + C) * (int)sizeof(T), tid);
+    rows_to_lds(t + p0 * ldt, lt, ((n - 1) * ldt + C) * 4, tid);
     __syncthreads();
     if (tid < n) {
       const T* yp = ly + tid * ldy;
@@ -156,7 +158,7 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const T* __restrict__ y, i
       }
     }
     __syncthreads();
-    if (gy) rows_from_lds(gy + p0 * ldg, lg, n * ldg * (int)sizeof(T), tid);
+    if (gy) rows_from_lds(gy + p0 * ldg, lg, ((n - 1) * ldg + C) * (int)sizeof(T), tid);
     __syncthreads();
   }
   const float tot = block_sum(part, sh);
