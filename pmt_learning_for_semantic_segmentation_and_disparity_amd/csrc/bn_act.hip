@@ -571,15 +571,6 @@ __global__ __launch_bounds__(256) void bn_finalize_bwd_kernel(const float* __res
   }
 }
 
-template <typename T>
-bool vec_rows(int C, std::initializer_list<int> lds, std::initializer_list<const void*> ptrs) {
-  const int n = Chunk<T>::N;
-  if (C % n) return false;
-  for (int l : lds) if (l % n) return false;
-  for (const void* p : ptrs) if (p && ((uintptr_t)p & 15)) return false;
-  return true;
-}
-
 struct Plan { RowGeom rg; dim3 grid; };
 Plan plan(int units, long npix_g, int G, int max_blocks = 2048) {
   Plan p;
@@ -598,7 +589,7 @@ int tune_fused_blocks() { return sdhip_diag().tune_fused_blocks; }
 
 int check_rows(const char* who, long npix, int C, int G, int dtype) {
   SDHIP_CHECK_ARG(npix > 0 && C > 0 && G >= 1 && npix % G == 0, "%s: bad shape npix=%ld C=%d groups=%d", who, npix, C, G);
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "%s: unknown dtype %d", who, dtype);
+  SDHIP_CHECK_DTYPE(who, dtype);
   return 0;
 }
 
@@ -688,25 +679,14 @@ extern "C" int sdhip_affine_act(const void* x, int ldx, void* y, int ldy, const 
   SDHIP_CHECK_ARG(x && y && ldx >= C && ldy >= C && (!res || ldr >= C), "affine_act: bad pointers/strides");
   SDHIP_CHECK_ARG(act == 0 || act == 1 || act == 2 || act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID, "affine_act: activation %d", act);
   hipStream_t s = (hipStream_t)stream;
-#define ARGS(T) (const T*)x, ldx, (T*)y, ldy, (const T*)res, ldr, scale, shift, C, npix / G, act
-  if (dtype == SDHIP_F32) {
-    const bool v = vec_rows<float>(C, {ldx, ldy, res ? ldr : 0}, {x, y, res});
-    Plan pl = plan(v ? C / 4 : C, npix / G, G);
-    if (hard_act(act)) {
-      if (v) hipLaunchKernelGGL((affine_act_kernel<float, true, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-      else hipLaunchKernelGGL((affine_act_kernel<float, false, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-    } else if (v) hipLaunchKernelGGL((affine_act_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-    else hipLaunchKernelGGL((affine_act_kernel<float, false>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-  } else {
-    const bool v = vec_rows<bf16_t>(C, {ldx, ldy, res ? ldr : 0}, {x, y, res});
-    Plan pl = plan(v ? C / 8 : C, npix / G, G);
-    if (hard_act(act)) {
-      if (v) hipLaunchKernelGGL((affine_act_kernel<bf16_t, true, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-      else hipLaunchKernelGGL((affine_act_kernel<bf16_t, false, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-    } else if (v) hipLaunchKernelGGL((affine_act_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-    else hipLaunchKernelGGL((affine_act_kernel<bf16_t, false>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-  }
-#undef ARGS
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const bool v = sdhip_vec_ok<T>(C, {ldx, ldy, res ? ldr : 0}, {x, y, res});
+    const Plan pl = plan(v ? C / Chunk<T>::N : C, npix / G, G);
+    sdhip_by_flag(v, [&](auto V) { sdhip_by_flag(hard_act(act), [&](auto HS) {
+      hipLaunchKernelGGL((affine_act_kernel<T, V(), HS()>), pl.grid, dim3(256), 0, s, (const T*)x, ldx, (T*)y, ldy, (const T*)res, ldr, scale, shift, C, npix / G, act, pl.rg);
+    }); });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -727,25 +707,14 @@ extern "C" int sdhip_affine_act_bwd(const void* gy, int ldg, const void* x, int 
         sdhip_zero_async(dshift, sizeof(float) * (size_t)nrep * G * C, s) != hipSuccess)
       SDHIP_FAIL(SDHIP_ERR_LAUNCH, "affine_act_bwd: memset failed");
   }
-#define ARGS(T) (const T*)gy, ldg, (const T*)x, ldx, (T*)gx, ldgx, scale, shift, dscale, dshift, nrep, C, npix / G, act, accumulate
-  if (dtype == SDHIP_F32) {
-    const bool v = vec_rows<float>(C, {ldg, ldx, gx ? ldgx : 0}, {gy, x, gx});
-    Plan pl = plan(v ? C / 4 : C, npix / G, G, 1024);
-    if (hard_act(act)) {
-      if (v) hipLaunchKernelGGL((affine_act_bwd_kernel<float, true, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-      else hipLaunchKernelGGL((affine_act_bwd_kernel<float, false, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-    } else if (v) hipLaunchKernelGGL((affine_act_bwd_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-    else hipLaunchKernelGGL((affine_act_bwd_kernel<float, false>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-  } else {
-    const bool v = vec_rows<bf16_t>(C, {ldg, ldx, gx ? ldgx : 0}, {gy, x, gx});
-    Plan pl = plan(v ? C / 8 : C, npix / G, G, 1024);
-    if (hard_act(act)) {
-      if (v) hipLaunchKernelGGL((affine_act_bwd_kernel<bf16_t, true, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-      else hipLaunchKernelGGL((affine_act_bwd_kernel<bf16_t, false, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-    } else if (v) hipLaunchKernelGGL((affine_act_bwd_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-    else hipLaunchKernelGGL((affine_act_bwd_kernel<bf16_t, false>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-  }
-#undef ARGS
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const bool v = sdhip_vec_ok<T>(C, {ldg, ldx, gx ? ldgx : 0}, {gy, x, gx});
+    const Plan pl = plan(v ? C / Chunk<T>::N : C, npix / G, G, 1024);
+    sdhip_by_flag(v, [&](auto V) { sdhip_by_flag(hard_act(act), [&](auto HS) {
+      hipLaunchKernelGGL((affine_act_bwd_kernel<T, V(), HS()>), pl.grid, dim3(256), 0, s, (const T*)gy, ldg, (const T*)x, ldx, (T*)gx, ldgx, scale, shift, dscale, dshift, nrep, C, npix / G, act, accumulate, pl.rg);
+    }); });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -757,19 +726,14 @@ extern "C" int sdhip_stats_fix(const void* gin, int ldgi, const void* x, int ldx
   if (int rc = check_rows("stats_fix", npix, C, G, dtype)) return rc;
   SDHIP_CHECK_ARG(gin && x && gout && dS && ldgi >= C && ldx >= C && ldgo >= C, "stats_fix: bad pointers/strides");
   hipStream_t s = (hipStream_t)stream;
-#define ARGS(T) (const T*)gin, ldgi, (const T*)x, ldx, (T*)gout, ldgo, dS, ldc, C, npix / G
-  if (dtype == SDHIP_F32) {
-    const bool v = vec_rows<float>(C, {ldgi, ldx, ldgo}, {gin, x, gout});
-    Plan pl = plan(v ? C / 4 : C, npix / G, G);
-    if (v) hipLaunchKernelGGL((stats_fix_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-    else hipLaunchKernelGGL((stats_fix_kernel<float, false>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-  } else {
-    const bool v = vec_rows<bf16_t>(C, {ldgi, ldx, ldgo}, {gin, x, gout});
-    Plan pl = plan(v ? C / 8 : C, npix / G, G);
-    if (v) hipLaunchKernelGGL((stats_fix_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-    else hipLaunchKernelGGL((stats_fix_kernel<bf16_t, false>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-  }
-#undef ARGS
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const bool v = sdhip_vec_ok<T>(C, {ldgi, ldx, ldgo}, {gin, x, gout});
+    const Plan pl = plan(v ? C / Chunk<T>::N : C, npix / G, G);
+    sdhip_by_flag(v, [&](auto V) {
+      hipLaunchKernelGGL((stats_fix_kernel<T, V()>), pl.grid, dim3(256), 0, s, (const T*)gin, ldgi, (const T*)x, ldx, (T*)gout, ldgo, dS, ldc, C, npix / G, pl.rg);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -783,25 +747,14 @@ extern "C" int sdhip_bn_bwd_apply(const void* gy, int ldg, const void* x, int ld
   SDHIP_CHECK_ARG(gy && x && gx && scale && shift && dS && ldg >= C && ldx >= C && ldgx >= C, "bn_bwd_apply: bad pointers/strides");
   SDHIP_CHECK_ARG(act == 0 || act == 1 || act == 2 || act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID, "bn_bwd_apply: activation %d", act);
   hipStream_t s = (hipStream_t)stream;
-#define ARGS(T) (const T*)gy, ldg, (const T*)x, ldx, (T*)gx, ldgx, scale, shift, dS, ldc, C, npix / G, act
-  if (dtype == SDHIP_F32) {
-    const bool v = vec_rows<float>(C, {ldg, ldx, ldgx}, {gy, x, gx});
-    Plan pl = plan(v ? C / 4 : C, npix / G, G, 1024);
-    if (hard_act(act)) {
-      if (v) hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-      else hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-    } else if (v) hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-  } else {
-    const bool v = vec_rows<bf16_t>(C, {ldg, ldx, ldgx}, {gy, x, gx});
-    Plan pl = plan(v ? C / 8 : C, npix / G, G, 1024);
-    if (hard_act(act)) {
-      if (v) hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, true, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-      else hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, false, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-    } else if (v) hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, false>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-  }
-#undef ARGS
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const bool v = sdhip_vec_ok<T>(C, {ldg, ldx, ldgx}, {gy, x, gx});
+    const Plan pl = plan(v ? C / Chunk<T>::N : C, npix / G, G, 1024);
+    sdhip_by_flag(v, [&](auto V) { sdhip_by_flag(hard_act(act), [&](auto HS) {
+      hipLaunchKernelGGL((bn_bwd_apply_kernel<T, V(), HS()>), pl.grid, dim3(256), 0, s, (const T*)gy, ldg, (const T*)x, ldx, (T*)gx, ldgx, scale, shift, dS, ldc, C, npix / G, act, pl.rg);
+    }); });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -820,26 +773,15 @@ extern "C" int sdhip_affine_act_bn(const void* x, int ldx, void* y, int ldy, con
   SDHIP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr) && count > 0., "affine_act_bn: bad statistics arguments");
   SDHIP_CHECK_ARG(act == 0 || act == 1 || act == 2 || act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID, "affine_act_bn: activation %d", act);
   hipStream_t s = (hipStream_t)stream;
-#define ARGS(T) (const T*)x, ldx, (T*)y, ldy, (const T*)res, ldr, stats, ldc, nrep, gamma, beta, running_mean, running_var, \
-                scale, shift, mean_out, invstd_out, C, npix / G, count, eps, momentum, act
-  if (dtype == SDHIP_F32) {
-    const bool v = vec_rows<float>(C, {ldx, ldy, res ? ldr : 0}, {x, y, res});
-    Plan pl = plan(v ? C / 4 : C, npix / G, G, tune_fused_blocks());
-    if (hard_act(act)) {
-      if (v) hipLaunchKernelGGL((affine_act_bn_kernel<float, true, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-      else hipLaunchKernelGGL((affine_act_bn_kernel<float, false, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-    } else if (v) hipLaunchKernelGGL((affine_act_bn_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-    else hipLaunchKernelGGL((affine_act_bn_kernel<float, false>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-  } else {
-    const bool v = vec_rows<bf16_t>(C, {ldx, ldy, res ? ldr : 0}, {x, y, res});
-    Plan pl = plan(v ? C / 8 : C, npix / G, G, tune_fused_blocks());
-    if (hard_act(act)) {
-      if (v) hipLaunchKernelGGL((affine_act_bn_kernel<bf16_t, true, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-      else hipLaunchKernelGGL((affine_act_bn_kernel<bf16_t, false, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-    } else if (v) hipLaunchKernelGGL((affine_act_bn_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-    else hipLaunchKernelGGL((affine_act_bn_kernel<bf16_t, false>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-  }
-#undef ARGS
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const bool v = sdhip_vec_ok<T>(C, {ldx, ldy, res ? ldr : 0}, {x, y, res});
+    const Plan pl = plan(v ? C / Chunk<T>::N : C, npix / G, G, tune_fused_blocks());
+    sdhip_by_flag(v, [&](auto V) { sdhip_by_flag(hard_act(act), [&](auto HS) {
+      hipLaunchKernelGGL((affine_act_bn_kernel<T, V(), HS()>), pl.grid, dim3(256), 0, s, (const T*)x, ldx, (T*)y, ldy, (const T*)res, ldr, stats, ldc, nrep, gamma, beta, running_mean, running_var,
+                         scale, shift, mean_out, invstd_out, C, npix / G, count, eps, momentum, act, pl.rg);
+    }); });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -857,26 +799,15 @@ static int bn_bwd_apply_fin_impl(const void* gy, int ldg, const void* x, int ldx
   SDHIP_CHECK_ARG((act == 0 || act == 1 || act == 2 || act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID) && count > 0. && (dgamma == nullptr) == (dbeta == nullptr),
                   "bn_bwd_apply_fin: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-#define ARGS(T) (const T*)gy, ldg, (const T*)x, ldx, (T*)gx, ldgx, scale, shift, dscale, dshift, nrep, gamma, mean, invstd, \
-                dgamma, dbeta, accumulate_params, param_scale, C, npix / G, 1.0 / count, act, dsum
-  if (dtype == SDHIP_F32) {
-    const bool v = vec_rows<float>(C, {ldg, ldx, ldgx}, {gy, x, gx});
-    Plan pl = plan(v ? C / 4 : C, npix / G, G, tune_fused_blocks());
-    if (hard_act(act)) {
-      if (v) hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<float, true, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-      else hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<float, false, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-    } else if (v) hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-    else hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<float, false>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-  } else {
-    const bool v = vec_rows<bf16_t>(C, {ldg, ldx, ldgx}, {gy, x, gx});
-    Plan pl = plan(v ? C / 8 : C, npix / G, G, tune_fused_blocks());
-    if (hard_act(act)) {
-      if (v) hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<bf16_t, true, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-      else hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<bf16_t, false, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-    } else if (v) hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-    else hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<bf16_t, false>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-  }
-#undef ARGS
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const bool v = sdhip_vec_ok<T>(C, {ldg, ldx, ldgx}, {gy, x, gx});
+    const Plan pl = plan(v ? C / Chunk<T>::N : C, npix / G, G, tune_fused_blocks());
+    sdhip_by_flag(v, [&](auto V) { sdhip_by_flag(hard_act(act), [&](auto HS) {
+      hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<T, V(), HS()>), pl.grid, dim3(256), 0, s, (const T*)gy, ldg, (const T*)x, ldx, (T*)gx, ldgx, scale, shift, dscale, dshift, nrep, gamma, mean, invstd,
+                         dgamma, dbeta, accumulate_params, param_scale, C, npix / G, 1.0 / count, act, dsum, pl.rg);
+    }); });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -919,19 +850,14 @@ extern "C" int sdhip_channel_stats(const void* x, int ldx, double* stats, int ld
         if (sdhip_zero_async(stats + r * (size_t)ldc, sizeof(double) * (size_t)C, s) != hipSuccess) SDHIP_FAIL(SDHIP_ERR_LAUNCH, "channel_stats: clear failed");
     }
   }
-#define ARGS(T) (const T*)x, ldx, stats, ldc, nrep, C, npix / G
-  if (dtype == SDHIP_F32) {
-    const bool v = vec_rows<float>(C, {ldx}, {x});
-    Plan pl = plan(v ? C / 4 : C, npix / G, G, 1024);
-    if (v) hipLaunchKernelGGL((channel_stats_kernel<float, true>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-    else hipLaunchKernelGGL((channel_stats_kernel<float, false>), pl.grid, dim3(256), 0, s, ARGS(float), pl.rg);
-  } else {
-    const bool v = vec_rows<bf16_t>(C, {ldx}, {x});
-    Plan pl = plan(v ? C / 8 : C, npix / G, G, 1024);
-    if (v) hipLaunchKernelGGL((channel_stats_kernel<bf16_t, true>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-    else hipLaunchKernelGGL((channel_stats_kernel<bf16_t, false>), pl.grid, dim3(256), 0, s, ARGS(bf16_t), pl.rg);
-  }
-#undef ARGS
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const bool v = sdhip_vec_ok<T>(C, {ldx}, {x});
+    const Plan pl = plan(v ? C / Chunk<T>::N : C, npix / G, G, 1024);
+    sdhip_by_flag(v, [&](auto V) {
+      hipLaunchKernelGGL((channel_stats_kernel<T, V()>), pl.grid, dim3(256), 0, s, (const T*)x, ldx, stats, ldc, nrep, C, npix / G, pl.rg);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -1057,20 +983,16 @@ extern "C" int sdhip_stats_fix_fin(const void* gin, int ldgi, const void* x, int
                   ldgo >= 32 && cs >= 0 && cs + 32 <= Cf && ldc >= Cf && nrep >= 1 && count > 0., "stats_fix_fin: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   const int nfb = sdhip_cdiv(Cf, 32);
-#define ARGS(T) (const T*)gin, ldgi, (const T*)x, ldx, (T*)gout, ldgo, npix / G, pl.rg, dS, ldc, cs, dscale, dshift, nrep, gamma, mean, invstd, \
-                dgamma, dbeta, accumulate_params, param_scale, Cf, G, 1.0 / count
-  if (dtype == SDHIP_F32) {
-    SDHIP_CHECK_ARG((vec_rows<float>(32, {ldgi, ldx, ldgo}, {gin, x, gout})), "stats_fix_fin: rows must be 16-byte aligned");
-    Plan pl = plan(32 / 4, npix / G, G);
+  const int rc = sdhip_by_dtype(dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    SDHIP_CHECK_ARG((sdhip_vec_ok<T>(32, {ldgi, ldx, ldgo}, {gin, x, gout})), "stats_fix_fin: rows must be 16-byte aligned");
+    Plan pl = plan(32 / Chunk<T>::N, npix / G, G);
     if ((int)pl.grid.x < nfb) pl.grid.x = nfb;            // enough workgroups for the per-channel part
-    hipLaunchKernelGGL((stats_fix_fin_kernel<float>), pl.grid, dim3(256), 0, s, ARGS(float));
-  } else {
-    SDHIP_CHECK_ARG((vec_rows<bf16_t>(32, {ldgi, ldx, ldgo}, {gin, x, gout})), "stats_fix_fin: rows must be 16-byte aligned");
-    Plan pl = plan(32 / 8, npix / G, G);
-    if ((int)pl.grid.x < nfb) pl.grid.x = nfb;
-    hipLaunchKernelGGL((stats_fix_fin_kernel<bf16_t>), pl.grid, dim3(256), 0, s, ARGS(bf16_t));
-  }
-#undef ARGS
+    hipLaunchKernelGGL((stats_fix_fin_kernel<T>), pl.grid, dim3(256), 0, s, (const T*)gin, ldgi, (const T*)x, ldx, (T*)gout, ldgo, npix / G, pl.rg,
+                       dS, ldc, cs, dscale, dshift, nrep, gamma, mean, invstd, dgamma, dbeta, accumulate_params, param_scale, Cf, G, 1.0 / count);
+    return SDHIP_OK;
+  });
+  if (rc) return rc;
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }

@@ -445,17 +445,9 @@ int corr_raise_lds(K kern, size_t lds) {
 }
 
 bool corr_tiled_ok(const void* a, const void* b, const void* c, const void* d, int C, int ld, int PH, int PW, int dil, int ld_out, int dtype) {
-  auto al = [](const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; };
   int nks;
-  return dtype == SDHIP_BF16 && dil == 1 && C % 8 == 0 && ld % 8 == 0 && al(a) && al(b) && al(c) && al(d) && ld_out == PH * PW &&
+  return dtype == SDHIP_BF16 && dil == 1 && sdhip_vec_ok<bf16_t>(C, {ld}, {a, b, c, d}) && ld_out == PH * PW &&
          PH * PW >= 9 && corr_tile_plan(PH, PW, &nks) != 0 && !sdhip_diag().corr_no_tiled;
-}
-
-template <typename T>
-bool vec_ok(const void* a, const void* b, const void* c, const void* d, int C, int ld) {
-  const int n = Chunk<T>::N;
-  auto al = [](const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; };
-  return (C % n == 0) && (ld % n == 0) && al(a) && al(b) && al(c) && al(d);
 }
 
 int check_common(int B, int H, int W, int C, int ld_in, int PH, int PW, int dil, int ld_out, int dtype) {
@@ -463,7 +455,7 @@ int check_common(int B, int H, int W, int C, int ld_in, int PH, int PW, int dil,
   SDHIP_CHECK_ARG(PH > 0 && PW > 0 && (PH & 1) && (PW & 1), "corr: patch size must be odd, got (%d,%d)", PH, PW);
   SDHIP_CHECK_ARG(dil >= 1, "corr: dilation_patch must be >= 1");
   SDHIP_CHECK_ARG(ld_in >= C && ld_out >= PH * PW, "corr: pixel stride smaller than channel count");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "corr: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("corr", dtype);
   SDHIP_CHECK_ARG((long)B * H * W < (1L << 31), "corr: more than 2^31 pixels");
   return 0;
 }
@@ -490,14 +482,13 @@ extern "C" int sdhip_corr_fwd(const void* in1, const void* in2, void* out, int B
     return SDHIP_OK;
   }
   dim3 grid(sdhip_cdiv(npix, kWavesPerBlock)), block(kWavesPerBlock * 64);
-#define LAUNCH(T, VEC) hipLaunchKernelGGL((corr_fwd_kernel<T, VEC>), grid, block, 0, s, (const T*)in1, (const T*)in2, \
-                                          (T*)out, B, H, W, C, ld_in, PH, PW, dil_patch, ld_out)
-  if (dtype == SDHIP_F32) {
-    if (vec_ok<float>(in1, in2, nullptr, nullptr, C, ld_in)) LAUNCH(float, true); else LAUNCH(float, false);
-  } else {
-    if (vec_ok<bf16_t>(in1, in2, nullptr, nullptr, C, ld_in)) LAUNCH(bf16_t, true); else LAUNCH(bf16_t, false);
-  }
-#undef LAUNCH
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {ld_in}, {in1, in2}), [&](auto V) {
+      hipLaunchKernelGGL((corr_fwd_kernel<T, V()>), grid, block, 0, s, (const T*)in1, (const T*)in2, (T*)out, B, H, W, C, ld_in, PH, PW,
+                         dil_patch, ld_out);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -523,14 +514,13 @@ extern "C" int sdhip_corr_bwd(const void* in1, const void* in2, const void* gout
 #undef TBWD
   }
   dim3 grid(sdhip_cdiv(npix, kWavesPerBlock)), block(kWavesPerBlock * 64);
-#define LAUNCH(T, VEC) hipLaunchKernelGGL((corr_bwd_kernel<T, VEC>), grid, block, 0, s, (const T*)in1, (const T*)in2, \
-                                          (const T*)gout, (T*)gin1, (T*)gin2, B, H, W, C, ld_in, PH, PW, dil_patch, ld_out)
-  if (dtype == SDHIP_F32) {
-    if (vec_ok<float>(in1, in2, gin1, gin2, C, ld_in)) LAUNCH(float, true); else LAUNCH(float, false);
-  } else {
-    if (vec_ok<bf16_t>(in1, in2, gin1, gin2, C, ld_in)) LAUNCH(bf16_t, true); else LAUNCH(bf16_t, false);
-  }
-#undef LAUNCH
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {ld_in}, {in1, in2, gin1, gin2}), [&](auto V) {
+      hipLaunchKernelGGL((corr_bwd_kernel<T, V()>), grid, block, 0, s, (const T*)in1, (const T*)in2, (const T*)gout, (T*)gin1, (T*)gin2,
+                         B, H, W, C, ld_in, PH, PW, dil_patch, ld_out);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }

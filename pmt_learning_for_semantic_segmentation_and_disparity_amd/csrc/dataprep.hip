@@ -90,7 +90,7 @@ extern "C" int sdhip_prepare_sample(const unsigned char* left, const unsigned ch
   SDHIP_CHECK_ARG(H > 0 && W > 0 && out_h > 0 && out_w > 0, "prepare_sample: empty image");
   SDHIP_CHECK_ARG(crop_top >= 0 && crop_left >= 0 && crop_top + out_h <= H && crop_left + out_w <= W,
                   "prepare_sample: crop %dx%d at (%d,%d) leaves the %dx%d image", out_h, out_w, crop_top, crop_left, H, W);
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "prepare_sample: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("prepare_sample", dtype);
   SDHIP_CHECK_ARG(row_roll >= 0 && row_roll < out_h, "prepare_sample: row_roll %d outside [0, %d)", row_roll, out_h);
   SDHIP_CHECK_ARG(left || seg || depth, "prepare_sample: nothing to do");
   if (left) SDHIP_CHECK_ARG(right && out_left && out_right && mean && stdv && img_cs >= 3 && img_pitch >= (long)W * img_cs && ld_img >= 3,
@@ -122,8 +122,10 @@ extern "C" int sdhip_prepare_sample(const unsigned char* left, const unsigned ch
   const long n = (long)out_h * out_w;
   long blocks = (n + 255) / 256;
   if (blocks > 2048) blocks = 2048;
-  if (dtype == SDHIP_F32) hipLaunchKernelGGL(prepare_sample_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(prepare_sample_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(prepare_sample_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -210,7 +212,7 @@ extern "C" int sdhip_flip_sample(void* left, void* right, int ld_img, float* seg
                                  void* workspace, long workspace_bytes, int dtype, void* stream) {
   SDHIP_CHECK_ARG(left && right && seg && disp && workspace && H > 0 && W > 20 && n_seg >= 2 && ld_img >= 3 && ld_seg >= n_seg,
                   "flip_sample: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "flip_sample: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("flip_sample", dtype);
   SDHIP_CHECK_ARG(workspace_bytes >= sdhip_flip_sample_workspace_bytes(H, W, n_seg), "flip_sample: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const long n = (long)H * W;
@@ -223,12 +225,11 @@ extern "C" int sdhip_flip_sample(void* left, void* right, int ld_img, float* seg
   hipLaunchKernelGGL(flip_winner_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)disp, winner, H, W);
   hipLaunchKernelGGL(flip_maps_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)disp, (const float*)seg, ld_seg, n_seg,
                      (const int*)winner, dtmp, stmp, H, W);
-  if (dtype == SDHIP_F32)
-    hipLaunchKernelGGL(flip_apply_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, (float*)left, (float*)right, ld_img, disp, seg, ld_seg,
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(flip_apply_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, (T*)left, (T*)right, ld_img, disp, seg, ld_seg,
                        n_seg, (const float*)dtmp, (const float*)stmp, H, W);
-  else
-    hipLaunchKernelGGL(flip_apply_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, s, (bf16_t*)left, (bf16_t*)right, ld_img, disp, seg, ld_seg,
-                       n_seg, (const float*)dtmp, (const float*)stmp, H, W);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -269,14 +270,16 @@ __global__ __launch_bounds__(256) void double_left_kernel(T* __restrict__ left, 
 extern "C" int sdhip_double_left_sample(void* left, void* right, int ld_img, float* seg, int ld_seg, int n_seg, float* disp,
                                         int H, int W, int dtype, void* stream) {
   SDHIP_CHECK_ARG(H > 0 && W > 0 && (left || seg || disp), "double_left_sample: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "double_left_sample: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("double_left_sample", dtype);
   if (left) SDHIP_CHECK_ARG(right && ld_img >= 3, "double_left_sample: image arguments");
   if (seg) SDHIP_CHECK_ARG(n_seg >= 1 && ld_seg >= n_seg, "double_left_sample: segmentation arguments");
   const long n = (long)H * ((W + 1) / 2);
   long blocks = (n + 255) / 256;
   if (blocks > 2048) blocks = 2048;
-  if (dtype == SDHIP_F32) hipLaunchKernelGGL(double_left_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (float*)left, (float*)right, ld_img, seg, ld_seg, n_seg, disp, H, W);
-  else hipLaunchKernelGGL(double_left_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (bf16_t*)left, (bf16_t*)right, ld_img, seg, ld_seg, n_seg, disp, H, W);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(double_left_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (T*)left, (T*)right, ld_img, seg, ld_seg, n_seg, disp, H, W);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }

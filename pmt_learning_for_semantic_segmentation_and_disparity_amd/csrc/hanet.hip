@@ -147,11 +147,13 @@ int blocks_for(long total) { long b = (total + 255) / 256; return (int)(b > 4096
 extern "C" int sdhip_rowpool_max_fwd(const void* x, int ldx, void* y, int ldy, int* idx, int B, int H, int W, int C, int OH,
                                      int dtype, void* stream) {
   SDHIP_CHECK_ARG(x && y && idx && B > 0 && H > 0 && W > 0 && C > 0 && OH > 0, "rowpool_max_fwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "rowpool_max_fwd: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("rowpool_max_fwd", dtype);
   SDHIP_CHECK_ARG((long)H * W < (1L << 31), "rowpool_max_fwd: image too large");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == SDHIP_F32) hipLaunchKernelGGL(rowpool_max_fwd_kernel<float>, dim3(OH, B), dim3(256), 0, s, (const float*)x, ldx, (float*)y, ldy, idx, H, W, C, OH);
-  else hipLaunchKernelGGL(rowpool_max_fwd_kernel<bf16_t>, dim3(OH, B), dim3(256), 0, s, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, idx, H, W, C, OH);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(rowpool_max_fwd_kernel<T>, dim3(OH, B), dim3(256), 0, s, (const T*)x, ldx, (T*)y, ldy, idx, H, W, C, OH);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -159,20 +161,18 @@ extern "C" int sdhip_rowpool_max_fwd(const void* x, int ldx, void* y, int ldy, i
 extern "C" int sdhip_rowpool_max_bwd(const void* gy, int ldg, const int* idx, void* gx, int ldgx, int B, int H, int W, int C, int OH,
                                      int dtype, void* stream) {
   SDHIP_CHECK_ARG(gy && idx && gx && B > 0 && H > 0 && W > 0 && C > 0 && OH > 0 && ldg >= C && ldgx >= C, "rowpool_max_bwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "rowpool_max_bwd: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("rowpool_max_bwd", dtype);
   hipStream_t s = (hipStream_t)stream;
   const size_t es = dtype == SDHIP_BF16 ? 2 : 4;
   const long nz = (long)B * H * W * C;
-  if (ldgx == C) {   // dense: one contiguous clear
-    if (sdhip_zero_async(gx, (size_t)nz * es, s) != hipSuccess) SDHIP_FAIL(SDHIP_ERR_LAUNCH, "rowpool_max_bwd: memset failed");
-  } else if (dtype == SDHIP_F32) {
-    hipLaunchKernelGGL(zero_rows_kernel<float>, dim3(blocks_for(nz)), dim3(256), 0, s, (float*)gx, ldgx, C, nz);
-  } else {
-    hipLaunchKernelGGL(zero_rows_kernel<bf16_t>, dim3(blocks_for(nz)), dim3(256), 0, s, (bf16_t*)gx, ldgx, C, nz);
-  }
+  if (ldgx == C && sdhip_zero_async(gx, (size_t)nz * es, s) != hipSuccess)   // dense: one contiguous clear
+    SDHIP_FAIL(SDHIP_ERR_LAUNCH, "rowpool_max_bwd: memset failed");
   const long total = (long)B * C;
-  if (dtype == SDHIP_F32) hipLaunchKernelGGL(rowpool_max_bwd_kernel<float>, dim3(blocks_for(total)), dim3(256), 0, s, (const float*)gy, ldg, idx, (float*)gx, ldgx, H, W, C, OH, total);
-  else hipLaunchKernelGGL(rowpool_max_bwd_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, s, (const bf16_t*)gy, ldg, idx, (bf16_t*)gx, ldgx, H, W, C, OH, total);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (ldgx != C) hipLaunchKernelGGL(zero_rows_kernel<T>, dim3(blocks_for(nz)), dim3(256), 0, s, (T*)gx, ldgx, C, nz);
+    hipLaunchKernelGGL(rowpool_max_bwd_kernel<T>, dim3(blocks_for(total)), dim3(256), 0, s, (const T*)gy, ldg, idx, (T*)gx, ldgx, H, W, C, OH, total);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -180,11 +180,13 @@ extern "C" int sdhip_rowpool_max_bwd(const void* gy, int ldg, const int* idx, vo
 extern "C" int sdhip_mul_rows_fwd(const void* a, int lda, const void* att, int ldt, void* y, int ldy, int B, int H, int W, int C,
                                   int dtype, void* stream) {
   SDHIP_CHECK_ARG(a && att && y && B > 0 && H > 0 && W > 0 && C > 0, "mul_rows_fwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "mul_rows_fwd: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("mul_rows_fwd", dtype);
   hipStream_t s = (hipStream_t)stream;
   const long total = (long)B * H * W * C;
-  if (dtype == SDHIP_F32) hipLaunchKernelGGL(mul_rows_fwd_kernel<float>, dim3(blocks_for(total)), dim3(256), 0, s, (const float*)a, lda, (const float*)att, ldt, (float*)y, ldy, W, C, total);
-  else hipLaunchKernelGGL(mul_rows_fwd_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, s, (const bf16_t*)a, lda, (const bf16_t*)att, ldt, (bf16_t*)y, ldy, W, C, total);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(mul_rows_fwd_kernel<T>, dim3(blocks_for(total)), dim3(256), 0, s, (const T*)a, lda, (const T*)att, ldt, (T*)y, ldy, W, C, total);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -192,10 +194,13 @@ extern "C" int sdhip_mul_rows_fwd(const void* a, int lda, const void* att, int l
 extern "C" int sdhip_mul_rows_bwd(const void* g, int ldg, const void* a, int lda, const void* att, int ldt, void* ga, int ldga,
                                   void* gatt, int ldgt, int B, int H, int W, int C, int dtype, void* stream) {
   SDHIP_CHECK_ARG(g && a && att && ga && gatt && B > 0 && H > 0 && W > 0 && C > 0, "mul_rows_bwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "mul_rows_bwd: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("mul_rows_bwd", dtype);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == SDHIP_F32) hipLaunchKernelGGL(mul_rows_bwd_kernel<float>, dim3(B * H), dim3(256), 0, s, (const float*)g, ldg, (const float*)a, lda, (const float*)att, ldt, (float*)ga, ldga, (float*)gatt, ldgt, W, C);
-  else hipLaunchKernelGGL(mul_rows_bwd_kernel<bf16_t>, dim3(B * H), dim3(256), 0, s, (const bf16_t*)g, ldg, (const bf16_t*)a, lda, (const bf16_t*)att, ldt, (bf16_t*)ga, ldga, (bf16_t*)gatt, ldgt, W, C);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(mul_rows_bwd_kernel<T>, dim3(B * H), dim3(256), 0, s, (const T*)g, ldg, (const T*)a, lda, (const T*)att, ldt, (T*)ga, ldga,
+                       (T*)gatt, ldgt, W, C);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -203,11 +208,13 @@ extern "C" int sdhip_mul_rows_bwd(const void* g, int ldg, const void* a, int lda
 extern "C" int sdhip_dropout_channels(const void* x, int ldx, void* y, int ldy, const long* seed, long layer_id, int B, int L, int C,
                                       float p, int dtype, void* stream) {
   SDHIP_CHECK_ARG(x && y && seed && B > 0 && L > 0 && C > 0 && p >= 0.f && p < 1.f, "dropout_channels: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "dropout_channels: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("dropout_channels", dtype);
   hipStream_t s = (hipStream_t)stream;
   const long total = (long)B * L * C;
-  if (dtype == SDHIP_F32) hipLaunchKernelGGL(dropout_channels_kernel<float>, dim3(blocks_for(total)), dim3(256), 0, s, (const float*)x, ldx, (float*)y, ldy, seed, layer_id, L, C, p, total);
-  else hipLaunchKernelGGL(dropout_channels_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, s, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, seed, layer_id, L, C, p, total);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(dropout_channels_kernel<T>, dim3(blocks_for(total)), dim3(256), 0, s, (const T*)x, ldx, (T*)y, ldy, seed, layer_id, L, C, p, total);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }

@@ -517,7 +517,7 @@ extern "C" int sdhip_lovasz_softmax(const void* logits, int ldy, const float* ta
   SDHIP_CHECK_ARG(logits && target && loss && workspace && npix > 0 && C > 0 && ldy >= C && ldt >= C && (!grad || ldg >= C),
                   "lovasz_softmax: bad arguments");
   SDHIP_CHECK_ARG(npix < (1L << 31), "lovasz_softmax: more than 2^31 pixels");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "lovasz_softmax: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("lovasz_softmax", dtype);
   const Layout L = layout(npix, C);
   SDHIP_CHECK_ARG((size_t)workspace_bytes >= L.total, "lovasz_softmax: workspace too small (%ld < %zu)", workspace_bytes, L.total);
   hipStream_t s = (hipStream_t)stream;
@@ -532,8 +532,10 @@ extern "C" int sdhip_lovasz_softmax(const void* logits, int ldy, const float* ta
   SDHIP_CHECK_ARG(C <= 65535, "lovasz_softmax: more than 65535 classes");
   // (a kernel, not hipMemsetAsync: the step is replayed from a hipGraph, and everything in it is kept to kernel nodes)
   if (sdhip_zero_async(ws + L.counts, L.bfg - L.counts, s) != hipSuccess) SDHIP_FAIL(SDHIP_ERR_LAUNCH, "lovasz_softmax: clearing the counters failed");
-  if (dtype == SDHIP_F32) launch_lovasz_errors<float>(s, (const float*)logits, ldy, target, ldt, kv_a, counts, npix, C, ignore_void);
-  else launch_lovasz_errors<bf16_t>(s, (const bf16_t*)logits, ldy, target, ldt, kv_a, counts, npix, C, ignore_void);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    launch_lovasz_errors<T>(s, (const T*)logits, ldy, target, ldt, kv_a, counts, npix, C, ignore_void);
+  });
   // four stable passes over bits 0-7, 8-15, 16-23, 24-31 (keys < 2^30); a -> b -> a -> b -> a: the sorted arrays end in `a`
   const dim3 gs((unsigned)((L.cols + 3) / 4), (unsigned)C);
   for (int pass = 0; pass < 4; ++pass) {
@@ -547,10 +549,10 @@ extern "C" int sdhip_lovasz_softmax(const void* logits, int ldy, const float* ta
   hipLaunchKernelGGL(lovasz_fgcount_kernel, gc, dim3(256), 0, s, (const uint2*)kv_a, bfg, npix, L.nchunk);
   hipLaunchKernelGGL(lovasz_grad_kernel, gc, dim3(256), 0, s, (const uint2*)kv_a, (const unsigned int*)bfg,
                      (const unsigned int*)counts, gerr, lossc, npix, C, L.nchunk);
-  if (dtype == SDHIP_F32)
-    launch_lovasz_backward<float>(grid_stream(npix), s, (const float*)logits, ldy, target, ldt, gerr, counts, lossc, (float*)grad, ldg, loss, npix, C, weight, ignore_void);
-  else
-    launch_lovasz_backward<bf16_t>(grid_stream(npix), s, (const bf16_t*)logits, ldy, target, ldt, gerr, counts, lossc, (bf16_t*)grad, ldg, loss, npix, C, weight, ignore_void);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    launch_lovasz_backward<T>(grid_stream(npix), s, (const T*)logits, ldy, target, ldt, gerr, counts, lossc, (T*)grad, ldg, loss, npix, C, weight, ignore_void);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }

@@ -191,11 +191,11 @@ extern "C" int sdhip_step_metrics(const void* seg, int lds, const float* seg_tar
   if (seg_target) SDHIP_CHECK_ARG((Ct == L || Ct == L + 1) && ldt >= Ct,
                                   "step_metrics: target must hold labels or labels+1 (ignore) one-hot channels (L=%d Ct=%d ldt=%d)", L, Ct, ldt);
   if (disp) SDHIP_CHECK_ARG(disp_target, "step_metrics: disparity target missing");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "step_metrics: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("step_metrics", dtype);
   const long npix = (long)B * hw;
-  if (dtype == SDHIP_F32)
-    return launch_metrics<float>(seg, lds, seg_target, ldt, Ct, disp, disp_target, counts, sums, npix, hw, L, max_disp, mask_invalid,
-                                 nrep, rep_stride, (hipStream_t)stream);
-  return launch_metrics<bf16_t>(seg, lds, seg_target, ldt, Ct, disp, disp_target, counts, sums, npix, hw, L, max_disp, mask_invalid,
-                                nrep, rep_stride, (hipStream_t)stream);
+  return sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch_metrics<T>(seg, lds, seg_target, ldt, Ct, disp, disp_target, counts, sums, npix, hw, L, max_disp, mask_invalid,
+                             nrep, rep_stride, (hipStream_t)stream);
+  });
 }

@@ -274,30 +274,29 @@ __global__ __launch_bounds__(256) void dw_wgrad_sum_kernel(const float* __restri
   }
 }
 
-template <typename T>
-bool dw_vec(int C, int ld1, int ld2, const void* p1, const void* p2) {
-  constexpr int N = Chunk<T>::N;
-  return C % N == 0 && ld1 % N == 0 && ld2 % N == 0 && ((uintptr_t)p1 & 15) == 0 && ((uintptr_t)p2 & 15) == 0;
+// (k, stride) of the plain depthwise kernels -> template arguments (the entry points admit k = 3 / 5 and stride = 1 / 2 only)
+template <typename F>
+void dw_by_ks(int k, int stride, F&& f) {
+  sdhip_by_flag(k == 5, [&](auto K5) { sdhip_by_flag(stride == 2, [&](auto S2) {
+    f(std::integral_constant<int, K5() ? 5 : 3>{}, std::integral_constant<int, S2() ? 2 : 1>{});
+  }); });
 }
 
-template <typename T, bool VEC, int K, int S, bool BWD>
-void dw_launch(const void* src, int lds, const float* w, void* out, int ldo, double* stats, int sld, int nrep, float* pool,
-               int pool_parts, int B, int SH, int SW, int OH, int OW, int C, int ipg, hipStream_t s) {
-  const DwGeom dg = dw_geom(VEC ? C / Unit<T, VEC>::N : C);
-  const int nstrip = OH * ((OW + DW_R - 1) / DW_R);
-  dim3 grid((unsigned)sdhip_cdiv(nstrip, dg.ty), (unsigned)sdhip_cdiv(dg.units, dg.tx), (unsigned)B);
-  hipLaunchKernelGGL((dw_conv_kernel<T, VEC, K, S, BWD>), grid, dim3(256), 0, s, (const T*)src, lds, w, (T*)out, ldo, stats, sld,
-                     nrep, pool, pool_parts, SH, SW, OH, OW, C, ipg, dg);
-}
-
-template <typename T, bool BWD>
-void dw_dispatch(bool vec, int k, int stride, const void* src, int lds, const float* w, void* out, int ldo, double* stats, int sld,
-                 int nrep, float* pool, int pool_parts, int B, int SH, int SW, int OH, int OW, int C, int ipg, hipStream_t s) {
-#define DW_CASE(V, K, S) if (vec == V && k == K && stride == S) \
-    return dw_launch<T, V, K, S, BWD>(src, lds, w, out, ldo, stats, sld, nrep, pool, pool_parts, B, SH, SW, OH, OW, C, ipg, s)
-  DW_CASE(true, 3, 1); DW_CASE(true, 3, 2); DW_CASE(true, 5, 1); DW_CASE(true, 5, 2);
-  DW_CASE(false, 3, 1); DW_CASE(false, 3, 2); DW_CASE(false, 5, 1); DW_CASE(false, 5, 2);
-#undef DW_CASE
+// forward (bwd = false: src = x, out = y) and data gradient (bwd = true: src = gy, out = gx) are one kernel
+void dw_conv(bool bwd, int dtype, int k, int stride, const void* src, int lds, const float* w, void* out, int ldo, double* stats, int sld,
+             int nrep, float* pool, int pool_parts, int B, int SH, int SW, int OH, int OW, int C, int ipg, hipStream_t s) {
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {lds, ldo}, {src, out}), [&](auto V) { sdhip_by_flag(bwd, [&](auto BWD) {
+      dw_by_ks(k, stride, [&](auto K, auto S) {
+        const DwGeom dg = dw_geom(C / Unit<T, V()>::N);
+        const int nstrip = OH * ((OW + DW_R - 1) / DW_R);
+        dim3 grid((unsigned)sdhip_cdiv(nstrip, dg.ty), (unsigned)sdhip_cdiv(dg.units, dg.tx), (unsigned)B);
+        hipLaunchKernelGGL((dw_conv_kernel<T, V(), K(), S(), BWD()>), grid, dim3(256), 0, s, (const T*)src, lds, w, (T*)out, ldo, stats, sld,
+                           nrep, pool, pool_parts, SH, SW, OH, OW, C, ipg, dg);
+      });
+    }); });
+  });
 }
 
 inline int dw_out(int n, int k, int s) { return (n + 2 * ((k - 1) / 2) - k) / s + 1; }
@@ -310,30 +309,11 @@ inline int dw_wgrad_parts(int B, int H, int W, int C, int k, int stride) {
   return (int)(bx < 1 ? 1 : (bx > 256 ? 256 : bx));
 }
 
-template <typename T, bool VEC, int K, int S>
-void dw_wgrad_launch(const void* x, int ldx, const void* gy, int ldg, float* part, int nparts, int B, int H, int W, int Ho, int Wo,
-                     int C, hipStream_t s) {
-  const DwGeom dg = dw_geom(VEC ? C / Unit<T, VEC>::N : C);
-  dim3 grid((unsigned)nparts, (unsigned)sdhip_cdiv(dg.units, dg.tx), (unsigned)K);
-  hipLaunchKernelGGL((dw_wgrad_kernel<T, VEC, K, S>), grid, dim3(256), 0, s, (const T*)x, ldx, (const T*)gy, ldg, part, B, H, W, Ho,
-                     Wo, C, dg);
-}
-
-template <typename T>
-void dw_wgrad_dispatch(bool vec, int k, int stride, const void* x, int ldx, const void* gy, int ldg, float* part, int nparts, int B,
-                       int H, int W, int Ho, int Wo, int C, hipStream_t s) {
-#define DW_CASE(V, K, S) if (vec == V && k == K && stride == S) \
-    return dw_wgrad_launch<T, V, K, S>(x, ldx, gy, ldg, part, nparts, B, H, W, Ho, Wo, C, s)
-  DW_CASE(true, 3, 1); DW_CASE(true, 3, 2); DW_CASE(true, 5, 1); DW_CASE(true, 5, 2);
-  DW_CASE(false, 3, 1); DW_CASE(false, 3, 2); DW_CASE(false, 5, 1); DW_CASE(false, 5, 2);
-#undef DW_CASE
-}
-
 // pool slots of the forward: its strip-block count on the vector or the element-wise path, whichever is larger
 inline int dw_pool_parts(int H, int W, int C, int k, int stride, int dtype) {
   const int Ho = dw_out(H, k, stride), Wo = dw_out(W, k, stride);
   const int nstrip = Ho * ((Wo + DW_R - 1) / DW_R);
-  const int N = dtype == SDHIP_F32 ? 4 : 8;
+  const int N = sdhip_by_dtype(dtype, [](auto tag) { return Chunk<typename decltype(tag)::type>::N; });
   int parts = sdhip_cdiv(nstrip, dw_geom(C).ty);
   if (C % N == 0) {
     const int pv = sdhip_cdiv(nstrip, dw_geom(C / N).ty);
@@ -738,50 +718,25 @@ __global__ __launch_bounds__(256) void dwd_wgrad_kernel(const T* __restrict__ x,
   }
 }
 
-// the 16-byte path of the dilated kernels needs aligned strides and pointers only (the channel tail is masked)
-template <typename T>
-bool dwd_vec(int ld1, int ld2, int ld3, const void* p1, const void* p2, const void* p3) {
-  constexpr int N = Chunk<T>::N;
-  return ld1 % N == 0 && ld2 % N == 0 && ld3 % N == 0 && (((uintptr_t)p1 | (uintptr_t)p2 | (uintptr_t)p3) & 15) == 0;
-}
-
-template <typename T, bool VEC, bool BWD>
-void dwd_launch(const void* src, int lds, const float* w, const void* xm, int ldm, void* out, int ldo, double* stats, int sld,
-                int nrep, int B, int SH, int SW, int OH, int OW, int C, int S, int D, int in_relu, int ipg, hipStream_t s) {
-  constexpr int N = Unit<T, VEC>::N;
-  const DwGeom dg = dw_geom((C + N - 1) / N);
-  // pixels per thread: as many as leave ~2048 workgroups (8 per CU) to the launch, at most DWD_MAX_PIX
-  const long rows = sdhip_cdiv((long)OH * OW, dg.ty);
-  const long others = (long)sdhip_cdiv(dg.units, dg.tx) * B;
-  long pix = rows * others / 2048;
-  pix = pix < 1 ? 1 : (pix > DWD_MAX_PIX ? DWD_MAX_PIX : pix);
-  dim3 grid((unsigned)sdhip_cdiv(rows, pix), (unsigned)sdhip_cdiv(dg.units, dg.tx), (unsigned)B);
-  hipLaunchKernelGGL((dwd_conv_kernel<T, VEC, BWD>), grid, dim3(256), 0, s, (const T*)src, lds, w, (const T*)xm, ldm, (T*)out, ldo,
-                     stats, sld, nrep, SH, SW, OH, OW, C, S, D, in_relu, ipg, (int)pix, dg);
-}
-
-template <typename T, bool BWD>
-void dwd_dispatch(const void* src, int lds, const float* w, const void* xm, int ldm, void* out, int ldo, double* stats, int sld,
-                  int nrep, int B, int SH, int SW, int OH, int OW, int C, int S, int D, int in_relu, int ipg, hipStream_t s) {
-  if (dwd_vec<T>(lds, ldo, xm ? ldm : 0, src, out, xm))
-    dwd_launch<T, true, BWD>(src, lds, w, xm, ldm, out, ldo, stats, sld, nrep, B, SH, SW, OH, OW, C, S, D, in_relu, ipg, s);
-  else
-    dwd_launch<T, false, BWD>(src, lds, w, xm, ldm, out, ldo, stats, sld, nrep, B, SH, SW, OH, OW, C, S, D, in_relu, ipg, s);
-}
-
-template <typename T>
-void dwd_wgrad_dispatch(const void* x, int ldx, const void* gy, int ldg, float* part, int nparts, int B, int H, int W, int Ho,
-                        int Wo, int C, int S, int D, int in_relu, hipStream_t s) {
-  const bool vec = dwd_vec<T>(ldx, ldg, 0, x, gy, nullptr);
-  const int N = vec ? Chunk<T>::N : 1;
-  const DwGeom dg = dw_geom((C + N - 1) / N);
-  dim3 grid((unsigned)nparts, (unsigned)sdhip_cdiv(dg.units, dg.tx), 3u);
-  if (vec)
-    hipLaunchKernelGGL((dwd_wgrad_kernel<T, true>), grid, dim3(256), 0, s, (const T*)x, ldx, (const T*)gy, ldg, part, B, H, W, Ho, Wo,
-                       C, S, D, in_relu, dg);
-  else
-    hipLaunchKernelGGL((dwd_wgrad_kernel<T, false>), grid, dim3(256), 0, s, (const T*)x, ldx, (const T*)gy, ldg, part, B, H, W, Ho, Wo,
-                       C, S, D, in_relu, dg);
+// forward / data gradient of the dilated kernel.  Its 16-byte path needs aligned strides and pointers only (the channel tail
+// is masked): the C handed to sdhip_vec_ok is one that always divides.
+void dwd_conv(bool bwd, int dtype, const void* src, int lds, const float* w, const void* xm, int ldm, void* out, int ldo, double* stats,
+              int sld, int nrep, int B, int SH, int SW, int OH, int OW, int C, int S, int D, int in_relu, int ipg, hipStream_t s) {
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(0, {lds, ldo, xm ? ldm : 0}, {src, out, xm}), [&](auto V) { sdhip_by_flag(bwd, [&](auto BWD) {
+      constexpr int N = Unit<T, V()>::N;
+      const DwGeom dg = dw_geom((C + N - 1) / N);
+      // pixels per thread: as many as leave ~2048 workgroups (8 per CU) to the launch, at most DWD_MAX_PIX
+      const long rows = sdhip_cdiv((long)OH * OW, dg.ty);
+      const long others = (long)sdhip_cdiv(dg.units, dg.tx) * B;
+      long pix = rows * others / 2048;
+      pix = pix < 1 ? 1 : (pix > DWD_MAX_PIX ? DWD_MAX_PIX : pix);
+      dim3 grid((unsigned)sdhip_cdiv(rows, pix), (unsigned)sdhip_cdiv(dg.units, dg.tx), (unsigned)B);
+      hipLaunchKernelGGL((dwd_conv_kernel<T, V(), BWD()>), grid, dim3(256), 0, s, (const T*)src, lds, w, (const T*)xm, ldm, (T*)out, ldo,
+                         stats, sld, nrep, SH, SW, OH, OW, C, S, D, in_relu, ipg, (int)pix, dg);
+    }); });
+  });
 }
 
 inline int dwd_out(int n, int stride) { return (n - 1) / stride + 1; }
@@ -812,17 +767,14 @@ extern "C" int sdhip_dw_dil_conv_fwd(const void* x, int ldx, const float* w, voi
   SDHIP_CHECK_ARG(x && w && y, "dw_dil_conv_fwd: null pointer");
   SDHIP_CHECK_ARG(dwd_shape_ok(B, H, W, C, stride, dil) && ldx >= C && ldy >= C, "dw_dil_conv_fwd: bad shape/strides (stride %d, dil %d)",
                   stride, dil);
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "dw_dil_conv_fwd: dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("dw_dil_conv_fwd", dtype);
   SDHIP_CHECK_ARG(groups > 0 && B % groups == 0, "dw_dil_conv_fwd: groups %d does not divide B %d", groups, B);
   if (nrep < 1) nrep = 1;
   if (sld <= 0) sld = C;
   SDHIP_CHECK_ARG(!stats || sld >= C, "dw_dil_conv_fwd: statistics stride");
   const int Ho = dwd_out(H, stride), Wo = dwd_out(W, stride);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == SDHIP_F32)
-    dwd_dispatch<float, false>(x, ldx, w, nullptr, 0, y, ldy, stats, sld, nrep, B, H, W, Ho, Wo, C, stride, dil, in_relu != 0, B / groups, s);
-  else
-    dwd_dispatch<bf16_t, false>(x, ldx, w, nullptr, 0, y, ldy, stats, sld, nrep, B, H, W, Ho, Wo, C, stride, dil, in_relu != 0, B / groups, s);
+  dwd_conv(false, dtype, x, ldx, w, nullptr, 0, y, ldy, stats, sld, nrep, B, H, W, Ho, Wo, C, stride, dil, in_relu != 0, B / groups, s);
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -832,13 +784,10 @@ extern "C" int sdhip_dw_dil_conv_dgrad(const void* gy, int ldg, const float* w, 
   SDHIP_CHECK_ARG(gy && w && gx, "dw_dil_conv_dgrad: null pointer");
   SDHIP_CHECK_ARG(dwd_shape_ok(B, H, W, C, stride, dil) && ldg >= C && ldgx >= C && (!x || ldx >= C),
                   "dw_dil_conv_dgrad: bad shape/strides (stride %d, dil %d)", stride, dil);
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "dw_dil_conv_dgrad: dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("dw_dil_conv_dgrad", dtype);
   const int Ho = dwd_out(H, stride), Wo = dwd_out(W, stride);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == SDHIP_F32)
-    dwd_dispatch<float, true>(gy, ldg, w, x, ldx, gx, ldgx, nullptr, 0, 1, B, Ho, Wo, H, W, C, stride, dil, 0, 1, s);
-  else
-    dwd_dispatch<bf16_t, true>(gy, ldg, w, x, ldx, gx, ldgx, nullptr, 0, 1, B, Ho, Wo, H, W, C, stride, dil, 0, 1, s);
+  dwd_conv(true, dtype, gy, ldg, w, x, ldx, gx, ldgx, nullptr, 0, 1, B, Ho, Wo, H, W, C, stride, dil, 0, 1, s);
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -848,15 +797,21 @@ extern "C" int sdhip_dw_dil_conv_wgrad(const void* x, int ldx, const void* gy, i
   SDHIP_CHECK_ARG(x && gy && dw && part, "dw_dil_conv_wgrad: null pointer");
   SDHIP_CHECK_ARG(dwd_shape_ok(B, H, W, C, stride, dil) && ldx >= C && ldg >= C, "dw_dil_conv_wgrad: bad shape/strides (stride %d, dil %d)",
                   stride, dil);
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "dw_dil_conv_wgrad: dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("dw_dil_conv_wgrad", dtype);
   SDHIP_CHECK_ARG(nparts == dwd_wgrad_parts(B, H, W, C, stride), "dw_dil_conv_wgrad: %d partial slots, sdhip_dw_dil_wgrad_parts says %d",
                   nparts, dwd_wgrad_parts(B, H, W, C, stride));
   const int Ho = dwd_out(H, stride), Wo = dwd_out(W, stride);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == SDHIP_F32)
-    dwd_wgrad_dispatch<float>(x, ldx, gy, ldg, part, nparts, B, H, W, Ho, Wo, C, stride, dil, in_relu != 0, s);
-  else
-    dwd_wgrad_dispatch<bf16_t>(x, ldx, gy, ldg, part, nparts, B, H, W, Ho, Wo, C, stride, dil, in_relu != 0, s);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(0, {ldx, ldg}, {x, gy}), [&](auto V) {   // (channel tail masked, as in dwd_conv)
+      constexpr int N = Unit<T, V()>::N;
+      const DwGeom dg = dw_geom((C + N - 1) / N);
+      dim3 grid((unsigned)nparts, (unsigned)sdhip_cdiv(dg.units, dg.tx), 3u);
+      hipLaunchKernelGGL((dwd_wgrad_kernel<T, V()>), grid, dim3(256), 0, s, (const T*)x, ldx, (const T*)gy, ldg, part, B, H, W, Ho, Wo,
+                         C, stride, dil, in_relu != 0, dg);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   hipLaunchKernelGGL(dw_wgrad_sum_kernel, dim3((unsigned)sdhip_cdiv(9L * C, 32)), dim3(256), 0, s, part, nparts, dw, 9, C);
   SDHIP_LAUNCH_CHECK();
@@ -878,7 +833,7 @@ extern "C" int sdhip_dw_conv_fwd(const void* x, int ldx, const float* w, void* y
   SDHIP_CHECK_ARG(x && w && y, "dw_conv_fwd: null pointer");
   SDHIP_CHECK_ARG((k == 3 || k == 5) && (stride == 1 || stride == 2), "dw_conv_fwd: k=%d stride=%d (3/5, 1/2 only)", k, stride);
   SDHIP_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && ldx >= C && ldy >= C, "dw_conv_fwd: bad shape/strides");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "dw_conv_fwd: dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("dw_conv_fwd", dtype);
   SDHIP_CHECK_ARG(groups > 0 && B % groups == 0, "dw_conv_fwd: groups %d does not divide B %d", groups, B);
   if (nrep < 1) nrep = 1;
   if (sld <= 0) sld = C;
@@ -887,12 +842,7 @@ extern "C" int sdhip_dw_conv_fwd(const void* x, int ldx, const float* w, void* y
                   dw_pool_parts(H, W, C, k, stride, dtype));
   const int Ho = dw_out(H, k, stride), Wo = dw_out(W, k, stride);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == SDHIP_F32)
-    dw_dispatch<float, false>(dw_vec<float>(C, ldx, ldy, x, y), k, stride, x, ldx, w, y, ldy, stats, sld, nrep, pool, pool_parts, B, H,
-                              W, Ho, Wo, C, B / groups, s);
-  else
-    dw_dispatch<bf16_t, false>(dw_vec<bf16_t>(C, ldx, ldy, x, y), k, stride, x, ldx, w, y, ldy, stats, sld, nrep, pool, pool_parts, B,
-                               H, W, Ho, Wo, C, B / groups, s);
+  dw_conv(false, dtype, k, stride, x, ldx, w, y, ldy, stats, sld, nrep, pool, pool_parts, B, H, W, Ho, Wo, C, B / groups, s);
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -902,15 +852,10 @@ extern "C" int sdhip_dw_conv_dgrad(const void* gy, int ldg, const float* w, void
   SDHIP_CHECK_ARG(gy && w && gx, "dw_conv_dgrad: null pointer");
   SDHIP_CHECK_ARG((k == 3 || k == 5) && (stride == 1 || stride == 2), "dw_conv_dgrad: k=%d stride=%d (3/5, 1/2 only)", k, stride);
   SDHIP_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && ldg >= C && ldgx >= C, "dw_conv_dgrad: bad shape/strides");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "dw_conv_dgrad: dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("dw_conv_dgrad", dtype);
   const int Ho = dw_out(H, k, stride), Wo = dw_out(W, k, stride);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == SDHIP_F32)
-    dw_dispatch<float, true>(dw_vec<float>(C, ldg, ldgx, gy, gx), k, stride, gy, ldg, w, gx, ldgx, nullptr, 0, 1, nullptr, 0, B, Ho,
-                             Wo, H, W, C, 1, s);
-  else
-    dw_dispatch<bf16_t, true>(dw_vec<bf16_t>(C, ldg, ldgx, gy, gx), k, stride, gy, ldg, w, gx, ldgx, nullptr, 0, 1, nullptr, 0, B,
-                              Ho, Wo, H, W, C, 1, s);
+  dw_conv(true, dtype, k, stride, gy, ldg, w, gx, ldgx, nullptr, 0, 1, nullptr, 0, B, Ho, Wo, H, W, C, 1, s);
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -920,15 +865,20 @@ extern "C" int sdhip_dw_conv_wgrad(const void* x, int ldx, const void* gy, int l
   SDHIP_CHECK_ARG(x && gy && dw && part, "dw_conv_wgrad: null pointer");
   SDHIP_CHECK_ARG((k == 3 || k == 5) && (stride == 1 || stride == 2), "dw_conv_wgrad: k=%d stride=%d (3/5, 1/2 only)", k, stride);
   SDHIP_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && ldx >= C && ldg >= C, "dw_conv_wgrad: bad shape/strides");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "dw_conv_wgrad: dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("dw_conv_wgrad", dtype);
   SDHIP_CHECK_ARG(nparts == dw_wgrad_parts(B, H, W, C, k, stride), "dw_conv_wgrad: %d partial slots, sdhip_dw_wgrad_parts says %d",
                   nparts, dw_wgrad_parts(B, H, W, C, k, stride));
   const int Ho = dw_out(H, k, stride), Wo = dw_out(W, k, stride);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == SDHIP_F32)
-    dw_wgrad_dispatch<float>(dw_vec<float>(C, ldx, ldg, x, gy), k, stride, x, ldx, gy, ldg, part, nparts, B, H, W, Ho, Wo, C, s);
-  else
-    dw_wgrad_dispatch<bf16_t>(dw_vec<bf16_t>(C, ldx, ldg, x, gy), k, stride, x, ldx, gy, ldg, part, nparts, B, H, W, Ho, Wo, C, s);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {ldx, ldg}, {x, gy}), [&](auto V) { dw_by_ks(k, stride, [&](auto K, auto S) {
+      const DwGeom dg = dw_geom(C / Unit<T, V()>::N);
+      dim3 grid((unsigned)nparts, (unsigned)sdhip_cdiv(dg.units, dg.tx), (unsigned)K());
+      hipLaunchKernelGGL((dw_wgrad_kernel<T, V(), K(), S()>), grid, dim3(256), 0, s, (const T*)x, ldx, (const T*)gy, ldg, part, B, H, W, Ho,
+                         Wo, C, dg);
+    }); });
+  });
   SDHIP_LAUNCH_CHECK();
   hipLaunchKernelGGL(dw_wgrad_sum_kernel, dim3((unsigned)sdhip_cdiv((long)k * k * C, 32)), dim3(256), 0, s, part, nparts, dw, k * k, C);
   SDHIP_LAUNCH_CHECK();
@@ -965,22 +915,18 @@ extern "C" int sdhip_se_scale_bwd(const void* gy, int ldg, const void* x, int ld
   SDHIP_CHECK_ARG(gy && x && gx && s, "se_scale_bwd: null pointer");
   SDHIP_CHECK_ARG(B > 0 && C > 0 && npix_img > 0 && ldg >= C && ldx >= C && ldgx >= C, "se_scale_bwd: bad shape/strides");
   SDHIP_CHECK_ARG(act == 0 || act == 1 || act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID, "se_scale_bwd: activation %d", act);
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "se_scale_bwd: dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("se_scale_bwd", dtype);
   hipStream_t st = (hipStream_t)stream;
-#define SE_LAUNCH(T, V) do { \
-    const DwGeom dg = dw_geom(V ? C / Chunk<T>::N : C); \
-    long bx = sdhip_cdiv(npix_img, (long)dg.ty * 4); if (bx > 256) bx = 256; \
-    dim3 grid((unsigned)bx, (unsigned)sdhip_cdiv(dg.units, dg.tx), (unsigned)B); \
-    hipLaunchKernelGGL((se_scale_bwd_kernel<T, V>), grid, dim3(256), 0, st, (const T*)gy, ldg, (const T*)x, ldx, (T*)gx, ldgx, s, gadd, \
-                       npix_img, C, act, dg); } while (0)
-  if (dtype == SDHIP_F32) {
-    const bool v = C % 4 == 0 && ldg % 4 == 0 && ldx % 4 == 0 && ldgx % 4 == 0 && (((uintptr_t)gy | (uintptr_t)x | (uintptr_t)gx) & 15) == 0;
-    if (v) SE_LAUNCH(float, true); else SE_LAUNCH(float, false);
-  } else {
-    const bool v = C % 8 == 0 && ldg % 8 == 0 && ldx % 8 == 0 && ldgx % 8 == 0 && (((uintptr_t)gy | (uintptr_t)x | (uintptr_t)gx) & 15) == 0;
-    if (v) SE_LAUNCH(bf16_t, true); else SE_LAUNCH(bf16_t, false);
-  }
-#undef SE_LAUNCH
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {ldg, ldx, ldgx}, {gy, x, gx}), [&](auto V) {
+      const DwGeom dg = dw_geom(C / Unit<T, V()>::N);
+      long bx = sdhip_cdiv(npix_img, (long)dg.ty * 4); if (bx > 256) bx = 256;
+      dim3 grid((unsigned)bx, (unsigned)sdhip_cdiv(dg.units, dg.tx), (unsigned)B);
+      hipLaunchKernelGGL((se_scale_bwd_kernel<T, V()>), grid, dim3(256), 0, st, (const T*)gy, ldg, (const T*)x, ldx, (T*)gx, ldgx, s, gadd,
+                         npix_img, C, act, dg);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }

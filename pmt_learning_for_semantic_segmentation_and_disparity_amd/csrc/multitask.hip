@@ -251,22 +251,16 @@ inline bool mt_rows_ok(int C, int ldy, int es, const void* logits) {
 extern "C" int sdhip_mt_seg_fwd(const void* logits, int ldy, const int64_t* labels, const float* log_var, float* map, float* lse,
                                 double* sum, float* mean, long npix, int C, int ignore_index, float sum_weight, int dtype, void* stream) {
   SDHIP_CHECK_ARG(logits && labels && log_var && map && lse && sum && npix > 0 && C > 0 && ldy >= C, "mt_seg_fwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "mt_seg_fwd: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("mt_seg_fwd", dtype);
   hipStream_t s = (hipStream_t)stream;
   const long* lab = reinterpret_cast<const long*>(labels);
-  const int es = dtype == SDHIP_F32 ? 4 : 2;
-  if (mt_rows_ok(C, ldy, es, logits)) {
-    const size_t lds = rows_lds_bytes(ldy, es);
-    if (dtype == SDHIP_F32)
-      hipLaunchKernelGGL(mt_seg_fwd_rows_kernel<float>, mt_rows_grid(npix), dim3(256), lds, s, (const float*)logits, ldy, lab, log_var, map, lse, sum, npix, C, ignore_index, sum_weight);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (mt_rows_ok(C, ldy, sizeof(T), logits))
+      hipLaunchKernelGGL(mt_seg_fwd_rows_kernel<T>, mt_rows_grid(npix), dim3(256), rows_lds_bytes(ldy, sizeof(T)), s, (const T*)logits, ldy, lab, log_var, map, lse, sum, npix, C, ignore_index, sum_weight);
     else
-      hipLaunchKernelGGL(mt_seg_fwd_rows_kernel<bf16_t>, mt_rows_grid(npix), dim3(256), lds, s, (const bf16_t*)logits, ldy, lab, log_var, map, lse, sum, npix, C, ignore_index, sum_weight);
-  } else {
-    if (dtype == SDHIP_F32)
-      hipLaunchKernelGGL(mt_seg_fwd_kernel<float>, mt_grid(npix), dim3(256), 0, s, (const float*)logits, ldy, lab, log_var, map, lse, sum, npix, C, ignore_index, sum_weight);
-    else
-      hipLaunchKernelGGL(mt_seg_fwd_kernel<bf16_t>, mt_grid(npix), dim3(256), 0, s, (const bf16_t*)logits, ldy, lab, log_var, map, lse, sum, npix, C, ignore_index, sum_weight);
-  }
+      hipLaunchKernelGGL(mt_seg_fwd_kernel<T>, mt_grid(npix), dim3(256), 0, s, (const T*)logits, ldy, lab, log_var, map, lse, sum, npix, C, ignore_index, sum_weight);
+  });
   if (mean) hipLaunchKernelGGL(mt_mean_kernel, dim3(1), dim3(64), 0, s, sum, mean);
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
@@ -277,24 +271,19 @@ extern "C" int sdhip_mt_seg_bwd(const void* logits, int ldy, const int64_t* labe
                                 float* grad_log_var, long npix, int C, int ignore_index, int dtype, void* stream) {
   SDHIP_CHECK_ARG(logits && labels && lse && log_var && npix > 0 && C > 0 && ldy >= C && (!grad || ldg >= C) && g_stride >= 0,
                   "mt_seg_bwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "mt_seg_bwd: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("mt_seg_bwd", dtype);
   if (!grad && !grad_log_var) return SDHIP_OK;
   hipStream_t s = (hipStream_t)stream;
   const long* lab = reinterpret_cast<const long*>(labels);
-  const int es = dtype == SDHIP_F32 ? 4 : 2;
-  if (mt_rows_ok(C, ldy, es, logits)) {
-    const size_t lds = rows_lds_bytes(ldy, es);
-    const int dense = grad && ldy == C && ldg == C && (((uintptr_t)grad) & 3) == 0;
-    if (dtype == SDHIP_F32)
-      hipLaunchKernelGGL(mt_seg_bwd_rows_kernel<float>, mt_rows_grid(npix), dim3(256), lds, s, (const float*)logits, ldy, lab, lse, log_var, gmap, g_stride, gmean, gmean_scale, (float*)grad, ldg, grad_log_var, npix, C, ignore_index, dense);
-    else
-      hipLaunchKernelGGL(mt_seg_bwd_rows_kernel<bf16_t>, mt_rows_grid(npix), dim3(256), lds, s, (const bf16_t*)logits, ldy, lab, lse, log_var, gmap, g_stride, gmean, gmean_scale, (bf16_t*)grad, ldg, grad_log_var, npix, C, ignore_index, dense);
-  } else {
-    if (dtype == SDHIP_F32)
-      hipLaunchKernelGGL(mt_seg_bwd_kernel<float>, mt_grid(npix), dim3(256), 0, s, (const float*)logits, ldy, lab, lse, log_var, gmap, g_stride, gmean, gmean_scale, (float*)grad, ldg, grad_log_var, npix, C, ignore_index);
-    else
-      hipLaunchKernelGGL(mt_seg_bwd_kernel<bf16_t>, mt_grid(npix), dim3(256), 0, s, (const bf16_t*)logits, ldy, lab, lse, log_var, gmap, g_stride, gmean, gmean_scale, (bf16_t*)grad, ldg, grad_log_var, npix, C, ignore_index);
-  }
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (mt_rows_ok(C, ldy, sizeof(T), logits)) {
+      const int dense = grad && ldy == C && ldg == C && (((uintptr_t)grad) & 3) == 0;
+      hipLaunchKernelGGL(mt_seg_bwd_rows_kernel<T>, mt_rows_grid(npix), dim3(256), rows_lds_bytes(ldy, sizeof(T)), s, (const T*)logits, ldy, lab, lse, log_var, gmap, g_stride, gmean, gmean_scale, (T*)grad, ldg, grad_log_var, npix, C, ignore_index, dense);
+    } else {
+      hipLaunchKernelGGL(mt_seg_bwd_kernel<T>, mt_grid(npix), dim3(256), 0, s, (const T*)logits, ldy, lab, lse, log_var, gmap, g_stride, gmean, gmean_scale, (T*)grad, ldg, grad_log_var, npix, C, ignore_index);
+    }
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -302,12 +291,12 @@ extern "C" int sdhip_mt_seg_bwd(const void* logits, int ldy, const int64_t* labe
 extern "C" int sdhip_mt_l1_fwd(const void* pred, int ldp, const float* target, const float* log_var, float* map, double* sum,
                                float* mean, long n, float sum_weight, int dtype, void* stream) {
   SDHIP_CHECK_ARG(pred && target && log_var && map && sum && n > 0 && ldp >= 1, "mt_l1_fwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "mt_l1_fwd: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("mt_l1_fwd", dtype);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == SDHIP_F32)
-    hipLaunchKernelGGL(mt_l1_fwd_kernel<float>, mt_grid(n), dim3(256), 0, s, (const float*)pred, ldp, target, log_var, map, sum, n, sum_weight);
-  else
-    hipLaunchKernelGGL(mt_l1_fwd_kernel<bf16_t>, mt_grid(n), dim3(256), 0, s, (const bf16_t*)pred, ldp, target, log_var, map, sum, n, sum_weight);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(mt_l1_fwd_kernel<T>, mt_grid(n), dim3(256), 0, s, (const T*)pred, ldp, target, log_var, map, sum, n, sum_weight);
+  });
   if (mean) hipLaunchKernelGGL(mt_mean_kernel, dim3(1), dim3(64), 0, s, sum, mean);
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
@@ -317,13 +306,13 @@ extern "C" int sdhip_mt_l1_bwd(const void* pred, int ldp, const float* target, c
                                const float* gmean, float gmean_scale, void* grad, int ldg, float* grad_log_var, long n, int dtype,
                                void* stream) {
   SDHIP_CHECK_ARG(pred && target && log_var && n > 0 && ldp >= 1 && (!grad || ldg >= 1) && g_stride >= 0, "mt_l1_bwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "mt_l1_bwd: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("mt_l1_bwd", dtype);
   if (!grad && !grad_log_var) return SDHIP_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == SDHIP_F32)
-    hipLaunchKernelGGL(mt_l1_bwd_kernel<float>, mt_grid(n), dim3(256), 0, s, (const float*)pred, ldp, target, log_var, gmap, g_stride, gmean, gmean_scale, (float*)grad, ldg, grad_log_var, n);
-  else
-    hipLaunchKernelGGL(mt_l1_bwd_kernel<bf16_t>, mt_grid(n), dim3(256), 0, s, (const bf16_t*)pred, ldp, target, log_var, gmap, g_stride, gmean, gmean_scale, (bf16_t*)grad, ldg, grad_log_var, n);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(mt_l1_bwd_kernel<T>, mt_grid(n), dim3(256), 0, s, (const T*)pred, ldp, target, log_var, gmap, g_stride, gmean, gmean_scale, (T*)grad, ldg, grad_log_var, n);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }

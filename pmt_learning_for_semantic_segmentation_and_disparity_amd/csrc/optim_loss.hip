@@ -234,7 +234,7 @@ extern "C" int sdhip_sgd_step(float* params, const float* grads, float* momentum
 extern "C" int sdhip_ce_loss(const void* logits, int ldy, const float* target, int ldt, void* grad, int ldg, double* loss,
                              long npix, int C, float weight, int dtype, void* stream) {
   SDHIP_CHECK_ARG(logits && target && loss && npix > 0 && C > 0 && ldy >= C && ldt >= C && (!grad || ldg >= C), "ce_loss: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "ce_loss: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("ce_loss", dtype);
   const float wn = weight / (float)npix;
   hipStream_t s = (hipStream_t)stream;
   const int es = dtype == SDHIP_F32 ? 4 : 2;
@@ -242,17 +242,17 @@ extern "C" int sdhip_ce_loss(const void* logits, int ldy, const float* target, i
   if (C > 4 && C <= 64 && by + bt + bg <= 60 * 1024 && ((uintptr_t)logits & 3) == 0 && (!grad || ((uintptr_t)grad & 3) == 0)) {
     long b = (npix + 255) / 256;
     if (b > 768) b = 768;
-    if (dtype == SDHIP_F32)
-      hipLaunchKernelGGL(ce_rows_kernel<float>, dim3((unsigned)b), dim3(256), by + bt + bg, s, (const float*)logits, ldy, target, ldt, (float*)grad, ldg, loss, npix, C, wn, (int)by, (int)(by + bt));
-    else
-      hipLaunchKernelGGL(ce_rows_kernel<bf16_t>, dim3((unsigned)b), dim3(256), by + bt + bg, s, (const bf16_t*)logits, ldy, target, ldt, (bf16_t*)grad, ldg, loss, npix, C, wn, (int)by, (int)(by + bt));
+    sdhip_by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(ce_rows_kernel<T>, dim3((unsigned)b), dim3(256), by + bt + bg, s, (const T*)logits, ldy, target, ldt, (T*)grad, ldg, loss, npix, C, wn, (int)by, (int)(by + bt));
+    });
     SDHIP_LAUNCH_CHECK();
     return SDHIP_OK;
   }
-  if (dtype == SDHIP_F32)
-    hipLaunchKernelGGL(ce_kernel<float>, grid_loss(npix), dim3(256), 0, s, (const float*)logits, ldy, target, ldt, (float*)grad, ldg, loss, npix, C, wn);
-  else
-    hipLaunchKernelGGL(ce_kernel<bf16_t>, grid_loss(npix), dim3(256), 0, s, (const bf16_t*)logits, ldy, target, ldt, (bf16_t*)grad, ldg, loss, npix, C, wn);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(ce_kernel<T>, grid_loss(npix), dim3(256), 0, s, (const T*)logits, ldy, target, ldt, (T*)grad, ldg, loss, npix, C, wn);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -260,12 +260,12 @@ extern "C" int sdhip_ce_loss(const void* logits, int ldy, const float* target, i
 extern "C" int sdhip_l1_loss(const void* pred, const float* target, void* grad, double* loss, long n, float weight,
                              int mask_nonpositive, int dtype, void* stream) {
   SDHIP_CHECK_ARG(pred && target && loss && n > 0, "l1_loss: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "l1_loss: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("l1_loss", dtype);
   const float wn = weight / (float)n;
-  if (dtype == SDHIP_F32)
-    hipLaunchKernelGGL(l1_kernel<float>, grid_loss(n), dim3(256), 0, (hipStream_t)stream, (const float*)pred, target, (float*)grad, loss, n, wn, mask_nonpositive);
-  else
-    hipLaunchKernelGGL(l1_kernel<bf16_t>, grid_loss(n), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred, target, (bf16_t*)grad, loss, n, wn, mask_nonpositive);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(l1_kernel<T>, grid_loss(n), dim3(256), 0, (hipStream_t)stream, (const T*)pred, target, (T*)grad, loss, n, wn, mask_nonpositive);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -292,12 +292,12 @@ __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, T
 
 extern "C" int sdhip_dropout(const void* x, void* y, const long* seed, long layer_id, long n, float p, int dtype, void* stream) {
   SDHIP_CHECK_ARG(x && y && seed && n > 0 && p >= 0.f && p < 1.f, "dropout: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "dropout: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("dropout", dtype);
   const float scale = 1.f / (1.f - p);
-  if (dtype == SDHIP_F32)
-    hipLaunchKernelGGL(dropout_kernel<float>, grid_for(n), dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, seed, layer_id, n, p, scale);
-  else
-    hipLaunchKernelGGL(dropout_kernel<bf16_t>, grid_for(n), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, seed, layer_id, n, p, scale);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(dropout_kernel<T>, grid_for(n), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, seed, layer_id, n, p, scale);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -331,9 +331,11 @@ __global__ __launch_bounds__(256) void log_softmax_bwd_kernel(const T* __restric
 
 extern "C" int sdhip_log_softmax_fwd(const void* x, int ldx, void* y, int ldy, long npix, int C, int dtype, void* stream) {
   SDHIP_CHECK_ARG(x && y && npix > 0 && C > 0 && ldx >= C && ldy >= C, "log_softmax_fwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "log_softmax_fwd: unknown dtype %d", dtype);
-  if (dtype == SDHIP_F32) hipLaunchKernelGGL(log_softmax_fwd_kernel<float>, grid_for(npix), dim3(256), 0, (hipStream_t)stream, (const float*)x, ldx, (float*)y, ldy, npix, C);
-  else hipLaunchKernelGGL(log_softmax_fwd_kernel<bf16_t>, grid_for(npix), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, npix, C);
+  SDHIP_CHECK_DTYPE("log_softmax_fwd", dtype);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(log_softmax_fwd_kernel<T>, grid_for(npix), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, (T*)y, ldy, npix, C);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -341,9 +343,11 @@ extern "C" int sdhip_log_softmax_fwd(const void* x, int ldx, void* y, int ldy, l
 extern "C" int sdhip_log_softmax_bwd(const void* gy, int ldg, const void* y, int ldy, void* gx, int ldgx, long npix, int C,
                                      int dtype, void* stream) {
   SDHIP_CHECK_ARG(gy && y && gx && npix > 0 && C > 0 && ldg >= C && ldy >= C && ldgx >= C, "log_softmax_bwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "log_softmax_bwd: unknown dtype %d", dtype);
-  if (dtype == SDHIP_F32) hipLaunchKernelGGL(log_softmax_bwd_kernel<float>, grid_for(npix), dim3(256), 0, (hipStream_t)stream, (const float*)gy, ldg, (const float*)y, ldy, (float*)gx, ldgx, npix, C);
-  else hipLaunchKernelGGL(log_softmax_bwd_kernel<bf16_t>, grid_for(npix), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)gy, ldg, (const bf16_t*)y, ldy, (bf16_t*)gx, ldgx, npix, C);
+  SDHIP_CHECK_DTYPE("log_softmax_bwd", dtype);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(log_softmax_bwd_kernel<T>, grid_for(npix), dim3(256), 0, (hipStream_t)stream, (const T*)gy, ldg, (const T*)y, ldy, (T*)gx, ldgx, npix, C);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }

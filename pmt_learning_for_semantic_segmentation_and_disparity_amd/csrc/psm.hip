@@ -21,15 +21,6 @@ inline dim3 grid_for(long items) {
   return dim3((unsigned)b);
 }
 
-template <typename T>
-bool vec_ok(int C, std::initializer_list<int> lds, std::initializer_list<const void*> ptrs) {
-  const int n = Chunk<T>::N;
-  if (C % n) return false;
-  for (int l : lds) if (l % n) return false;
-  for (const void* p : ptrs) if (p && ((uintptr_t)p & 15)) return false;
-  return true;
-}
-
 // dense[n,d,h,w,:] <-> stuffed[n, d*sd, h*s, w*s, :]   (SCATTER: dense -> stuffed, stuffed pre-zeroed; else gather)
 template <typename T, bool VEC, bool SCATTER>
 __global__ __launch_bounds__(256) void stuff_kernel(const T* __restrict__ src, T* __restrict__ dst, Vol dense, Vol stuffed, int sd, int s) {
@@ -439,7 +430,7 @@ __global__ void f32_to_T_kernel(const float* __restrict__ src, T* __restrict__ d
 extern "C" int sdhip_stuff(const void* src, int lds_, void* dst, int ldd, int N, int D, int H, int W, int C,
                            int sd, int s, int scatter, int dtype, void* stream) {
   SDHIP_CHECK_ARG(src && dst && N > 0 && D > 0 && H > 0 && W > 0 && C > 0 && sd >= 1 && s >= 1, "stuff: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "stuff: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("stuff", dtype);
   const int Ds = (D - 1) * sd + 1, Hs = (H - 1) * s + 1, Ws = (W - 1) * s + 1;
   hipStream_t st = (hipStream_t)stream;
   // scatter: src dense (ld lds_), dst stuffed (ld ldd, zeroed here);  gather: src stuffed (ld lds_), dst dense (ld ldd)
@@ -451,11 +442,12 @@ extern "C" int sdhip_stuff(const void* src, int lds_, void* dst, int ldd, int N,
     SDHIP_CHECK_ARG(ldd == C, "stuff: the zero-stuffed output must be dense");
     if (sdhip_zero_async(dst, (size_t)N * Ds * Hs * Ws * C * es, st) != hipSuccess) SDHIP_FAIL(SDHIP_ERR_LAUNCH, "stuff: memset failed");
   }
-#define GO(T, V) do { if (scatter) hipLaunchKernelGGL((stuff_kernel<T, V, true>), grid_for(np * (V ? C / Chunk<T>::N : C)), dim3(256), 0, st, (const T*)src, (T*)dst, dense, stuffed, sd, s); \
-                      else hipLaunchKernelGGL((stuff_kernel<T, V, false>), grid_for(np * (V ? C / Chunk<T>::N : C)), dim3(256), 0, st, (const T*)src, (T*)dst, dense, stuffed, sd, s); } while (0)
-  if (dtype == SDHIP_F32) { if (vec_ok<float>(C, {lds_, ldd}, {src, dst})) GO(float, true); else GO(float, false); }
-  else { if (vec_ok<bf16_t>(C, {lds_, ldd}, {src, dst})) GO(bf16_t, true); else GO(bf16_t, false); }
-#undef GO
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {lds_, ldd}, {src, dst}), [&](auto V) { sdhip_by_flag(scatter != 0, [&](auto SC) {
+      hipLaunchKernelGGL((stuff_kernel<T, V(), SC()>), grid_for(np * (C / Unit<T, V()>::N)), dim3(256), 0, st, (const T*)src, (T*)dst, dense, stuffed, sd, s);
+    }); });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -463,16 +455,15 @@ extern "C" int sdhip_stuff(const void* src, int lds_, void* dst, int ldd, int N,
 extern "C" int sdhip_cost_volume_fwd(const void* left, const void* right, int ld, void* vol, int B, int D, int H, int W, int C,
                                      int dtype, void* stream) {
   SDHIP_CHECK_ARG(left && right && vol && B > 0 && D > 0 && H > 0 && W > 0 && C > 0 && ld >= C, "cost_volume_fwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "cost_volume_fwd: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("cost_volume_fwd", dtype);
   const long nv = (long)B * D * H * W;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == SDHIP_F32) {
-    if (vec_ok<float>(C, {ld}, {left, right, vol})) hipLaunchKernelGGL((cost_volume_fwd<float, true>), grid_for(nv * (2 * C / 4)), dim3(256), 0, st, (const float*)left, (const float*)right, ld, (float*)vol, B, D, H, W, C);
-    else hipLaunchKernelGGL((cost_volume_fwd<float, false>), grid_for(nv * 2 * C), dim3(256), 0, st, (const float*)left, (const float*)right, ld, (float*)vol, B, D, H, W, C);
-  } else {
-    if (vec_ok<bf16_t>(C, {ld}, {left, right, vol})) hipLaunchKernelGGL((cost_volume_fwd<bf16_t, true>), grid_for(nv * (2 * C / 8)), dim3(256), 0, st, (const bf16_t*)left, (const bf16_t*)right, ld, (bf16_t*)vol, B, D, H, W, C);
-    else hipLaunchKernelGGL((cost_volume_fwd<bf16_t, false>), grid_for(nv * 2 * C), dim3(256), 0, st, (const bf16_t*)left, (const bf16_t*)right, ld, (bf16_t*)vol, B, D, H, W, C);
-  }
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {ld}, {left, right, vol}), [&](auto V) {
+      hipLaunchKernelGGL((cost_volume_fwd<T, V()>), grid_for(nv * (2 * C / Unit<T, V()>::N)), dim3(256), 0, st, (const T*)left, (const T*)right, ld, (T*)vol, B, D, H, W, C);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -480,16 +471,15 @@ extern "C" int sdhip_cost_volume_fwd(const void* left, const void* right, int ld
 extern "C" int sdhip_cost_volume_bwd(const void* gvol, void* gleft, void* gright, int ld, int B, int D, int H, int W, int C,
                                      int dtype, void* stream) {
   SDHIP_CHECK_ARG(gvol && gleft && gright && B > 0 && D > 0 && H > 0 && W > 0 && C > 0 && ld >= C, "cost_volume_bwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "cost_volume_bwd: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("cost_volume_bwd", dtype);
   const long np = (long)B * H * W;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == SDHIP_F32) {
-    if (vec_ok<float>(C, {ld}, {gvol, gleft, gright})) hipLaunchKernelGGL((cost_volume_bwd<float, true>), grid_for(np * (C / 4)), dim3(256), 0, st, (const float*)gvol, (float*)gleft, (float*)gright, ld, B, D, H, W, C);
-    else hipLaunchKernelGGL((cost_volume_bwd<float, false>), grid_for(np * C), dim3(256), 0, st, (const float*)gvol, (float*)gleft, (float*)gright, ld, B, D, H, W, C);
-  } else {
-    if (vec_ok<bf16_t>(C, {ld}, {gvol, gleft, gright})) hipLaunchKernelGGL((cost_volume_bwd<bf16_t, true>), grid_for(np * (C / 8)), dim3(256), 0, st, (const bf16_t*)gvol, (bf16_t*)gleft, (bf16_t*)gright, ld, B, D, H, W, C);
-    else hipLaunchKernelGGL((cost_volume_bwd<bf16_t, false>), grid_for(np * C), dim3(256), 0, st, (const bf16_t*)gvol, (bf16_t*)gleft, (bf16_t*)gright, ld, B, D, H, W, C);
-  }
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {ld}, {gvol, gleft, gright}), [&](auto V) {
+      hipLaunchKernelGGL((cost_volume_bwd<T, V()>), grid_for(np * (C / Unit<T, V()>::N)), dim3(256), 0, st, (const T*)gvol, (T*)gleft, (T*)gright, ld, B, D, H, W, C);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -498,19 +488,23 @@ extern "C" int sdhip_softargmin_fwd(const void* cost, void* pred, float* stats, 
                                     int dtype, void* stream) {
   SDHIP_CHECK_ARG(cost && pred && B > 0 && D4 > 0 && D4 <= kMaxD4 && H4 > 0 && W4 > 0 && Dout > 0 && H > 0 && W > 0,
                   "softargmin_fwd: bad arguments (at most %d low-resolution disparity levels)", kMaxD4);
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "softargmin_fwd: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("softargmin_fwd", dtype);
   const long np = (long)B * H * W;
   hipStream_t st = (hipStream_t)stream;
   if (Dout == 4 * D4) {
     const dim3 grid((unsigned)((np + 255) / 256));
-    if (dtype == SDHIP_F32) hipLaunchKernelGGL(softargmin4_fwd<float>, grid, dim3(256), 0, st, (const float*)cost, (float*)pred, stats, B, D4, H4, W4, H, W);
-    else hipLaunchKernelGGL(softargmin4_fwd<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)cost, (bf16_t*)pred, stats, B, D4, H4, W4, H, W);
+    sdhip_by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(softargmin4_fwd<T>, grid, dim3(256), 0, st, (const T*)cost, (T*)pred, stats, B, D4, H4, W4, H, W);
+    });
     SDHIP_LAUNCH_CHECK();
     return SDHIP_OK;
   }
   SDHIP_CHECK_ARG(!stats, "softargmin_fwd: per-pixel statistics are produced for Dout = 4 * D4 only");
-  if (dtype == SDHIP_F32) hipLaunchKernelGGL(softargmin_fwd<float>, grid_for(np), dim3(256), 0, st, (const float*)cost, (float*)pred, B, D4, H4, W4, Dout, H, W);
-  else hipLaunchKernelGGL(softargmin_fwd<bf16_t>, grid_for(np), dim3(256), 0, st, (const bf16_t*)cost, (bf16_t*)pred, B, D4, H4, W4, Dout, H, W);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(softargmin_fwd<T>, grid_for(np), dim3(256), 0, st, (const T*)cost, (T*)pred, B, D4, H4, W4, Dout, H, W);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -524,7 +518,7 @@ extern "C" int sdhip_softargmin_bwd(const void* cost, const void* gpred, const f
                                     long workspace_floats, int B, int D4, int H4, int W4, int Dout, int H, int W, int dtype, void* stream) {
   SDHIP_CHECK_ARG(cost && gpred && gcost && workspace && B > 0 && D4 > 0 && D4 <= kMaxD4 && H4 > 0 && W4 > 0 && Dout > 0 && H > 0 && W > 0,
                   "softargmin_bwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "softargmin_bwd: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("softargmin_bwd", dtype);
   SDHIP_CHECK_ARG(workspace_floats >= sdhip_softargmin_bwd_workspace_floats(B, D4, H4, W4, Dout, H, W),
                   "softargmin_bwd: workspace too small (%ld floats)", workspace_floats);
   hipStream_t st = (hipStream_t)stream;
@@ -533,13 +527,11 @@ extern "C" int sdhip_softargmin_bwd(const void* cost, const void* gpred, const f
     // two stages, no atomics: per-pixel gradients of the D4 levels (f32, [B][D4][H][W]), then the bilinear adjoint per cell
     const dim3 g1((unsigned)((np + 255) / 256)), g2((unsigned)((long)B * D4 * sdhip_cdiv(H4, 8) * sdhip_cdiv(W4, 32)));
     (void)nv;
-    if (dtype == SDHIP_F32) {
-      hipLaunchKernelGGL(softargmin4_bwd_levels<float>, g1, dim3(256), 0, st, (const float*)cost, (const float*)gpred, stats, workspace, B, D4, H4, W4, H, W);
-      hipLaunchKernelGGL(softargmin_bwd_cells<float>, g2, dim3(256), 0, st, (const float*)workspace, (float*)gcost, B, D4, H4, W4, H, W);
-    } else {
-      hipLaunchKernelGGL(softargmin4_bwd_levels<bf16_t>, g1, dim3(256), 0, st, (const bf16_t*)cost, (const bf16_t*)gpred, stats, (bf16_t*)workspace, B, D4, H4, W4, H, W);
-      hipLaunchKernelGGL(softargmin_bwd_cells<bf16_t>, g2, dim3(256), 0, st, (const bf16_t*)workspace, (bf16_t*)gcost, B, D4, H4, W4, H, W);
-    }
+    sdhip_by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(softargmin4_bwd_levels<T>, g1, dim3(256), 0, st, (const T*)cost, (const T*)gpred, stats, (T*)workspace, B, D4, H4, W4, H, W);
+      hipLaunchKernelGGL(softargmin_bwd_cells<T>, g2, dim3(256), 0, st, (const T*)workspace, (T*)gcost, B, D4, H4, W4, H, W);
+    });
     SDHIP_LAUNCH_CHECK();
     return SDHIP_OK;
   }
@@ -555,13 +547,11 @@ extern "C" int sdhip_softargmin_bwd(const void* cost, const void* gpred, const f
   }
   const long sa_tiles = (long)B * sdhip_cdiv(H, kSaTH) * sdhip_cdiv(W, kSaTW);
   const int sa_grid = (int)(sa_tiles < 2048 ? sa_tiles : 2048);
-  if (dtype == SDHIP_F32) {
-    hipLaunchKernelGGL(softargmin_bwd<float>, dim3(sa_grid), dim3(256), sa_lds, st, (const float*)cost, (const float*)gpred, gcost_f32, B, D4, H4, W4, Dout, H, W);
-    hipLaunchKernelGGL(f32_to_T_kernel<float>, grid_for(nv), dim3(256), 0, st, gcost_f32, (float*)gcost, nv);
-  } else {
-    hipLaunchKernelGGL(softargmin_bwd<bf16_t>, dim3(sa_grid), dim3(256), sa_lds, st, (const bf16_t*)cost, (const bf16_t*)gpred, gcost_f32, B, D4, H4, W4, Dout, H, W);
-    hipLaunchKernelGGL(f32_to_T_kernel<bf16_t>, grid_for(nv), dim3(256), 0, st, gcost_f32, (bf16_t*)gcost, nv);
-  }
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(softargmin_bwd<T>, dim3(sa_grid), dim3(256), sa_lds, st, (const T*)cost, (const T*)gpred, gcost_f32, B, D4, H4, W4, Dout, H, W);
+    hipLaunchKernelGGL(f32_to_T_kernel<T>, grid_for(nv), dim3(256), 0, st, gcost_f32, (T*)gcost, nv);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }

@@ -296,15 +296,6 @@ __global__ __launch_bounds__(256) void mul_bcast_bwd(const T* __restrict__ g, in
   }
 }
 
-template <typename T>
-bool vec_ok(int C, std::initializer_list<int> lds, std::initializer_list<const void*> ptrs) {
-  const int n = Chunk<T>::N;
-  if (C % n) return false;
-  for (int l : lds) if (l % n) return false;
-  for (const void* p : ptrs) if (p && ((uintptr_t)p & 15)) return false;
-  return true;
-}
-
 inline dim3 grid_for(long items) {
   long b = (items + 255) / 256;
   if (b > 4096) b = 4096;
@@ -323,9 +314,11 @@ Axis make_axis(int in, int out, int mode, float scale_override) {
 
 static int check_img(const char* who, int B, int H, int W, int C, int ld, int dtype) {
   SDHIP_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && ld >= C, "%s: bad tensor B=%d H=%d W=%d C=%d ld=%d", who, B, H, W, C, ld);
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "%s: unknown dtype %d", who, dtype);
+  SDHIP_CHECK_DTYPE(who, dtype);
   return 0;
 }
+
+// the launches below give one thread to each unit (16-byte chunk or element) of each pixel: np * C / Unit<T, V()>::N items
 
 extern "C" int sdhip_maxpool3s2_fwd(const void* x, int ldx, void* y, int ldy, unsigned char* idx,
                                     int B, int H, int W, int C, int dtype, void* stream) {
@@ -334,16 +327,12 @@ extern "C" int sdhip_maxpool3s2_fwd(const void* x, int ldx, void* y, int ldy, un
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   Img in{B, H, W, C, ldx}, out{B, Ho, Wo, C, ldy};
   const long np = (long)B * Ho * Wo;
-#define VOK(T) vec_ok<T>(C, {ldx, ldy}, {x, y})
-#define IV(n) (np * (C / (n)))
-  if (dtype == SDHIP_F32) {
-    if (VOK(float)) hipLaunchKernelGGL((maxpool3s2_fwd<float, true>), grid_for(IV(4)), dim3(256), 0, (hipStream_t)stream, (const float*)x, in, (float*)y, out, idx);
-    else hipLaunchKernelGGL((maxpool3s2_fwd<float, false>), grid_for(np * C), dim3(256), 0, (hipStream_t)stream, (const float*)x, in, (float*)y, out, idx);
-  } else {
-    if (VOK(bf16_t)) hipLaunchKernelGGL((maxpool3s2_fwd<bf16_t, true>), grid_for(IV(8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, in, (bf16_t*)y, out, idx);
-    else hipLaunchKernelGGL((maxpool3s2_fwd<bf16_t, false>), grid_for(np * C), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, in, (bf16_t*)y, out, idx);
-  }
-#undef VOK
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {ldx, ldy}, {x, y}), [&](auto V) {
+      hipLaunchKernelGGL((maxpool3s2_fwd<T, V()>), grid_for(np * (C / Unit<T, V()>::N)), dim3(256), 0, (hipStream_t)stream, (const T*)x, in, (T*)y, out, idx);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -355,15 +344,12 @@ extern "C" int sdhip_maxpool3s2_bwd(const void* gy, int ldg, const unsigned char
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   Img in{B, H, W, C, ldgx}, out{B, Ho, Wo, C, ldg};
   const long np = (long)B * H * W;
-#define VOK(T) vec_ok<T>(C, {ldg, ldgx}, {gy, gx})
-  if (dtype == SDHIP_F32) {
-    if (VOK(float)) hipLaunchKernelGGL((maxpool3s2_bwd<float, true>), grid_for(IV(4)), dim3(256), 0, (hipStream_t)stream, (const float*)gy, out, idx, (float*)gx, in);
-    else hipLaunchKernelGGL((maxpool3s2_bwd<float, false>), grid_for(np * C), dim3(256), 0, (hipStream_t)stream, (const float*)gy, out, idx, (float*)gx, in);
-  } else {
-    if (VOK(bf16_t)) hipLaunchKernelGGL((maxpool3s2_bwd<bf16_t, true>), grid_for(IV(8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)gy, out, idx, (bf16_t*)gx, in);
-    else hipLaunchKernelGGL((maxpool3s2_bwd<bf16_t, false>), grid_for(np * C), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)gy, out, idx, (bf16_t*)gx, in);
-  }
-#undef VOK
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {ldg, ldgx}, {gy, gx}), [&](auto V) {
+      hipLaunchKernelGGL((maxpool3s2_bwd<T, V()>), grid_for(np * (C / Unit<T, V()>::N)), dim3(256), 0, (hipStream_t)stream, (const T*)gy, out, idx, (T*)gx, in);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -374,15 +360,12 @@ extern "C" int sdhip_avgpool_fwd(const void* x, int ldx, void* y, int ldy, int B
   SDHIP_CHECK_ARG(x && y && ldy >= C && k >= 1 && H >= k && W >= k, "avgpool_fwd: bad arguments (k=%d H=%d W=%d)", k, H, W);
   Img in{B, H, W, C, ldx}, out{B, H / k, W / k, C, ldy};
   const long np = (long)B * out.H * out.W;
-#define VOK(T) vec_ok<T>(C, {ldx, ldy}, {x, y})
-  if (dtype == SDHIP_F32) {
-    if (VOK(float)) hipLaunchKernelGGL((avgpool_fwd<float, true>), grid_for(IV(4)), dim3(256), 0, (hipStream_t)stream, (const float*)x, in, (float*)y, out, k);
-    else hipLaunchKernelGGL((avgpool_fwd<float, false>), grid_for(np * C), dim3(256), 0, (hipStream_t)stream, (const float*)x, in, (float*)y, out, k);
-  } else {
-    if (VOK(bf16_t)) hipLaunchKernelGGL((avgpool_fwd<bf16_t, true>), grid_for(IV(8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, in, (bf16_t*)y, out, k);
-    else hipLaunchKernelGGL((avgpool_fwd<bf16_t, false>), grid_for(np * C), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, in, (bf16_t*)y, out, k);
-  }
-#undef VOK
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {ldx, ldy}, {x, y}), [&](auto V) {
+      hipLaunchKernelGGL((avgpool_fwd<T, V()>), grid_for(np * (C / Unit<T, V()>::N)), dim3(256), 0, (hipStream_t)stream, (const T*)x, in, (T*)y, out, k);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -393,15 +376,12 @@ extern "C" int sdhip_avgpool_bwd(const void* gy, int ldg, void* gx, int ldgx, in
   SDHIP_CHECK_ARG(gy && gx && ldg >= C && k >= 1 && H >= k && W >= k, "avgpool_bwd: bad arguments");
   Img in{B, H, W, C, ldgx}, out{B, H / k, W / k, C, ldg};
   const long np = (long)B * H * W;
-#define VOK(T) vec_ok<T>(C, {ldg, ldgx}, {gy, gx})
-  if (dtype == SDHIP_F32) {
-    if (VOK(float)) hipLaunchKernelGGL((avgpool_bwd<float, true>), grid_for(IV(4)), dim3(256), 0, (hipStream_t)stream, (const float*)gy, out, (float*)gx, in, k);
-    else hipLaunchKernelGGL((avgpool_bwd<float, false>), grid_for(np * C), dim3(256), 0, (hipStream_t)stream, (const float*)gy, out, (float*)gx, in, k);
-  } else {
-    if (VOK(bf16_t)) hipLaunchKernelGGL((avgpool_bwd<bf16_t, true>), grid_for(IV(8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)gy, out, (bf16_t*)gx, in, k);
-    else hipLaunchKernelGGL((avgpool_bwd<bf16_t, false>), grid_for(np * C), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)gy, out, (bf16_t*)gx, in, k);
-  }
-#undef VOK
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {ldg, ldgx}, {gy, gx}), [&](auto V) {
+      hipLaunchKernelGGL((avgpool_bwd<T, V()>), grid_for(np * (C / Unit<T, V()>::N)), dim3(256), 0, (hipStream_t)stream, (const T*)gy, out, (T*)gx, in, k);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -413,15 +393,12 @@ extern "C" int sdhip_resize_fwd(const void* x, int ldx, void* y, int ldy, int B,
   Img in{B, H, W, C, ldx}, out{B, Ho, Wo, C, ldy};
   const Axis ah = make_axis(H, Ho, mode, scale_h), aw = make_axis(W, Wo, mode, scale_w);
   const long np = (long)B * Ho * Wo;
-#define VOK(T) vec_ok<T>(C, {ldx, ldy}, {x, y})
-  if (dtype == SDHIP_F32) {
-    if (VOK(float)) hipLaunchKernelGGL((resize_fwd<float, true>), grid_for(IV(4)), dim3(256), 0, (hipStream_t)stream, (const float*)x, in, (float*)y, out, ah, aw);
-    else hipLaunchKernelGGL((resize_fwd<float, false>), grid_for(np * C), dim3(256), 0, (hipStream_t)stream, (const float*)x, in, (float*)y, out, ah, aw);
-  } else {
-    if (VOK(bf16_t)) hipLaunchKernelGGL((resize_fwd<bf16_t, true>), grid_for(IV(8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, in, (bf16_t*)y, out, ah, aw);
-    else hipLaunchKernelGGL((resize_fwd<bf16_t, false>), grid_for(np * C), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, in, (bf16_t*)y, out, ah, aw);
-  }
-#undef VOK
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {ldx, ldy}, {x, y}), [&](auto V) {
+      hipLaunchKernelGGL((resize_fwd<T, V()>), grid_for(np * (C / Unit<T, V()>::N)), dim3(256), 0, (hipStream_t)stream, (const T*)x, in, (T*)y, out, ah, aw);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -442,19 +419,21 @@ extern "C" int sdhip_resize_bwd(const void* gy, int ldg, void* gx, int ldgx, flo
     return span >= 32.f ? 16 : span >= 12.f ? 4 : 1;
   };
   const int sw = lanes(aw), sh = lanes(ah);
-  if (dtype == SDHIP_F32) {
-    const bool v1 = vec_ok<float>(C, {ldg}, {gy, tmp}), v2 = vec_ok<float>(C, {ldgx}, {gx, tmp});
-    if (v1) hipLaunchKernelGGL((resize_bwd_axis<float, true, float>), grid_for(np1 * (C / 4) * sw), dim3(256), 0, s, (const float*)gy, ldg, tmp, C, (long)B * Ho, 1, C, aw, sw);
-    else hipLaunchKernelGGL((resize_bwd_axis<float, false, float>), grid_for(np1 * C * sw), dim3(256), 0, s, (const float*)gy, ldg, tmp, C, (long)B * Ho, 1, C, aw, sw);
-    if (v2) hipLaunchKernelGGL((resize_bwd_axis<float, true, float>), grid_for(np2 * (C / 4) * sh), dim3(256), 0, s, (const float*)tmp, C, (float*)gx, ldgx, (long)B, W, C, ah, sh);
-    else hipLaunchKernelGGL((resize_bwd_axis<float, false, float>), grid_for(np2 * C * sh), dim3(256), 0, s, (const float*)tmp, C, (float*)gx, ldgx, (long)B, W, C, ah, sh);
-  } else {
-    const bool v1 = vec_ok<bf16_t>(C, {ldg}, {gy});
-    if (v1) hipLaunchKernelGGL((resize_bwd_axis<bf16_t, true, float>), grid_for(np1 * (C / 8) * sw), dim3(256), 0, s, (const bf16_t*)gy, ldg, tmp, C, (long)B * Ho, 1, C, aw, sw);
-    else hipLaunchKernelGGL((resize_bwd_axis<bf16_t, false, float>), grid_for(np1 * C * sw), dim3(256), 0, s, (const bf16_t*)gy, ldg, tmp, C, (long)B * Ho, 1, C, aw, sw);
-    // second pass reads f32, writes bf16: scalar units keep it simple (the tensor is the small, pre-upsampling one)
-    hipLaunchKernelGGL((resize_bwd_axis<float, false, bf16_t>), grid_for(np2 * C * sh), dim3(256), 0, s, (const float*)tmp, C, (bf16_t*)gx, ldgx, (long)B, W, C, ah, sh);
-  }
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    constexpr bool f32 = std::is_same<T, float>::value;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {ldg}, {gy, f32 ? tmp : nullptr}), [&](auto V) {
+      hipLaunchKernelGGL((resize_bwd_axis<T, V(), float>), grid_for(np1 * (C / Unit<T, V()>::N) * sw), dim3(256), 0, s, (const T*)gy, ldg, tmp, C, (long)B * Ho, 1, C, aw, sw);
+    });
+    if constexpr (f32) {
+      sdhip_by_flag(sdhip_vec_ok<T>(C, {ldgx}, {gx, tmp}), [&](auto V) {
+        hipLaunchKernelGGL((resize_bwd_axis<float, V(), T>), grid_for(np2 * (C / Unit<T, V()>::N) * sh), dim3(256), 0, s, (const float*)tmp, C, (T*)gx, ldgx, (long)B, W, C, ah, sh);
+      });
+    } else {
+      // second pass reads f32, writes bf16: scalar units keep it simple (the tensor is the small, pre-upsampling one)
+      hipLaunchKernelGGL((resize_bwd_axis<float, false, T>), grid_for(np2 * C * sh), dim3(256), 0, s, (const float*)tmp, C, (T*)gx, ldgx, (long)B, W, C, ah, sh);
+    }
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -462,17 +441,13 @@ extern "C" int sdhip_resize_bwd(const void* gy, int ldg, void* gx, int ldgx, flo
 extern "C" int sdhip_mul_bcast_fwd(const void* a, int lda, const void* m, int ldm, void* y, int ldy, long npix, int C,
                                    int dtype, void* stream) {
   SDHIP_CHECK_ARG(a && m && y && npix > 0 && C > 0 && lda >= C && ldy >= C && ldm >= 1, "mul_bcast_fwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "mul_bcast_fwd: unknown dtype %d", dtype);
-  const long np = npix;
-#define VOK(T) vec_ok<T>(C, {lda, ldy}, {a, y})
-  if (dtype == SDHIP_F32) {
-    if (VOK(float)) hipLaunchKernelGGL((mul_bcast_fwd<float, true>), grid_for(IV(4)), dim3(256), 0, (hipStream_t)stream, (const float*)a, lda, (const float*)m, ldm, (float*)y, ldy, npix, C);
-    else hipLaunchKernelGGL((mul_bcast_fwd<float, false>), grid_for(np * C), dim3(256), 0, (hipStream_t)stream, (const float*)a, lda, (const float*)m, ldm, (float*)y, ldy, npix, C);
-  } else {
-    if (VOK(bf16_t)) hipLaunchKernelGGL((mul_bcast_fwd<bf16_t, true>), grid_for(IV(8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)m, ldm, (bf16_t*)y, ldy, npix, C);
-    else hipLaunchKernelGGL((mul_bcast_fwd<bf16_t, false>), grid_for(np * C), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)m, ldm, (bf16_t*)y, ldy, npix, C);
-  }
-#undef VOK
+  SDHIP_CHECK_DTYPE("mul_bcast_fwd", dtype);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {lda, ldy}, {a, y}), [&](auto V) {
+      hipLaunchKernelGGL((mul_bcast_fwd<T, V()>), grid_for(npix * (C / Unit<T, V()>::N)), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, (const T*)m, ldm, (T*)y, ldy, npix, C);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -480,17 +455,13 @@ extern "C" int sdhip_mul_bcast_fwd(const void* a, int lda, const void* m, int ld
 extern "C" int sdhip_mul_bcast_bwd(const void* g, int ldg, const void* a, int lda, const void* m, int ldm,
                                    void* ga, int ldga, void* gm, int ldgm, long npix, int C, int dtype, void* stream) {
   SDHIP_CHECK_ARG(g && a && m && ga && gm && npix > 0 && C > 0 && ldg >= C && lda >= C && ldga >= C, "mul_bcast_bwd: bad arguments");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "mul_bcast_bwd: unknown dtype %d", dtype);
-#define VOK(T) vec_ok<T>(C, {ldg, lda, ldga}, {g, a, ga})
-  if (dtype == SDHIP_F32) {
-    if (VOK(float)) hipLaunchKernelGGL((mul_bcast_bwd<float, true>), grid_for(npix), dim3(256), 0, (hipStream_t)stream, (const float*)g, ldg, (const float*)a, lda, (const float*)m, ldm, (float*)ga, ldga, (float*)gm, ldgm, npix, C);
-    else hipLaunchKernelGGL((mul_bcast_bwd<float, false>), grid_for(npix), dim3(256), 0, (hipStream_t)stream, (const float*)g, ldg, (const float*)a, lda, (const float*)m, ldm, (float*)ga, ldga, (float*)gm, ldgm, npix, C);
-  } else {
-    if (VOK(bf16_t)) hipLaunchKernelGGL((mul_bcast_bwd<bf16_t, true>), grid_for(npix), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)g, ldg, (const bf16_t*)a, lda, (const bf16_t*)m, ldm, (bf16_t*)ga, ldga, (bf16_t*)gm, ldgm, npix, C);
-    else hipLaunchKernelGGL((mul_bcast_bwd<bf16_t, false>), grid_for(npix), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)g, ldg, (const bf16_t*)a, lda, (const bf16_t*)m, ldm, (bf16_t*)ga, ldga, (bf16_t*)gm, ldgm, npix, C);
-  }
-#undef VOK
-#undef IV
+  SDHIP_CHECK_DTYPE("mul_bcast_bwd", dtype);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {ldg, lda, ldga}, {g, a, ga}), [&](auto V) {
+      hipLaunchKernelGGL((mul_bcast_bwd<T, V()>), grid_for(npix), dim3(256), 0, (hipStream_t)stream, (const T*)g, ldg, (const T*)a, lda, (const T*)m, ldm, (T*)ga, ldga, (T*)gm, ldgm, npix, C);
+    });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }

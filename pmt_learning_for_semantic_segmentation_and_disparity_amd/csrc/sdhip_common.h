@@ -6,6 +6,8 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <stdlib.h>
+#include <initializer_list>
+#include <type_traits>
 
 #include "../../include/sdhip.h"
 
@@ -127,6 +129,32 @@ __device__ __forceinline__ float act_hs_d(float v, int act) {
 }
 
 static inline int sdhip_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ---- host dispatch: runtime dtype / bool -> template argument -----------------------------------------------------
+// An entry point writes its launch once, inside generic lambdas:
+//   sdhip_by_dtype(dtype, [&](auto tag) { using T = typename decltype(tag)::type;
+//     sdhip_by_flag(vec, [&](auto V) { hipLaunchKernelGGL((kernel<T, V()>), grid, block, lds, s, (const T*)x, ...); }); });
+// Only what is nested gets instantiated: a flag that one dtype never takes is dispatched inside an `if constexpr` on T.
+// The dtype must have passed SDHIP_CHECK_DTYPE before.
+template <typename T> struct SdhipType { using type = T; };
+template <typename F> inline auto sdhip_by_dtype(int dtype, F&& f) {
+  return dtype == SDHIP_F32 ? f(SdhipType<float>{}) : f(SdhipType<bf16_t>{});
+}
+template <typename F> inline auto sdhip_by_flag(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+#define SDHIP_CHECK_DTYPE(who, dtype) \
+  SDHIP_CHECK_ARG((dtype) == SDHIP_F32 || (dtype) == SDHIP_BF16, "%s: unknown dtype %d", who, (int)(dtype))
+
+// may rows of C channels be moved as 16-byte chunks: C and every pixel stride a whole number of chunks, every non-null
+// pointer 16-byte aligned.  (A kernel that masks its own channel tail passes a C that always divides, e.g. 0.)
+template <typename T>
+inline bool sdhip_vec_ok(int C, std::initializer_list<int> lds, std::initializer_list<const void*> ptrs) {
+  const int n = Chunk<T>::N;
+  if (C % n) return false;
+  for (int l : lds) if (l % n) return false;
+  for (const void* p : ptrs) if (p && ((uintptr_t)p & 15)) return false;
+  return true;
+}
 
 // ---- zero fill as a KERNEL ------------------------------------------------------------------------------------------
 // hipMemsetAsync becomes a memset node when the training step is captured into a hipGraph, and on ROCm 7.2 such a node

@@ -271,18 +271,21 @@ void seg_bwd_launch(const void* y, int ldy, const float* t, int ldt, void* gy, i
     hipLaunchKernelGGL((seg_bwd_kernel<T, CP, false>), grid, dim3(256), bc, s, (const T*)y, ldy, t, ldt, (T*)gy, ldg, coef, hw, C, 0, 0, 0);
 }
 
-#define SEG_DISPATCH_CP(FN, T, ...)                                   \
-  switch (seg_cp(C)) {                                                \
-    case 2: FN<T, 2>(__VA_ARGS__); break;                             \
-    case 4: FN<T, 4>(__VA_ARGS__); break;                             \
-    case 8: FN<T, 8>(__VA_ARGS__); break;                             \
-    case 12: FN<T, 12>(__VA_ARGS__); break;                           \
-    case 16: FN<T, 16>(__VA_ARGS__); break;                           \
-    case 20: FN<T, 20>(__VA_ARGS__); break;                           \
-    case 24: FN<T, 24>(__VA_ARGS__); break;                           \
-    case 28: FN<T, 28>(__VA_ARGS__); break;                           \
-    default: FN<T, 32>(__VA_ARGS__); break;                           \
+// width of the register rows, seg_cp(C) -> template argument: f(std::integral_constant<int, CP>)
+template <typename F>
+void seg_by_cp(int C, F&& f) {
+  switch (seg_cp(C)) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 20: return f(std::integral_constant<int, 20>{});
+    case 24: return f(std::integral_constant<int, 24>{});
+    case 28: return f(std::integral_constant<int, 28>{});
+    default: return f(std::integral_constant<int, 32>{});
   }
+}
 
 inline bool seg_shape_ok(int B, long hw, int C) { return B > 0 && B <= 65535 && hw > 0 && C > 0 && C <= SEG_MAX_C && (long)B * C <= (1L << 20); }
 
@@ -298,13 +301,15 @@ extern "C" int sdhip_seg_sums(const void* logits, int ldy, const float* target, 
   SDHIP_CHECK_ARG(logits && target && workspace, "seg_sums: null pointer");
   SDHIP_CHECK_ARG(seg_shape_ok(B, hw, C), "seg_sums: B %d, %ld pixels per image, C %d (1 <= C <= %d)", B, hw, C, SEG_MAX_C);
   SDHIP_CHECK_ARG(ldy >= C && ldt >= C, "seg_sums: pixel strides %d / %d below C = %d", ldy, ldt, C);
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "seg_sums: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("seg_sums", dtype);
   SDHIP_CHECK_ARG(workspace_bytes >= (long)seg_ws_bytes(B, hw, C) && (((uintptr_t)workspace) & 15) == 0,
                   "seg_sums: workspace of %ld bytes (16-byte aligned), %ld needed", workspace_bytes, (long)seg_ws_bytes(B, hw, C));
   hipStream_t s = (hipStream_t)stream;
   double* slots = (double*)workspace;
-  if (dtype == SDHIP_F32) { SEG_DISPATCH_CP(seg_sums_launch, float, logits, ldy, target, ldt, slots, B, hw, C, s) }
-  else { SEG_DISPATCH_CP(seg_sums_launch, bf16_t, logits, ldy, target, ldt, slots, B, hw, C, s) }
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    seg_by_cp(C, [&](auto CP) { seg_sums_launch<T, CP()>(logits, ldy, target, ldt, slots, B, hw, C, s); });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -328,13 +333,15 @@ extern "C" int sdhip_seg_terms_bwd(const void* logits, int ldy, const float* tar
   SDHIP_CHECK_ARG(logits && target && grad && workspace, "seg_terms_bwd: null pointer");
   SDHIP_CHECK_ARG(seg_shape_ok(B, hw, C), "seg_terms_bwd: B %d, %ld pixels per image, C %d (1 <= C <= %d)", B, hw, C, SEG_MAX_C);
   SDHIP_CHECK_ARG(ldy >= C && ldt >= C && ldg >= C, "seg_terms_bwd: pixel strides %d / %d / %d below C = %d", ldy, ldt, ldg, C);
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "seg_terms_bwd: unknown dtype %d", dtype);
+  SDHIP_CHECK_DTYPE("seg_terms_bwd", dtype);
   SDHIP_CHECK_ARG(workspace_bytes >= (long)seg_ws_bytes(B, hw, C) && (((uintptr_t)workspace) & 15) == 0,
                   "seg_terms_bwd: workspace of %ld bytes (16-byte aligned), %ld needed", workspace_bytes, (long)seg_ws_bytes(B, hw, C));
   hipStream_t s = (hipStream_t)stream;
   const float* coef = (const float*)((const unsigned char*)workspace + seg_slot_bytes(B, hw, C));
-  if (dtype == SDHIP_F32) { SEG_DISPATCH_CP(seg_bwd_launch, float, logits, ldy, target, ldt, grad, ldg, coef, B, hw, C, s) }
-  else { SEG_DISPATCH_CP(seg_bwd_launch, bf16_t, logits, ldy, target, ldt, grad, ldg, coef, B, hw, C, s) }
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    seg_by_cp(C, [&](auto CP) { seg_bwd_launch<T, CP()>(logits, ldy, target, ldt, grad, ldg, coef, B, hw, C, s); });
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }

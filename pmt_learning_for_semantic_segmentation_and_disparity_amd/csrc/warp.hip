@@ -235,7 +235,7 @@ inline int warp_check(const char* fn, const void* right, int ldr, const void* di
   SDHIP_CHECK_ARG(right && disp, "%s: null seg_right / disp pointer", fn);
   SDHIP_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0, "%s: bad shape B=%d H=%d W=%d C=%d", fn, B, H, W, C);
   SDHIP_CHECK_ARG(W <= (1 << 17) && (long)B * H < (1L << 31), "%s: shape too large (W <= 131072, B*H < 2^31)", fn);
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "%s: unknown dtype %d", fn, dtype);
+  SDHIP_CHECK_DTYPE(fn, dtype);
   SDHIP_CHECK_ARG(ldr >= C, "%s: seg_right pixel stride %d < C=%d", fn, ldr, C);
   SDHIP_CHECK_ARG(ldd >= 1, "%s: disp must be ONE channel with pixel stride >= 1 (got %d)", fn, ldd);
   if (gate) {
@@ -264,10 +264,10 @@ extern "C" int sdhip_warp_blend_fwd(const void* seg_left, int ldl, const void* s
   hipStream_t s = (hipStream_t)stream;
   const int lg = warp_group_log2(C);
   const dim3 grid((unsigned)((long)B * H), (unsigned)((((long)W << lg) + 255) / 256));
-  if (dtype == SDHIP_F32)
-    hipLaunchKernelGGL(warp_fwd_kernel<float>, grid, dim3(256), 0, s, (const float*)seg_left, ldl, (const float*)seg_right, ldr, (const float*)disp, ldd, offset_sign, (const float*)gate, ldgt, mode, (float*)warped, ldw, (float*)both, ldb, (float*)prob, ldp, W, C, lg);
-  else
-    hipLaunchKernelGGL(warp_fwd_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)seg_left, ldl, (const bf16_t*)seg_right, ldr, (const bf16_t*)disp, ldd, offset_sign, (const bf16_t*)gate, ldgt, mode, (bf16_t*)warped, ldw, (bf16_t*)both, ldb, (bf16_t*)prob, ldp, W, C, lg);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(warp_fwd_kernel<T>, grid, dim3(256), 0, s, (const T*)seg_left, ldl, (const T*)seg_right, ldr, (const T*)disp, ldd, offset_sign, (const T*)gate, ldgt, mode, (T*)warped, ldw, (T*)both, ldb, (T*)prob, ldp, W, C, lg);
+  });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
 }
@@ -290,10 +290,10 @@ extern "C" int sdhip_warp_blend_bwd(const void* g_both, int ldgb, const void* g_
   if (g_left || g_disp || g_gate) {
     const int lg = warp_group_log2(C);
     const dim3 grid((unsigned)((long)B * H), (unsigned)((((long)W << lg) + 255) / 256));
-    if (dtype == SDHIP_F32)
-      hipLaunchKernelGGL(warp_bwd_pixel_kernel<float>, grid, dim3(256), 0, s, (const float*)g_both, ldgb, (const float*)g_warped, ldgw, (const float*)seg_left, ldl, (const float*)seg_right, ldr, (const float*)disp, ldd, offset_sign, (const float*)gate, ldgt, mode, (float*)g_left, ldgl, (float*)g_disp, ldgd, (float*)g_gate, ldgg, W, C, lg);
-    else
-      hipLaunchKernelGGL(warp_bwd_pixel_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)g_both, ldgb, (const bf16_t*)g_warped, ldgw, (const bf16_t*)seg_left, ldl, (const bf16_t*)seg_right, ldr, (const bf16_t*)disp, ldd, offset_sign, (const bf16_t*)gate, ldgt, mode, (bf16_t*)g_left, ldgl, (bf16_t*)g_disp, ldgd, (bf16_t*)g_gate, ldgg, W, C, lg);
+    sdhip_by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(warp_bwd_pixel_kernel<T>, grid, dim3(256), 0, s, (const T*)g_both, ldgb, (const T*)g_warped, ldgw, (const T*)seg_left, ldl, (const T*)seg_right, ldr, (const T*)disp, ldd, offset_sign, (const T*)gate, ldgt, mode, (T*)g_left, ldgl, (T*)g_disp, ldgd, (T*)g_gate, ldgg, W, C, lg);
+    });
   }
   if (g_right) {
     int CG = kWarpLdsFloats / W;
@@ -301,12 +301,14 @@ extern "C" int sdhip_warp_blend_bwd(const void* g_both, int ldgb, const void* g_
     const dim3 grid((unsigned)((long)B * H), (unsigned)((C + CG - 1) / CG));
     const size_t lds = (size_t)W * CG * sizeof(float);
     const int lg = warp_group_log2(CG);
-    if (!(dtype == SDHIP_F32 ? warp_scatter_allow_lds<float>() : warp_scatter_allow_lds<bf16_t>()))
-      SDHIP_FAIL(SDHIP_ERR_LAUNCH, "warp_blend_bwd: the runtime refused %d bytes of dynamic LDS", kWarpLdsFloats * (int)sizeof(float));
-    if (dtype == SDHIP_F32)
-      hipLaunchKernelGGL(warp_bwd_scatter_kernel<float>, grid, dim3(256), lds, s, (const float*)g_both, ldgb, (const float*)g_warped, ldgw, (const float*)disp, ldd, offset_sign, (const float*)gate, ldgt, mode, (float*)g_right, ldgr, W, C, CG, lg);
-    else
-      hipLaunchKernelGGL(warp_bwd_scatter_kernel<bf16_t>, grid, dim3(256), lds, s, (const bf16_t*)g_both, ldgb, (const bf16_t*)g_warped, ldgw, (const bf16_t*)disp, ldd, offset_sign, (const bf16_t*)gate, ldgt, mode, (bf16_t*)g_right, ldgr, W, C, CG, lg);
+    const int rc = sdhip_by_dtype(dtype, [&](auto tag) -> int {
+      using T = typename decltype(tag)::type;
+      if (!warp_scatter_allow_lds<T>())
+        SDHIP_FAIL(SDHIP_ERR_LAUNCH, "warp_blend_bwd: the runtime refused %d bytes of dynamic LDS", kWarpLdsFloats * (int)sizeof(float));
+      hipLaunchKernelGGL(warp_bwd_scatter_kernel<T>, grid, dim3(256), lds, s, (const T*)g_both, ldgb, (const T*)g_warped, ldgw, (const T*)disp, ldd, offset_sign, (const T*)gate, ldgt, mode, (T*)g_right, ldgr, W, C, CG, lg);
+      return SDHIP_OK;
+    });
+    if (rc) return rc;
   }
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
