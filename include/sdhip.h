@@ -232,6 +232,23 @@ int sdhip_conv1x1_cat_fwd(const void* x0, int ld0, int c0, int us0, const void* 
 /* Pack many weights in one launch: desc = ndesc rows of 8 int64 {src ptr, dst ptr, M, K, T, stride_m, stride_k, flip}
  * in device memory (same layout rules as sdhip_conv_pack_weights). */
 int sdhip_conv_pack_batch(const long* desc, int ndesc, int dtype, void* stream);
+/* The eval counterpart of sdhip_conv_pack_batch (model.eval() + torch.no_grad() of test_model, torch_implementation.py:450-582):
+ * with running statistics, conv -> nn.BatchNorm2d -> activation (convbn / deconvbn, models/dsnet_t2.py:16-77) equals one
+ * convolution with pre-scaled weights, a bias and the activation epilogue of sdhip_conv2d_fwd.  desc = ndesc rows of 16 int64
+ * in device memory, one launch for all of them:
+ *   [0] kind: 0 = fold, 1 = table
+ *   fold : [1] src weight (f32)  [2] dst pack  [3] bias_out (f32 [M])  [4] M  [5] K  [6] T  [7] stride_m  [8] stride_k  [9] flip
+ *          (layout rules of sdhip_conv_pack_weights)
+ *   table: [2] scale (f32 [groups][C])  [3] shift (f32 [groups][C])  [4] C  [5] groups            ([1], [6..9] unused)
+ *   both : [10] gamma  [11] beta (either 0: 1 / 0)  [12] running_mean  [13] running_var  [14] eps (f32 bits in the low 32)
+ *          [15] bias of the convolution (f32 [M]) or 0
+ * Per channel m, in the f32 arithmetic of the eval branch of sdhip_bn_finalize:
+ *   scale = gamma / sqrt(running_var + eps),  shift = beta - running_mean * scale (+ conv_bias * scale).
+ * fold : packed[q][t][m][c] = W(m, k, t) * scale[m] (f32 product, rounded once to the pack dtype), bias_out[m] = shift[m]; the
+ *        pad rows m in [M, roundup(M,16)) and the channel tail of the last chunk are written as zeros.
+ * table: scale[g][c] / shift[g][c] for every g < groups (a BatchNorm that is not folded: it precedes its convolution, or its
+ *        node has no bias epilogue).  Nothing beyond M (C) entries of a per-channel array is read. */
+int sdhip_conv_pack_fold_batch(const long* desc, int ndesc, int dtype, void* stream);
 /* One launch unpacks (adds) every weight gradient of the step into the flat gradient buffer:
  * desc[i] = {acc ptr (f32, packed as written by sdhip_conv2d_wgrad), grad ptr, M, K, T, stride_m, stride_k, flip};
  * grad(m,k,t) += acc[k/CK][flip ? T-1-t : t][m][k%CK].  Replaces ~200 per-layer sdhip_conv_unpack_wgrad launches of a

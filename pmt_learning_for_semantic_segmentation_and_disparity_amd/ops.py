@@ -123,6 +123,7 @@ class StepContext:
         self.offset = 0
         self.measured = 0
         self.frozen_pack = False
+        self.frozen_bufs = None  # ids of the pack buffers the step's table rewrites (None: every cached pack counts as packed)
         self.direct_grads = False
         self.nbt = None          # list of (tensor, increment) recorded while measuring
         self.side = None         # second HIP stream: weight gradients run beside the data-gradient chain
@@ -141,6 +142,8 @@ class StepContext:
         # single GPU: the queue is flushed onto the side stream, with grids limited to part of the chip, when the backward pass
         # reaches the DenseNet towers (overlap_point) — their ~400 small dependent kernels leave most CUs idle
         self.overlap = False
+        # eval step only (evalstep.EvalStep): a FoldState switches conv_bn_act / _bn_finalize to the folded eval path
+        self.fold = None
 
     def flush_wgrads(self, max_wg=0):
         """Issue the queued weight-gradient launches (grouped) on the current stream; max_wg > 0 limits every grid."""
@@ -284,10 +287,11 @@ def packed_weight(weight, kind, mode, dtype):
     key = (kind, mode, dtype)
     hit = ent.get(key)
     c = _ctx[0]
-    if hit is not None and c is not None and c.frozen_pack:
+    frozen = hit is not None and c is not None and c.frozen_pack
+    if frozen and (c.frozen_bufs is None or id(hit[1]) in c.frozen_bufs):
         return hit[1]           # packed by the batched launch at step start (train.TrainStep.pack_all)
     ver = (weight._version, _pack_generation[0])
-    if hit is not None and hit[0] == ver and not torch.cuda.is_current_stream_capturing():
+    if not frozen and hit is not None and hit[0] == ver and not torch.cuda.is_current_stream_capturing():
         return hit[1]
     dt = _lib.BF16 if dtype == torch.bfloat16 else _lib.F32
     w = weight.detach()
@@ -295,7 +299,9 @@ def packed_weight(weight, kind, mode, dtype):
         w = w.contiguous()
     rows = _pack_rows(w, kind, mode, dt)
     per = _lib.packed_elems(rows[0][2], rows[0][3], T, dt)
-    buf = torch.empty(per * kd, dtype=dtype, device=weight.device)
+    # frozen, but no row of the step's table rewrites this pack: it is repacked here, at every use, INTO the cached buffer
+    # (another step's replayed table or graph may hold its address: a cached buffer is rewritten, never replaced)
+    buf = hit[1] if frozen else torch.empty(per * kd, dtype=dtype, device=weight.device)
     es = buf.element_size()
     for src_off, dst_blk, M, K, T_, sm, sk, flip in rows:   # one launch per depth tap (3-D) / one in all (2-D)
         call("sdhip_conv_pack_weights", ctypes_ptr(w.data_ptr() + 4 * src_off), ctypes_ptr(buf.data_ptr() + es * per * dst_blk),
@@ -324,23 +330,38 @@ def _pack_rows(w, kind, mode, dt):
     return rows
 
 
-def pack_descriptors(dtype, owners=None):
+def _pack_owned(w, own, spans):
+    """Does the cached weight `w` belong to a step: it is one of the step's tensors (`own`: ids; None: everything does), or -
+    `spans`: sorted (begin, end) byte ranges of the step's parameters - a dense f32 view that lies inside one of them (HANet
+    hands the kernels a (Cout, Cin, k, 1) view of its Conv1d weights: same memory, another tensor)."""
+    if own is None or id(w) in own:
+        return True
+    if spans is None or not w.is_contiguous() or w.dtype != torch.float32 or not w.numel():
+        return False
+    import bisect
+    lo = w.data_ptr()
+    i = bisect.bisect_right(spans, (lo, float("inf"))) - 1
+    return i >= 0 and spans[i][0] <= lo and lo + 4 * w.numel() <= spans[i][1]
+
+
+def pack_descriptors(dtype, owners=None, spans=None, modes=None):
     """int64 [n][8] descriptor table {src, dst, M, K, T, stride_m, stride_k, flip} of the cached packs of `dtype` that belong
     to the parameters in `owners` (an iterable of tensors; None: every cached pack).  A training step must pass ITS model's
     parameters: the table is replayed step after step (inside a hipGraph), so a row of another model's weight — or of a
     per-step temporary such as the space-to-depth stem weight — would keep reading and writing that tensor's memory after
     it has been freed (a GPU memory fault once the allocator has returned the block: found by the full test suite, where
-    several models are alive at once)."""
+    several models are alive at once).  spans: also the cached views inside those byte ranges (_pack_owned).  modes: only the
+    packs of these orientations (an eval forward reads 'fwd' packs only)."""
     own = None if owners is None else {id(t) for t in owners}
     rows = []
     # (a snapshot: the weak-reference callbacks of parameters that die meanwhile — a discarded model being collected — pop
     #  their entries, which must not happen under a live dictionary iterator)
     for ref, ent in list(_pack_cache.values()):
         w = ref()
-        if w is None or (own is not None and id(w) not in own):
+        if w is None or not _pack_owned(w, own, spans):
             continue
         for (kind, mode, dt), (_, buf) in list(ent.items()):
-            if dt != dtype:
+            if dt != dtype or (modes is not None and mode not in modes):
                 continue
             dtc = _lib.BF16 if dt == torch.bfloat16 else _lib.F32
             if kind == 'phase':     # the eight sub-pixel sub-kernels of a 3x3x3 stride-2 weight: one single-tap row per tap
@@ -352,6 +373,151 @@ def pack_descriptors(dtype, owners=None):
             for src_off, dst_blk, M, K, T, sm, sk, flip in prow:
                 rows.append([w.data_ptr() + 4 * src_off, buf.data_ptr() + buf.element_size() * per * dst_blk, M, K, T, sm, sk, flip])
     return rows
+
+
+def cached_packs(dtype, owners, spans=None, modes=None):
+    """The cached pack buffers that pack_descriptors(dtype, owners, spans, modes) names: whoever replays such a table keeps them."""
+    own = {id(t) for t in owners}
+    return [buf for ref, ent in list(_pack_cache.values()) if ref() is not None and _pack_owned(ref(), own, spans)
+            for (kind, mode, dt), (_, buf) in list(ent.items()) if dt == dtype and (modes is None or mode in modes)]
+
+
+# ---- eval step: BatchNorm folded into the packs (sdhip_conv_pack_fold_batch) ------------------------------------------------
+FOLD_COLS = 16      # int64 columns of a row of sdhip_conv_pack_fold_batch (include/sdhip.h)
+FOLD_ACTS = (0, 1, 2)   # activations the epilogue of sdhip_conv2d_fwd takes
+
+
+def _eps_bits(eps):
+    import struct
+    return struct.unpack("<I", struct.pack("<f", float(eps)))[0]
+
+
+def _addr(t):
+    return 0 if t is None else t.data_ptr()
+
+
+def fold_row(weight, kind, bn, conv_bias, pack, bias_out):
+    """One "fold" row of sdhip_conv_pack_fold_batch: the forward pack of a 2-D (Cout,Cin,kh,kw) / (Cin,Cout,kh,kw) weight
+    (M, K, T, strides and flip exactly those of _pack_rows) scaled by `bn`'s eval-mode scale; bias_out receives the shift."""
+    if weight.dim() != 4:
+        raise _lib.SdhipError("fold_row: only 2-D convolution weights fold")
+    (src_off, _, M, K, T, sm, sk, flip), = _pack_rows(weight, kind, 'fwd', None)
+    return [0, weight.data_ptr() + 4 * src_off, _addr(pack), _addr(bias_out), M, K, T, sm, sk, flip, _addr(bn.weight), _addr(bn.bias),
+            _addr(bn.running_mean), _addr(bn.running_var), _eps_bits(bn.eps), _addr(conv_bias)]
+
+
+def table_row(bn, groups, scale, shift):
+    """One "table" row: scale / shift [groups][C] of a BatchNorm that is not folded."""
+    return [1, 0, _addr(scale), _addr(shift), bn.num_features, groups, 0, 0, 0, 0, _addr(bn.weight), _addr(bn.bias),
+            _addr(bn.running_mean), _addr(bn.running_var), _eps_bits(bn.eps), 0]
+
+
+class FoldLayer:
+    __slots__ = ("weight", "bn", "kind", "pack", "bias_out", "ok")
+
+
+class FoldState:
+    """What an eval step (evalstep.EvalStep) knows about its model's BatchNorms.  While `measuring` (one eager pass) every
+    eligible conv + BatchNorm layer gets a private folded pack and bias, and every other eval-mode BatchNorm a slot in the
+    scale / shift tables; afterwards the records are fixed: a layer or BatchNorm the pass did not meet runs as it does without
+    an eval step."""
+
+    def __init__(self, dtype, device):
+        self.dtype, self.device = dtype, device
+        self.measuring = True
+        self.layers = {}       # (id(weight), id(bn), kind) -> FoldLayer
+        self.tables = {}       # (id(bn), groups) -> [bn, groups, scale view, shift view]
+        self.table_buf = None
+        self.calls = 0         # folded layer calls of the running step
+
+    def _launch(self, rows):
+        desc = torch.tensor(rows, dtype=torch.int64, device=self.device)
+        call("sdhip_conv_pack_fold_batch", ptr(desc), len(rows), _lib.BF16 if self.dtype == torch.bfloat16 else _lib.F32, stream_ptr())
+
+    def layer(self, weight, bn, kind):
+        key = (id(weight), id(bn), kind)
+        rec = self.layers.get(key)
+        if rec is None and self.measuring:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.SdhipError("FoldState: a layer cannot be recorded inside a capture")
+            rec = FoldLayer()
+            rec.weight, rec.bn, rec.kind, rec.ok = weight, bn, kind, True
+            (_, _, M, K, T, _, _, _), = _pack_rows(weight, kind, 'fwd', None)
+            dt = _lib.BF16 if self.dtype == torch.bfloat16 else _lib.F32
+            rec.pack = torch.empty(_lib.packed_elems(M, K, T, dt), dtype=self.dtype, device=self.device)
+            rec.bias_out = torch.empty(M, dtype=torch.float32, device=self.device)
+            self._launch([fold_row(weight.detach(), kind, bn, None, rec.pack, rec.bias_out)])
+            self.layers[key] = rec
+        return rec
+
+    def table(self, bn, groups):
+        """(scale, shift) views [groups][C] of the precomputed tables, or None (measuring: the slot is recorded)."""
+        key = (id(bn), groups)
+        rec = self.tables.get(key)
+        if rec is None:
+            if self.measuring:
+                self.tables[key] = [bn, groups, None, None]
+            return None
+        return (rec[2], rec[3]) if rec[2] is not None else None
+
+    def finish(self):
+        """End of the measuring pass: allocate the tables; rows() then describes every record."""
+        self.measuring = False
+        slot = lambda bn, g: (g * bn.num_features + 3) & ~3      # 16-byte aligned tables: the consumers read them as f32x4
+        n = sum(2 * slot(bn, g) for bn, g, _, _ in self.tables.values())
+        self.table_buf = torch.empty(max(n, 4), dtype=torch.float32, device=self.device)
+        off = 0
+        for rec in self.tables.values():
+            bn, g = rec[0], rec[1]
+            k, step = g * bn.num_features, slot(bn, g)
+            rec[2] = self.table_buf[off:off + k].view(g, bn.num_features)
+            rec[3] = self.table_buf[off + step:off + step + k].view(g, bn.num_features)
+            off += 2 * step
+
+    def rows(self):
+        rows = [fold_row(r.weight.detach(), r.kind, r.bn, None, r.pack, r.bias_out) for r in self.layers.values() if r.ok]
+        rows += [table_row(bn, g, sc, sh) for bn, g, sc, sh in self.tables.values()]
+        return rows
+
+
+def _fold_state(bn=None):
+    """The FoldState of the installed context when the folded eval path applies (eval-mode BatchNorm, no autograd)."""
+    c = _ctx[0]
+    if c is None or c.fold is None or torch.is_grad_enabled() or (bn is not None and bn.training):
+        return None
+    return c.fold
+
+
+def _folded_conv_bn_act(fold, x, weight, bn, spec, act, residual, groups):
+    """act(BatchNorm_eval(conv(x))) (+ residual) as ONE sdhip_conv2d_fwd over the folded pack (+ one copy that seeds the output
+    with the residual: never more launches than the unfolded path's three).  None: this layer does not fold (the caller runs
+    the unfolded path)."""
+    if act not in FOLD_ACTS or spec.D != 1 or spec.Do != 1 or weight.dim() != 4 or bn.running_mean is None or x.dtype != fold.dtype:
+        return None
+    rec = fold.layer(weight, bn, spec.kind)
+    if rec is None or not rec.ok:
+        return None
+    _require_gpu(x, weight)
+    B, Cin, H, W = x.shape
+    xv, ldx = aligned_view(x)
+    Cout = spec.cout(weight)
+    y, ldy = alloc_nhwc(B, Cout, spec.Ho, spec.Wo, x.dtype, x.device)
+    if residual is not None:
+        # the skip of d3 / d4 (Conv2DownUp): y starts as the residual and the convolution accumulates onto it - the epilogue sums
+        # act(conv + bias) and the skip in f32 and rounds once, where an add pass behind the convolution would round twice
+        if residual.shape != y.shape or residual.dtype != y.dtype:
+            raise _lib.SdhipError("conv_bn_act: residual does not match the output")
+        rv, ldres = nhwc_view(residual)
+        call("sdhip_affine_act", ptr(rv), ldres, ptr(y), ldy, None, 0, None, None, B * spec.Ho * spec.Wo, Cout, 1, 0, dtype_code(x),
+             stream_ptr())
+    ran = try_call("sdhip_conv2d_fwd", ptr(xv), ptr(rec.pack), ptr(y), ptr(rec.bias_out), None, None, None, 0, 1,
+                   B, H, W, Cin, ldx, spec.Ho, spec.Wo, Cout, ldy, spec.kh, spec.kw, spec.stride, spec.dil, spec.pad_t, spec.pad_l,
+                   *spec.depth(), 0, groups, act, int(residual is not None), dtype_code(x), stream_ptr())
+    if not ran:
+        rec.ok = False      # no kernel with this epilogue for the shape: the layer stays on the unfolded path for good
+        return None
+    fold.calls += 1
+    return y
 
 
 class ConvSpec:
@@ -410,6 +576,11 @@ def _bn_finalize(stats, nrep, bn, count, groups, synced=False):
     `count` is the LOCAL element count per group; under data parallelism statistics and count become global."""
     C = bn.num_features
     dev = bn.weight.device
+    if stats is None:
+        fold = _fold_state()
+        t = fold.table(bn, groups) if fold is not None else None
+        if t is not None:   # eval step: constants, written by the step's batched launch (mean / invstd serve a backward only)
+            return [t[0], t[1], None, None]
     if not synced:      # `synced`: the statistics were already summed over ranks (slab statistics of a dense block)
         stats, nrep = _sync_stats(stats, nrep)
     count = parallel.global_count(count)
@@ -1045,6 +1216,11 @@ def conv_bn_act(x, weight, bn, *, kind='conv', stride=1, dilation=1, padding=0, 
     to autograd, and a gradient parked in in_slot is summed into this node's data gradient by its own launch.
     in_bn / out_bn (BNSlot, optional): x is the output of the convbn + ReLU node that owns in_bn / this node's output has
     exactly one consumer, which holds out_bn as its in_bn."""
+    fold = _fold_state(bn)
+    if fold is not None:     # eval step: conv with the folded pack, bias and activation epilogue (FoldState)
+        y = _folded_conv_bn_act(fold, x, weight, bn, conv_spec(x, weight, kind, stride, dilation, padding), act, residual, groups)
+        if y is not None:
+            return y
     return _ConvBNActFn.apply(x, weight, bn.weight, bn.bias, residual, conv_spec(x, weight, kind, stride, dilation, padding),
                               bn, act, groups, in_slot, res_slot, in_bn, out_bn)
 

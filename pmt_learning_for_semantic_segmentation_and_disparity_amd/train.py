@@ -63,6 +63,55 @@ def flatten_parameters(model):
     return flat_p, flat_g
 
 
+def close_broken_capture(graph, streams, device, who):
+    """Best-effort return to a launchable process after an exception inside a capture (TrainStep, evalstep.EvalStep): the
+    capture is ended on every stream it spans and the allocator's pool redirection closed."""
+    try:
+        graph.capture_end()                  # ends the allocator's pool redirection when the capture itself is intact
+    except BaseException:
+        pass
+    for st in streams:
+        try:
+            _lib.abort_capture(st)
+        except _lib.SdhipError as e:
+            import sys
+            sys.stderr.write("[%s] %s\n" % (who, e))
+    try:
+        torch._C._cuda_endAllocateToPool(device.index or 0, graph.pool())
+    except BaseException:
+        pass
+
+
+def _default_generator(device):
+    return torch.cuda.default_generators[device.index if device.index is not None else torch.cuda.current_device()]
+
+
+def capture_generator_state(device):
+    """State of torch's default CUDA generator, taken before a capture begins (reset_capture_generator)."""
+    try:
+        return _default_generator(device).get_state()
+    except BaseException:
+        return None
+
+
+def reset_capture_generator(device, state, who):
+    """capture_begin put torch's default CUDA generator into capture mode and only a completed capture_end takes it out
+    again ("Offset increment outside graph capture" on the next torch.randn(device='cuda')): give the generator a fresh,
+    non-capturing state object carrying EXACTLY the seed and offset it had before the capture began - later torch CUDA draws
+    continue the stream instead of replaying it from its start."""
+    try:
+        gen = _default_generator(device)
+        fresh = torch.Generator(device=device)
+        if state is not None:
+            fresh.set_state(state)
+        else:
+            fresh.manual_seed(gen.initial_seed())
+        gen.graphsafe_set_state(fresh.graphsafe_get_state())
+    except BaseException as e:
+        import sys
+        sys.stderr.write("[%s] could not reset the capture state of torch's CUDA generator: %s\n" % (who, str(e).splitlines()[0]))
+
+
 class TrainStep:
     def __init__(self, model, dtype=torch.bfloat16, lr=None, betas=(0.9, 0.999), eps=1e-7, use_lovasz=True,
                  use_graph=True, world_size=1, process_group=None, use_side_stream=None, loss_fn=None, metrics=None, accumulate=1,
@@ -349,29 +398,11 @@ class TrainStep:
 
     def _close_broken_capture(self, graph, cap):
         """Best-effort return to a launchable process after an exception inside the capture."""
-        try:
-            graph.capture_end()                  # ends the allocator's pool redirection when the capture itself is intact
-        except BaseException:
-            pass
-        streams = [cap] + ([self.ctx.side] if self.ctx.side is not None else [])
-        for st in streams:
-            try:
-                _lib.abort_capture(st)
-            except _lib.SdhipError as e:
-                import sys
-                sys.stderr.write("[TrainStep] %s\n" % e)
-        try:
-            torch._C._cuda_endAllocateToPool(self.flat_p.device.index or 0, graph.pool())
-        except BaseException:
-            pass
+        close_broken_capture(graph, [cap] + ([self.ctx.side] if self.ctx.side is not None else []), self.flat_p.device, "TrainStep")
         del graph
 
     def _torch_generator_state(self):
-        try:
-            dev = self.flat_p.device
-            return torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()].get_state()
-        except BaseException:
-            return None
+        return capture_generator_state(self.flat_p.device)
 
     def _abandon_capture(self):
         """A capture that raised recorded launches but executed none: device state (parameters, moments, running
@@ -379,22 +410,7 @@ class TrainStep:
         step has to be reset before eager steps continue."""
         self.graph, self.graphs, self.use_graph, self.loss = None, {}, False, None
         torch.cuda.synchronize()               # raises if the process could not be brought back: nothing can run then
-        # capture_begin put torch's default CUDA generator into capture mode and only a completed capture_end takes it out
-        # again ("Offset increment outside graph capture" on the next torch.randn(device='cuda')): give the generator a
-        # fresh, non-capturing state object carrying EXACTLY the seed and offset it had before the capture began — later
-        # torch CUDA draws continue the stream instead of replaying it from its start
-        try:
-            dev = self.flat_p.device
-            gen = torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
-            fresh = torch.Generator(device=dev)
-            if getattr(self, "_gen_state", None) is not None:
-                fresh.set_state(self._gen_state)
-            else:
-                fresh.manual_seed(gen.initial_seed())
-            gen.graphsafe_set_state(fresh.graphsafe_get_state())
-        except BaseException as e:
-            import sys
-            sys.stderr.write("[TrainStep] could not reset the capture state of torch's CUDA generator: %s\n" % str(e).splitlines()[0])
+        reset_capture_generator(self.flat_p.device, getattr(self, "_gen_state", None), "TrainStep")
         self.ctx.unpacks = []
         self.ctx.wq = []
         self.ctx.wq_keep.clear()

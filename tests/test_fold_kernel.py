@@ -1,0 +1,229 @@
+"""sdhip_conv_pack_fold_batch: eval-mode BatchNorm folded into the packed weights of a convolution.
+
+CPU: the symbol is declared, exported and bound; the host row builder names the same pack geometry as ops._pack_rows.
+GPU: folded pack -> sdhip_conv2d_fwd(bias, act = ReLU) against an f64 CPU conv -> BatchNorm(eval) -> ReLU with non-trivial
+running statistics, on shapes that hit every edge of the pack (pad rows of M, channel tail of the last chunk, flip, more than
+one chunk), plus one map large enough for the persistent band kernel.  f32: the project's 1e-3 parity tolerance.  bf16: the
+same test first measures the existing unfolded path (conv, sdhip_bn_finalize, sdhip_affine_act) against the same f64 result;
+the folded path gets twice that relative L2 error - its rounding points differ (weights rounded after scaling, as against the
+raw output rounded before scaling) and are independent errors of the same size.  The destination pack and bias are filled with
+NaN before the fold launch, so finite outputs prove that the pad rows and tails are written, not skipped.
+
+Reference: models/dsnet_t2.py:16-77 (convbn / deconvbn) under model.eval() (torch_implementation.py:450-582)."""
+import ctypes
+import functools
+import os
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EPS = 1e-5
+
+# (kind, Cin, Cout, k, stride, dil, B, H, W)
+CASES = {
+    "conv3to1_k5_dil2": ("conv", 3, 1, 5, 1, 2, 2, 12, 20),
+    "conv8to19_k3": ("conv", 8, 19, 3, 1, 1, 2, 12, 20),
+    "conv65to64_k1": ("conv", 65, 64, 1, 1, 1, 2, 12, 20),
+    "conv16to32_k3_s2": ("conv", 16, 32, 3, 2, 1, 2, 12, 20),
+    "deconv32to33_k3": ("deconv", 32, 33, 3, 1, 1, 2, 12, 20),
+    "band64to64_k5": ("conv", 64, 64, 5, 1, 1, 1, 256, 384),      # the smallest map with >= 192 tiles of 16x32
+}
+BAND_ROWS = ((0, 16), (112, 144), (240, 256))    # output rows of the band case the f64 reference covers (both borders, the middle)
+
+
+# ---------------------------------------------------------------------------------------------------------------- CPU
+def test_fold_symbol_is_declared_exported_and_bound():
+    from pmt_learning_for_semantic_segmentation_and_disparity_amd import _lib
+    text = open(os.path.join(ROOT, "include", "sdhip.h")).read()
+    assert "int sdhip_conv_pack_fold_batch(const long* desc, int ndesc, int dtype, void* stream);" in text
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    assert hasattr(lib, "sdhip_conv_pack_fold_batch")
+    assert _lib.SIGNATURES["sdhip_conv_pack_fold_batch"] == [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    assert _lib._lib.sdhip_conv_pack_fold_batch.restype is ctypes.c_int
+    # argument validation happens before any GPU work
+    assert _lib._lib.sdhip_conv_pack_fold_batch(None, 0, 0, None) == _lib.ERR_ARG
+
+
+@pytest.mark.parametrize("kind,shape", [("conv", (19, 8, 3, 3)), ("deconv", (32, 33, 5, 5))])
+def test_fold_row_names_the_geometry_of_pack_rows(kind, shape):
+    """A (Cout,Cin,kh,kw) and a (Cin,Cout,kh,kw) weight: M, K, T, strides and flip of the fold row are those of _pack_rows."""
+    from pmt_learning_for_semantic_segmentation_and_disparity_amd import ops, _lib
+    w = torch.zeros(shape)
+    cout = shape[0] if kind == "conv" else shape[1]
+    bn = torch.nn.BatchNorm2d(cout, eps=1e-3)
+    row = ops.fold_row(w, kind, bn, None, None, None)
+    (src_off, blk, M, K, T, sm, sk, flip), = ops._pack_rows(w, kind, "fwd", _lib.F32)
+    assert len(row) == ops.FOLD_COLS == 16 and row[0] == 0
+    assert tuple(row[4:10]) == (M, K, T, sm, sk, flip) and M == cout and src_off == 0 and blk == 0
+    assert row[1] == w.data_ptr() and row[2] == 0 and row[3] == 0 and row[15] == 0
+    assert row[10:14] == [bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr()]
+    import struct
+    assert struct.unpack("<f", struct.pack("<I", row[14]))[0] == pytest.approx(1e-3, rel=1e-7)
+    t = ops.table_row(bn, 2, None, None)
+    assert len(t) == 16 and t[0] == 1 and t[4:6] == [cout, 2] and t[10:15] == row[10:15]
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU
+def _same_pad(size, k, stride, dil):
+    out = -(-size // stride)
+    total = max((out - 1) * stride - size + dil * (k - 1) + 1, 0)
+    return total // 2, total - total // 2
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    """Inputs (bf16-representable activations, so that both dtypes share one reference) and the f64 CPU result."""
+    kind, cin, cout, k, stride, dil, B, H, W = CASES[name]
+    g = torch.Generator().manual_seed(sum(map(ord, name)))
+    x = torch.randn((B, cin, H, W), generator=g).bfloat16().float()
+    wshape = (cout, cin, k, k) if kind == "conv" else (cin, cout, k, k)
+    w = torch.randn(wshape, generator=g) / (cin * k * k) ** 0.5
+    gamma = 0.5 + torch.rand(cout, generator=g)
+    beta = torch.rand(cout, generator=g) - 0.5
+    rmean = 0.3 * torch.randn(cout, generator=g)
+    rvar = 0.5 + 1.5 * torch.rand(cout, generator=g)
+    xd, wd = x.double(), w.double()
+
+    def bn_relu(y):
+        sc = gamma.double() / torch.sqrt(rvar.double() + EPS)
+        sh = beta.double() - rmean.double() * sc
+        return torch.relu(y * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1))
+
+    if kind == "deconv":       # stride-1 ConvTranspose2dSame: the full transposed convolution, cropped from full//2 - size//2
+        full = F.conv_transpose2d(xd, wd, stride=1, dilation=dil)
+        s0, s1 = (H + dil * (k - 1)) // 2 - H // 2, (W + dil * (k - 1)) // 2 - W // 2
+        ref = bn_relu(full[:, :, s0:s0 + H, s1:s1 + W])
+        rows = None
+    elif name.startswith("band"):   # the reference of three row bands only: a full f64 map of this size takes too long
+        pt, pb = _same_pad(H, k, stride, dil)
+        pl, pr = _same_pad(W, k, stride, dil)
+        xp = F.pad(xd, (pl, pr, pt, pb))
+        ref = torch.cat([bn_relu(F.conv2d(xp[:, :, r0:r1 + k - 1], wd)) for r0, r1 in BAND_ROWS], 2)
+        rows = torch.cat([torch.arange(r0, r1) for r0, r1 in BAND_ROWS])
+    else:                      # conv2dSame: TF-"same" padding, the odd pixel at the bottom / right
+        pt, pb = _same_pad(H, k, stride, dil)
+        pl, pr = _same_pad(W, k, stride, dil)
+        ref = bn_relu(F.conv2d(F.pad(xd, (pl, pr, pt, pb)), wd, stride=stride, dilation=dil))
+        rows = None
+    return x, w, gamma, beta, rmean, rvar, ref, rows
+
+
+def _bn(cout, gamma, beta, rmean, rvar):
+    bn = torch.nn.BatchNorm2d(cout, eps=EPS).cuda().eval()
+    with torch.no_grad():
+        bn.weight.copy_(gamma); bn.bias.copy_(beta); bn.running_mean.copy_(rmean); bn.running_var.copy_(rvar)
+    return bn
+
+
+def _run_conv(ops, x, pack, bias, spec, cout, act):
+    B, cin, H, W = x.shape
+    xv, ldx = ops.aligned_view(x)
+    y, ldy = ops.alloc_nhwc(B, cout, spec.Ho, spec.Wo, x.dtype, x.device)
+    ops._conv_launch(xv, ldx, pack, y, ldy, bias, None, None, None, B, H, W, cin, spec.Ho, spec.Wo, cout,
+                     spec.kh, spec.kw, spec.stride, spec.dil, spec.pad_t, spec.pad_l, False, 1, act, False)
+    return y, ldy
+
+
+def _folded(ops, _lib, x, w, bn, kind, spec, cout, dt):
+    (_, _, M, K, T, _, _, _), = ops._pack_rows(w, kind, "fwd", dt)
+    pack = torch.full((_lib.packed_elems(M, K, T, dt),), float("nan"), dtype=x.dtype, device="cuda")     # poison
+    bias_out = torch.full((M,), float("nan"), dtype=torch.float32, device="cuda")
+    desc = torch.tensor([ops.fold_row(w, kind, bn, None, pack, bias_out)], dtype=torch.int64, device="cuda")
+    _lib.call("sdhip_conv_pack_fold_batch", _lib.ptr(desc), 1, dt, _lib.stream_ptr())
+    assert bool(torch.isfinite(pack.float()).all()) and bool(torch.isfinite(bias_out).all()), "pad rows / tails were not written"
+    y, _ = _run_conv(ops, x, pack, bias_out, spec, cout, 1)
+    return y
+
+
+def _unfolded(ops, _lib, x, w, bn, kind, spec, cout, dt):
+    """Today's eval arithmetic: conv, sdhip_bn_finalize (running statistics), sdhip_affine_act."""
+    (_, _, M, K, T, sm, sk, flip), = ops._pack_rows(w, kind, "fwd", dt)
+    pack = torch.empty(_lib.packed_elems(M, K, T, dt), dtype=x.dtype, device="cuda")
+    _lib.call("sdhip_conv_pack_weights", _lib.ptr(w), _lib.ptr(pack), M, K, T, sm, sk, flip, dt, _lib.stream_ptr())
+    yraw, ldr = _run_conv(ops, x, pack, None, spec, cout, 0)
+    scale, shift = (torch.empty((1, cout), dtype=torch.float32, device="cuda") for _ in range(2))
+    _lib.call("sdhip_bn_finalize", None, 0, 1, _lib.ptr(bn.weight), _lib.ptr(bn.bias), _lib.ptr(bn.running_mean),
+              _lib.ptr(bn.running_var), _lib.ptr(scale), _lib.ptr(shift), None, None, cout, 1, 1.0, EPS, 0.0, _lib.stream_ptr())
+    B, _, Ho, Wo = yraw.shape
+    y, ldy = ops.alloc_nhwc(B, cout, Ho, Wo, x.dtype, x.device)
+    _lib.call("sdhip_affine_act", _lib.ptr(yraw), ldr, _lib.ptr(y), ldy, None, 0, _lib.ptr(scale), _lib.ptr(shift), B * Ho * Wo, cout,
+              1, 1, dt, _lib.stream_ptr())
+    return y, scale, shift
+
+
+def _rel_l2(got, want):
+    return float(torch.linalg.norm(got - want) / torch.linalg.norm(want).clamp_min(1e-12))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_hip_folded_conv_matches_f64_conv_bn_relu(name, dtype):
+    """Measured relative L2 errors against f64, bf16 (unfolded / folded) - DESIGN.md f-6 holds the table."""
+    from pmt_learning_for_semantic_segmentation_and_disparity_amd import ops, _lib
+    kind, cin, cout, k, stride, dil, B, H, W = CASES[name]
+    x, w, gamma, beta, rmean, rvar, ref, rows = _case(name)
+    dt = _lib.BF16 if dtype == torch.bfloat16 else _lib.F32
+    xg = x.cuda().to(dtype).contiguous(memory_format=torch.channels_last)
+    wg = w.cuda()
+    bn = _bn(cout, gamma, beta, rmean, rvar)
+    spec = ops.conv_spec(xg, wg, kind, stride, dil, "same" if kind == "conv" else "ctsame")
+    with torch.no_grad():
+        y = _folded(ops, _lib, xg, wg, bn, kind, spec, cout, dt)
+        yu, scale, shift = _unfolded(ops, _lib, xg, wg, bn, kind, spec, cout, dt)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(y.float()).all())
+    pick = (lambda t: t.double().cpu()) if rows is None else (lambda t: t.double().cpu()[:, :, rows])
+    got, got_u = pick(y), pick(yu)
+    assert got.shape == ref.shape
+    # the scale / shift a fold row writes are those of the eval branch of sdhip_bn_finalize
+    sc64 = gamma.double() / torch.sqrt(rvar.double() + EPS)
+    assert torch.allclose(scale.double().cpu()[0], sc64, rtol=1e-6, atol=0)
+    e_f, e_u = _rel_l2(got, ref), _rel_l2(got_u, ref)
+    print("fold-kernel %s %s: rel L2 vs f64 unfolded %.3e folded %.3e; max abs folded %.3e"
+          % (name, "bf16" if dt == _lib.BF16 else "f32", e_u, e_f, float((got - ref).abs().max())))
+    if dtype == torch.float32:
+        tol = 1e-3 * max(1.0, float(ref.abs().max()))
+        assert float((got - ref).abs().max()) <= tol, (name, float((got - ref).abs().max()), tol)
+    else:
+        assert e_f <= 2.0 * e_u, (name, e_f, e_u)
+
+
+@pytest.mark.gpu
+def test_hip_fold_batch_tables_and_conv_bias():
+    """One launch, three rows: a table row (scale / shift for 2 groups, equal to sdhip_bn_finalize's eval branch bit for bit), a
+    fold row with a convolution bias (shift += bias * scale) and a fold row without gamma / beta pointers (1 / 0)."""
+    from pmt_learning_for_semantic_segmentation_and_disparity_amd import ops, _lib
+    g = torch.Generator().manual_seed(7)
+    C = 37
+    bn = _bn(C, 0.5 + torch.rand(C, generator=g), torch.rand(C, generator=g) - 0.5, torch.randn(C, generator=g), 0.2 + torch.rand(C, generator=g))
+    w = torch.randn((C, 5, 3, 3), generator=g).cuda()
+    cb = torch.randn(C, generator=g).cuda()
+    nan = float("nan")
+    tab = torch.full((2, 2, C), nan, device="cuda")
+    n = _lib.packed_elems(C, 5, 9, _lib.F32)
+    p1, p2 = torch.full((n,), nan, device="cuda"), torch.full((n,), nan, device="cuda")
+    b1, b2 = torch.full((C,), nan, device="cuda"), torch.full((C,), nan, device="cuda")
+    plain = torch.nn.BatchNorm2d(C, eps=EPS, affine=False).cuda().eval()
+    with torch.no_grad():
+        plain.running_mean.copy_(bn.running_mean); plain.running_var.copy_(bn.running_var)
+    rows = [ops.table_row(bn, 2, tab[0], tab[1]), ops.fold_row(w, "conv", bn, cb, p1, b1), ops.fold_row(w, "conv", plain, None, p2, b2)]
+    desc = torch.tensor(rows, dtype=torch.int64, device="cuda")
+    _lib.call("sdhip_conv_pack_fold_batch", _lib.ptr(desc), 3, _lib.F32, _lib.stream_ptr())
+    want = [torch.empty((2, C), device="cuda") for _ in range(2)]
+    _lib.call("sdhip_bn_finalize", None, 0, 1, _lib.ptr(bn.weight), _lib.ptr(bn.bias), _lib.ptr(bn.running_mean),
+              _lib.ptr(bn.running_var), _lib.ptr(want[0]), _lib.ptr(want[1]), None, None, C, 2, 1.0, EPS, 0.0, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert torch.equal(tab[0], want[0]) and torch.equal(tab[1], want[1])
+    sc, sh = want[0][0], want[1][0]
+    assert torch.allclose(b1, sh + cb * sc, rtol=1e-6, atol=1e-6)
+    inv = 1.0 / torch.sqrt(bn.running_var + EPS)
+    assert torch.allclose(b2, -bn.running_mean * inv, rtol=1e-6, atol=1e-6)
+    # packed[q][t][m][c]: chunk 0 holds all 5 input channels (CK = 32 in f32), 9 taps, Mpad = 48 rows
+    P1, P2 = p1.view(1, 9, 48, 32), p2.view(1, 9, 48, 32)
+    wt = w.permute(2, 3, 0, 1).reshape(9, C, 5)
+    assert torch.equal(P1[0, :, :C, :5], wt * sc.view(1, C, 1)) and torch.equal(P2[0, :, :C, :5], wt * inv.view(1, C, 1))
+    assert float(P1[0, :, C:].abs().max()) == 0.0 and float(P1[0, :, :, 5:].abs().max()) == 0.0
+    assert float(P2[0, :, C:].abs().max()) == 0.0 and float(P2[0, :, :, 5:].abs().max()) == 0.0
