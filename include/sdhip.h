@@ -114,6 +114,9 @@ int sdhip_conv_unpack_wgrad(const float* acc, float* grad, int M, int K, int T,
 /* y[b,oh,ow,m] = act( bias[m] + sum_{t,k} W[m,k,t] * pro(x)[b, oh*stride + kh*dil - pad_t, ow*stride + kw*dil - pad_l, k] )
  *   pro(x) = x, or relu?(x*in_scale[g][k] + in_shift[g][k]) when in_scale != NULL (the BatchNorm+ReLU
  *            that precedes the conv, models/densenet.py:41-45,75-93); zero padding is applied AFTER pro;
+ *            in_scale / in_shift are f32 [groups][Cin] for ANY Cin (a channel count that is no multiple
+ *            of the 16-byte vector is supported): nothing outside those groups*Cin entries is read, and the elements
+ *            [Cin, ldx) of a pixel of x never reach the result, whatever they hold (NaN included);
  *   g      = b / (B/groups): statistics group of image b (left/right tower passes share a launch);
  *   stats  : if non-NULL, f64 [groups][2][stats_ld >= Cout] (stats_ld <= 0 means Cout; a slice of a wider
  *            statistics slab is addressed by offsetting the pointer), replicated stats_nrep times
@@ -194,12 +197,16 @@ int sdhip_conv2d_fwd_bnbwd(const void* x, const void* wpacked, void* y, double* 
  * zero-stuffed volume.  x: [B][D][H][W][Cin]; y: the [B][2D][2H][2W][Cout] output volume (pixel stride ldy), of which this
  * call writes the voxels (2d + off_d, 2h + off_h, 2w + off_w); wpacked: the phase's sub-kernel packed [kd][q][t][m][c]
  * with taps ordered input-offset-major (sdhip_conv_pack_weights per depth tap); stats: as sdhip_conv2d_fwd (the eight
- * calls add into the same sums).  bf16 / f32, 16-byte aligned pixels. */
+ * calls add into the same sums).  bf16 / f32, 16-byte aligned pixels.  The depth axis is doubled like the other two also
+ * in the 2-D form: with D = kd = 1 and off_d = 0, y is [B][2][2H][2W][Cout] and the four calls fill depth slice 0 of every
+ * image; slice 1 is not touched. */
 int sdhip_conv2d_fwd_phase(const void* x, const void* wpacked, void* y, double* stats, int stats_ld, int stats_nrep,
                            int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int kh, int kw,
                            int D, int kd, int groups, int off_d, int off_h, int off_w, int dtype, void* stream);
 /* prezeroed != 0: the caller already zeroed dw_packed / dbias (one arena memset per step instead of one per call).
- * dW (packed f32, zeroed here) = sum over pixels of dy (x) pro(x); dbias[m] = sum dy (optional). */
+ * dW (packed f32, zeroed here) = sum over pixels of dy (x) pro(x); dbias[m] = sum dy (optional).  Only the entries (m < Cout,
+ * k < Cin) of dw_packed receive anything: its pad rows [Cout, roundup(Cout,16)) and the channel tail of its last chunk stay
+ * exactly zero, whatever the elements [Cin, ldx) of x and [Cout, lddy) of dy hold. */
 int sdhip_conv2d_wgrad(const void* x, const void* dy, float* dw_packed, float* dbias,
                        const float* in_scale, const float* in_shift,
                        int B, int H, int W, int Cin, int ldx,

@@ -217,8 +217,20 @@ __global__ __launch_bounds__(256) void conv_fast_kernel(const FastArgs p) {
   // 2*V scale/shift values are fetched once per chunk (four 16-byte loads), not once per pixel.
   float psc[V], psf[V];
   auto prologue_load = [&](int ch0) {
-    if (ch0 < p.Cin) {   // Cin % V == 0 whenever a prologue is fused (host: the tail path never carries one)
+    if (ch0 < p.Cin) {
       if constexpr (!DMA) {
+        if (p.tail) {   // uniform, rare (Cin % V != 0): nothing past the Cin entries of the group's row is read, and the lanes
+                        // mask_tail zeroed get scale = shift = 0, so they stay zero through the affine (+ ReLU)
+          const float* tsc = p.pin_stats ? ptab_sc : p.in_scale + grp * p.Cin;
+          const float* tsf = p.pin_stats ? ptab_sh : p.in_shift + grp * p.Cin;
+#pragma unroll
+          for (int e = 0; e < V; ++e) {
+            const bool okc = ch0 + e < p.Cin;
+            psc[e] = okc ? tsc[okc ? ch0 + e : 0] : 0.f;
+            psf[e] = okc ? tsf[okc ? ch0 + e : 0] : 0.f;
+          }
+          return;
+        }
         if (p.pin_stats) {   // consumer-side finalize: the table built at kernel start
 #pragma unroll
           for (int e = 0; e < V; ++e) { psc[e] = ptab_sc[ch0 + e]; psf[e] = ptab_sh[ch0 + e]; }

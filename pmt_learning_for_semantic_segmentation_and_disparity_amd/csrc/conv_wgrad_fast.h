@@ -107,7 +107,7 @@ __device__ __forceinline__ void wgrad_fast_body(const WgfArgs& p, const int bx, 
   const int rest = wave / CIT;
   const int co_tile0 = (rest % COG) * NCO;
   const int tap_lane = rest / COG;
-  const int cin_q = qb ? CK : min(CK, p.Cin - q * CK);   // packed: every flushed chunk writes all 64 columns (pad columns are zeros)
+  const int cin_q = qb ? CK : min(CK, p.Cin - q * CK);   // packed: every wave flushes; the columns past Cin are left out per chunk there
   const int cout_m = min(MB, p.Cout - m0);
 
   f32x4 acc[MAXTW][NCO];
@@ -193,7 +193,7 @@ __device__ __forceinline__ void wgrad_fast_body(const WgfArgs& p, const int bx, 
 
   // Per-lane source offsets of an INTERIOR tile (no padding, no ragged edge): tile base + constant offset per round.
   // Lanes of dead columns / past the tile / past the channels read some valid address; their LDS rows are never used
-  // (or only feed dW columns nobody reads).
+  // (or only feed dW rows / columns the flush leaves out).
   constexpr int XR = 8;
   int xo[XR], yo[y_rounds];
   auto xpix = [&](int iw) { return qb ? (((iw >> (qsh + 1)) << 1) | (iw & 1)) : iw; };   // pixel column of a halo-line position
@@ -375,7 +375,7 @@ __device__ __forceinline__ void wgrad_fast_body(const WgfArgs& p, const int bx, 
             Chunk<T>::unpack(raw, f);
 #pragma unroll
             for (int e = 0; e < V; ++e) {
-              const float v = fmaf(f[e], psc[e], psf[e]);   // pad channels (>= Cin) only feed dW columns nobody reads
+              const float v = fmaf(f[e], psc[e], psf[e]);   // pad channels (>= Cin) only feed dW columns the flush leaves out
               f[e] = p.in_relu ? fmaxf(v, 0.f) : v;
             }
             raw = Chunk<T>::pack(f);
@@ -420,12 +420,15 @@ __device__ __forceinline__ void wgrad_fast_body(const WgfArgs& p, const int bx, 
       const int tt = tl * TAPL + tap_lane;
       if (tt < nt) {
         float* dst = p.dwp + ((long)((kdi * p.nq + q) * T_ + t0 + tt) * p.Mpad) * CK;
+        // Only real (m, k) entries are flushed: the pad rows [Cout, Mpad) and the channel tail of the last chunk were fed by
+        // whatever the lanes [Cout, lddy) of dY / [Cin, ldx) of X hold (other channels of a slab, NaN) and stay zero.
+        const bool kok = ci_tile * 16 + l15 < (qb ? p.Cin - (q * qb + tt) * CK : cin_q);
 #pragma unroll
         for (int mi = 0; mi < NCO; ++mi) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int m = m0 + (co_tile0 + mi) * 16 + 4 * lg + r;
-            if (m < p.Mpad) atomicAdd(dst + (long)m * CK + ci_tile * 16 + l15, acc[tl][mi][r]);
+            if (m < p.Cout && kok) atomicAdd(dst + (long)m * CK + ci_tile * 16 + l15, acc[tl][mi][r]);
           }
         }
       }

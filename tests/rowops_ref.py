@@ -340,3 +340,35 @@ class Rows:
         a[:, self.k:self.k + self.C] = 0
         b[:, self.k:self.k + self.C] = 0
         return bool(torch.equal(a.view(bits), b.view(bits)))
+
+
+class diag_switches:
+    """`with diag_switches(SDHIP_CONV_GENERIC="1", SDHIP_CONV_BIG=None):` sets (None: unsets) diagnostic environment
+    switches and has the library re-read them; on the way out — by an exception too — the environment is what it was and the
+    library has re-read it again, so a failing assert cannot leak a switch into the later tests of the process."""
+
+    def __init__(self, **env):
+        self.env = env
+
+    def __enter__(self):
+        import os
+        from pmt_learning_for_semantic_segmentation_and_disparity_amd import _lib
+        self.old = {k: os.environ.get(k) for k in self.env}
+        self._set(self.env)
+        _lib.reload_diag()
+        return self
+
+    def __exit__(self, *exc):
+        from pmt_learning_for_semantic_segmentation_and_disparity_amd import _lib
+        self._set(self.old)
+        _lib.reload_diag()
+        return False
+
+    @staticmethod
+    def _set(env):
+        import os
+        for k, v in env.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = str(v)

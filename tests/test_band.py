@@ -8,6 +8,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import sys  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from rowops_ref import diag_switches  # noqa: E402
+
 CASES = [  # name, B, Cin, Cout, H, W, kind, act
     ("c64_64_ragged", 2, 64, 64, 100, 450, 'conv', 0),      # the hot shape, ragged tiles in both directions
     ("c32_32", 4, 32, 32, 96, 256, 'conv', 1),              # one 32-channel half, 32 output channels (BN = 32)
@@ -109,17 +113,8 @@ def test_band_conv_statistics_match_old_kernel(B, ci, co, H, W, groups):
 
     y, yplain, rm, rv = run()
     assert ((y - yr).abs().max() / yr.abs().max()).item() < 2e-2
-    old = os.environ.get("SDHIP_CONV_NO_BAND")
-    os.environ["SDHIP_CONV_NO_BAND"] = "1"
-    _lib.reload_diag()
-    try:
+    with diag_switches(SDHIP_CONV_NO_BAND="1"):
         y0, yplain0, rm0, rv0 = run()
-    finally:
-        if old is None:
-            os.environ.pop("SDHIP_CONV_NO_BAND", None)
-        else:
-            os.environ["SDHIP_CONV_NO_BAND"] = old
-        _lib.reload_diag()
     # same products, different summation order over (tap, channel half): equal up to f32 rounding before the bf16 store
     assert (yplain - yplain0).abs().max().item() <= 2e-2 * yplain0.abs().max().item()
     assert ((yplain != yplain0).float().mean().item()) < 0.2

@@ -786,15 +786,6 @@ def test_bn_finalize_bwd(C):
         check("bn_finalize_bwd dstats", dS.np()[0], dSr, np.stack([e_dmu, e_dvar], 1) + F64EPS * np.abs(dSr))
 
 
-def _fused_cap(value):
-    from pmt_learning_for_semantic_segmentation_and_disparity_amd import _lib
-    if value is None:
-        os.environ.pop("SDHIP_TUNE_FUSED_BLOCKS", None)
-    else:
-        os.environ["SDHIP_TUNE_FUSED_BLOCKS"] = str(value)
-    _lib.reload_diag()
-
-
 def _affine_act_bn_case(dtype, C, lay, n, G, nrep, strided, act, with_res, opt, rng, label):
     count = float(n // G)
     x = make_x(rng, n, C, dtype)
@@ -881,16 +872,13 @@ def test_fused_kernels_capped_grid(dtype):
     """SDHIP_TUNE_FUSED_BLOCKS = 1 leaves one workgroup per block row and group.  (4, 9, 13) pixels, groups 1, C = 12: f32
     3 vector units -> ty = 85, bf16 12 scalar units -> ty = 21: 468 pixels are 6 / 23 trips of the plain loop and 2 / 6 trips
     of the 4-pixel unrolled one, the last of them ragged (468 = 5 x 85 + 43 = 22 x 21 + 6).  C = 520 bf16 keeps cb > 0 in it."""
-    _fused_cap(1)
-    try:
+    with R.diag_switches(SDHIP_TUNE_FUSED_BLOCKS=1):
         for C in (12, 520):
             n, G = 468, 1
             assert geom(dtype, C, n, G, 1, Rows(n, C, dtype))[2] == 1
             _affine_act_bn_case(dtype, C, "dense", n, G, 3, True, 1, True, "all", rng_for(C, 13), "affine_act_bn capped")
             _bwd_fin_case(dtype, C, "dense", n, G, 3, 1, False, 1.0, False, rng_for(C, 14), "bn_bwd_apply_fin capped")
             _bwd_fin_case(dtype, C, "dense", n, G, 32, 2, True, 1.0, True, rng_for(C, 15), "bn_bwd_apply_fin_d capped")
-    finally:
-        _fused_cap(None)
 
 
 @pytest.mark.gpu

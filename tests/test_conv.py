@@ -9,6 +9,10 @@ import torch
 from oracle import ref_models as R
 from oracle.detweights import fill_state_dict, randn_input
 
+import sys  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from rowops_ref import diag_switches  # noqa: E402
+
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "ops.npz")
 
 CONV_CASES = [("c1", 8, 16, 1, 1, 1, 9, 11), ("c3", 16, 8, 3, 1, 1, 12, 17), ("c5", 8, 8, 5, 1, 1, 13, 16),
@@ -199,8 +203,6 @@ def test_hip_1x1_wgrad_many_channels(B, H, W, Cin, ldx, Cout, pro, groups):
     partial last chunk — against an f32 contraction of the same (bf16-rounded) operands."""
     import os
     from pmt_learning_for_semantic_segmentation_and_disparity_amd import ops, _lib
-    os.environ["SDHIP_WGRAD_FORCE_PACK"] = "1"      # the launch heuristic would keep these small maps on the unpacked kernel
-    _lib.reload_diag()
     torch.manual_seed(Cin + Cout)
     dev = torch.device("cuda:0")
     slab = torch.randn(B, H, W, ldx, device=dev).to(torch.bfloat16)
@@ -211,7 +213,8 @@ def test_hip_1x1_wgrad_many_channels(B, H, W, Cin, ldx, Cout, pro, groups):
     sh = (torch.rand(groups, Cin, device=dev) - 0.5) if pro else None
     spec = ops.ConvSpec('conv', 1, 1, 1, 1, 0, 0, H, W)
     ops.set_step_context(None)
-    gw, _ = ops._wgrad_impl(x, ldx, g, Cout, w, None, spec, sc, sh, pro, groups)
+    with diag_switches(SDHIP_WGRAD_FORCE_PACK="1"):     # the launch heuristic would keep these small maps on the unpacked kernel
+        gw, _ = ops._wgrad_impl(x, ldx, g, Cout, w, None, spec, sc, sh, pro, groups)
     xe = x.float()
     if pro:
         per = B // groups
@@ -219,8 +222,6 @@ def test_hip_1x1_wgrad_many_channels(B, H, W, Cin, ldx, Cout, pro, groups):
         h4 = sh.repeat_interleave(per, 0)[:, :, None, None]
         xe = torch.relu(torch.addcmul(h4, xe, s4)).to(torch.bfloat16).float()     # the kernel rounds the prologue result to bf16
     want = torch.einsum("bmhw,bchw->mc", g.float(), xe)
-    os.environ.pop("SDHIP_WGRAD_FORCE_PACK", None)
-    _lib.reload_diag()
     err = float((gw.reshape(Cout, Cin) - want).norm() / want.norm())
     assert err < 2e-3, err
 

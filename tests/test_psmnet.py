@@ -11,6 +11,10 @@ import torch.nn.functional as F
 from oracle import ref_models as R
 from oracle.detweights import fill_state_dict, rand_input, randn_input
 
+import sys  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from rowops_ref import diag_switches  # noqa: E402
+
 GDIR = os.path.join(os.path.dirname(__file__), "golden")
 
 
@@ -125,23 +129,17 @@ def test_hip_conv3d_bf16_persistent_volume_kernel(B, ci, co, D, H, W):
     # convbn_3d + ReLU, then convbn_3d + skip (the shape of dres1, stackhourglass.py:65-68), both kernels
     res = {}
     for sw in ("", "1"):
-        if sw:
-            os.environ["SDHIP_CONV_NO_BAND3"] = sw
-        else:
-            os.environ.pop("SDHIP_CONV_NO_BAND3", None)
-        _lib.reload_diag()
-        torch.manual_seed(5)
-        bn1, bn2 = nn.BatchNorm3d(co).cuda().train(), nn.BatchNorm3d(co).cuda().train()
-        w1 = w.cuda().requires_grad_(True); w2 = (w * 0.5).cuda().requires_grad_(True)
-        x0 = _vol_to_images(x.cuda()).requires_grad_(True)
-        slot = ops.GradSlot(exclusive=True)
-        h, _ = ops.conv3d_bn_act(x0, D, w1, bn1, act=1, in_slot=slot)
-        y, _ = ops.conv3d_bn_act(h, D, w2, bn2, act=0, residual=x0, res_slot=slot)
-        y.backward(_vol_to_images(gy.cuda()))
-        torch.cuda.synchronize()
-        res[sw] = (y.detach().float(), x0.grad.float(), bn1.running_var.clone(), bn2.running_mean.clone(), bn1.weight.grad.clone())
-    os.environ.pop("SDHIP_CONV_NO_BAND3", None)
-    _lib.reload_diag()
+        with diag_switches(SDHIP_CONV_NO_BAND3=sw or None):
+            torch.manual_seed(5)
+            bn1, bn2 = nn.BatchNorm3d(co).cuda().train(), nn.BatchNorm3d(co).cuda().train()
+            w1 = w.cuda().requires_grad_(True); w2 = (w * 0.5).cuda().requires_grad_(True)
+            x0 = _vol_to_images(x.cuda()).requires_grad_(True)
+            slot = ops.GradSlot(exclusive=True)
+            h, _ = ops.conv3d_bn_act(x0, D, w1, bn1, act=1, in_slot=slot)
+            y, _ = ops.conv3d_bn_act(h, D, w2, bn2, act=0, residual=x0, res_slot=slot)
+            y.backward(_vol_to_images(gy.cuda()))
+            torch.cuda.synchronize()
+            res[sw] = (y.detach().float(), x0.grad.float(), bn1.running_var.clone(), bn2.running_mean.clone(), bn1.weight.grad.clone())
     for a, b in zip(res[""], res["1"]):
         assert _rel(a, b) < 2.0 ** -6, _rel(a, b)
 

@@ -4,9 +4,14 @@ layers: models/densenet.py:25-93, models/dsnet_t2.py:80-117, models_psmnet/stack
 before the optimizer step (:724), which is what allows the regrouping.  Results must equal the per-layer launches up to
 the order of the f32 atomic adds."""
 import ctypes
+import os
+import sys
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from rowops_ref import diag_switches  # noqa: E402
 
 
 def _layer(dev, B, H, W, Cin, Cout, k, ldx=None, pro=False, groups=1, stride=1, dil=1, D=1, kd=1, bias=False, seed=0):
@@ -130,14 +135,8 @@ def test_half_row_kernel_matches_f32_contraction(B, D, H, W, Cin, Cout):
     ops.set_step_context(None)
     got = {}
     for sw in ("", "1"):
-        if sw:
-            os.environ["SDHIP_WGRAD_NO_HALF32"] = sw
-        else:
-            os.environ.pop("SDHIP_WGRAD_NO_HALF32", None)
-        _lib.reload_diag()
-        got[sw], _ = ops._wgrad_impl(xi[0], xi[1], gi[0], gi[1], w, None, spec, None, None, False, 1)
-    os.environ.pop("SDHIP_WGRAD_NO_HALF32", None)
-    _lib.reload_diag()
+        with diag_switches(SDHIP_WGRAD_NO_HALF32=sw or None):
+            got[sw], _ = ops._wgrad_impl(xi[0], xi[1], gi[0], gi[1], w, None, spec, None, None, False, 1)
     n = float(want.norm())
     assert n > 0
     assert float((got[""] - want).norm()) / n < 2e-3, float((got[""] - want).norm()) / n
@@ -173,14 +172,8 @@ def test_single_map_wgrad_matches_f32_contraction(B, D, H, W, Cin, k):
     ops.set_step_context(None)
     got = {}
     for sw in ("", "1"):
-        if sw:
-            os.environ["SDHIP_CONV_NO_THIN"] = sw
-        else:
-            os.environ.pop("SDHIP_CONV_NO_THIN", None)
-        _lib.reload_diag()
-        got[sw], _ = ops._wgrad_impl(xi[0], xi[1], gi[0], gi[1], w, None, spec, None, None, False, 1)
-    os.environ.pop("SDHIP_CONV_NO_THIN", None)
-    _lib.reload_diag()
+        with diag_switches(SDHIP_CONV_NO_THIN=sw or None):
+            got[sw], _ = ops._wgrad_impl(xi[0], xi[1], gi[0], gi[1], w, None, spec, None, None, False, 1)
     n = float(want.norm())
     assert n > 0 and got[""].shape == want.shape
     assert float((got[""] - want).norm()) / n < 2e-3, float((got[""] - want).norm()) / n
