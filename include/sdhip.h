@@ -305,6 +305,14 @@ int sdhip_affine_act(const void* x, int ldx, void* y, int ldy, const void* res, 
 int sdhip_affine_act_bwd(const void* gy, int ldg, const void* x, int ldx, void* gx, int ldgx,
                          const float* scale, const float* shift, float* dscale, float* dshift, int nrep,
                          long npix, int C, int groups, int act, int accumulate, int prezeroed, int dtype, void* stream);
+/* Backward of y = act(conv_folded(x) + bias) through the activation and a FROZEN BatchNorm folded into the weight pack
+ * (sdhip_conv_pack_fold_batch; `-freeze_bn 1`, torch_implementation.py:235-241): graw[p][c] = gy[p][c] * act'(y[p][c]) *
+ * scale[g][c], the gradient of the RAW convolution output, from which the data and weight gradients run with the raw weight.
+ * The derivative is taken from the activation's OUTPUT y: act 0 -> 1, 1 (ReLU) -> y > 0, 2 (sigmoid) -> y (1 - y).
+ * scale: f32 [groups][C], group g owns the g-th npix/groups rows.  Only the C logical channels of a row are written.  The
+ * 16-byte path is taken when C and the three strides are multiples of 16 bytes of elements and the pointers are aligned. */
+int sdhip_act_out_bwd(const void* gy, int ldg, const void* y, int ldy, void* graw, int ldgr, const float* scale,
+                      long npix, int C, int groups, int act, int dtype, void* stream);
 /* out[row][c] += sum_r ws[r][row][c] over the 2*groups statistics rows (folds conv-epilogue replicas into a slab). */
 int sdhip_stats_replica_sum(const double* ws, double* out, int nrep, int groups, int C, int ldw, int ldo, void* stream);
 /* sdhip_stats_replica_sum of the Cn newest channels (replicas ws[nrep][groups][2][ldw]) into the statistics slab

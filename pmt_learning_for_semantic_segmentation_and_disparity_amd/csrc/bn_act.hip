@@ -160,6 +160,51 @@ __global__ __launch_bounds__(256) void affine_act_bwd_kernel(const T* gy, int ld
   }
 }
 
+// graw = gy * act'(y) * scale with the derivative taken from the activation's OUTPUT y (frozen BatchNorm folded into the
+// weight pack: the raw convolution output is never stored).  A pure stream of 2 reads and 1 write per element: 16 bytes per
+// lane in the vector form, 2 pixels per trip with both pairs of loads issued before the first use, ~20 VGPRs - the block
+// count, not the registers, bounds the bytes in flight.  grid: (pixel slabs, unit groups, scale groups)
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void act_out_bwd_kernel(const T* __restrict__ gy, int ldg, const T* __restrict__ y, int ldy,
+                                                          T* __restrict__ graw, int ldgr, const float* __restrict__ scale,
+                                                          int C, long npix_g, int act, RowGeom rg) {
+  constexpr int N = Unit<T, VEC>::N;
+  ROW_TXTY(rg, tx, ty);
+  const int u = blockIdx.y * rg.tx + tx;
+  if (ty >= rg.ty || u >= rg.units) return;
+  const int g = blockIdx.z, c0 = u * N;
+  float sc[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) sc[e] = scale[g * C + c0 + e];
+  const long base = (long)g * npix_g;
+  const long stride = (long)gridDim.x * rg.ty;
+  for (long pix0 = (long)blockIdx.x * rg.ty + ty; pix0 < npix_g; pix0 += 2 * stride) {
+    float gv[2][N], yv[2][N];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const long pix = pix0 + k * stride;
+      if (pix < npix_g) {
+        Unit<T, VEC>::load(gy + (base + pix) * ldg + c0, gv[k]);
+        Unit<T, VEC>::load(y + (base + pix) * ldy + c0, yv[k]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const long pix = pix0 + k * stride;
+      if (pix < npix_g) {
+#pragma unroll
+        for (int e = 0; e < N; ++e) {
+          float gm = gv[k][e];
+          if (act == 1) gm = yv[k][e] > 0.f ? gm : 0.f;          // -0.0 > 0 is false: an exact +0
+          else if (act == 2) gm *= fmaf(-yv[k][e], yv[k][e], yv[k][e]);   // y (1 - y), rounded once
+          gv[k][e] = gm * sc[e];
+        }
+        Unit<T, VEC>::store(graw + (base + pix) * ldgr + c0, gv[k]);
+      }
+    }
+  }
+}
+
 // g_out = g_in + dS1 + 2 * x * dS2   (dS is [G][2][C], f64 like the statistics it is the gradient of)
 template <typename T, bool VEC>
 __global__ __launch_bounds__(256) void stats_fix_kernel(const T* gin, int ldgi, const T* __restrict__ x, int ldx,
@@ -714,6 +759,25 @@ extern "C" int sdhip_affine_act_bwd(const void* gy, int ldg, const void* x, int 
     sdhip_by_flag(v, [&](auto V) { sdhip_by_flag(hard_act(act), [&](auto HS) {
       hipLaunchKernelGGL((affine_act_bwd_kernel<T, V(), HS()>), pl.grid, dim3(256), 0, s, (const T*)gy, ldg, (const T*)x, ldx, (T*)gx, ldgx, scale, shift, dscale, dshift, nrep, C, npix / G, act, accumulate, pl.rg);
     }); });
+  });
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}
+
+extern "C" int sdhip_act_out_bwd(const void* gy, int ldg, const void* y, int ldy, void* graw, int ldgr, const float* scale,
+                                 long npix, int C, int groups, int act, int dtype, void* stream) {
+  const int G = groups;
+  if (int rc = check_rows("act_out_bwd", npix, C, G, dtype)) return rc;
+  SDHIP_CHECK_ARG(gy && y && graw && scale && ldg >= C && ldy >= C && ldgr >= C, "act_out_bwd: bad pointers/strides");
+  SDHIP_CHECK_ARG(act == 0 || act == 1 || act == 2, "act_out_bwd: activation %d", act);
+  hipStream_t s = (hipStream_t)stream;
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const bool v = sdhip_vec_ok<T>(C, {ldg, ldy, ldgr}, {gy, y, graw});
+    const Plan pl = plan(v ? C / Chunk<T>::N : C, npix / G, G);
+    sdhip_by_flag(v, [&](auto V) {
+      hipLaunchKernelGGL((act_out_bwd_kernel<T, V()>), pl.grid, dim3(256), 0, s, (const T*)gy, ldg, (const T*)y, ldy, (T*)graw, ldgr, scale, C, npix / G, act, pl.rg);
+    });
   });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;

@@ -71,6 +71,24 @@ FUSE1_MAX_PIX = _lib_mod.TUNE_FUSE1_MAX_PIX
 PRO_MAX_PIX = _lib_mod.TUNE_PRO_MAX_PIX    # maps up to this many pixels: norm2 is finalized inside conv2's launch
 
 
+def block_training(block, name=None):
+    """Does a dense block normalise with batch statistics?  The block runs as one node with one mode, so it follows its norms:
+    all of them frozen (ops.bn_frozen: eval mode, no gradient to weight and bias; `-freeze_bn 1`, torch_implementation.py:235-241)
+    -> running statistics, whatever the block's own flag says; none frozen -> the block's flag; a mixture has no single mode."""
+    frozen = [ops.bn_frozen(n) for layer in block.values() for n in (layer.norm1, layer.norm2)]
+    if not any(frozen):
+        return block.training
+    if not all(frozen):
+        raise _lib_mod.SdhipError("dense block %s: %d of its %d BatchNorms are frozen; a block runs as one node and needs all of "
+                                  "them frozen or none" % (name or "of %d layers" % len(block), sum(frozen), len(frozen)))
+    return False
+
+
+def dense_blocks(model):
+    """[(qualified name, block)] of `model`: train.TrainStep runs block_training over them before a pass launches anything."""
+    return [(name, m) for name, m in model.named_modules() if isinstance(m, _DenseBlock)]
+
+
 class _DenseBlockFn(torch.autograd.Function):
     """(slab, slab statistics) = dense_block(x0); see the module docstring."""
 
@@ -84,7 +102,7 @@ class _DenseBlockFn(torch.autograd.Function):
         Ct = C0 + L * growth
         dev, dtype = x0.device, x0.dtype
         dt = dtype_code(x0)
-        training = block.training
+        training = block_training(block)
         npix = B * H * W
         count = (B // groups) * H * W
         slab = ops.empty_nhwc(B, Ct, H, W, dtype, dev)
@@ -194,8 +212,10 @@ class _DenseBlockFn(torch.autograd.Function):
             sl_g = g_slab[:, Cin:Cin + growth]
             sl_x = slab[:, Cin:Cin + growth]
             # (1) total gradient of this layer's 32 output channels (all consumers are already accumulated)
-            dy2 = ops.empty_nhwc(B, growth, H, W, dtype, dev)
-            if pend is not None:
+            dy2, ld2 = (ops.empty_nhwc(B, growth, H, W, dtype, dev), growth) if training else (sl_g, Ct)
+            if not training:
+                pass    # running statistics: no gradient flows through them, the slice of the slab gradient IS the total (no copy)
+            elif pend is not None:
                 # ... in the same launch as the per-channel finalize of the layer above (sdhip_stats_fix_fin)
                 dsc, dsh, nl, dgam, dbet, direct, Cf = pend
                 call("sdhip_stats_fix_fin", ptr(sl_g), Ct, ptr(sl_x), Ct, ptr(dy2), growth, npix, ptr(dS), Ct, Cin, ptr(dsc), ptr(dsh), NREP,
@@ -214,9 +234,9 @@ class _DenseBlockFn(torch.autograd.Function):
                 call("sdhip_conv2d_fwd_bnbwd", ptr(dy2), ptr(wd2), ptr(gp2), ptr(sums2), mid, NREP, ptr(y1), mid,
                      ptr(sc2), ptr(sh2), None, 0, B, H, W, growth, growth, H, W, mid, mid, 3, 3, 1, 1, 1, groups, 0, dt, st)
             else:
-                ops._conv_launch(dy2, growth, wd2, gp2, mid, None, None, None, None, B, H, W, growth, H, W, mid, 3, 3, 1, 1, 1, 1,
+                ops._conv_launch(dy2, ld2, wd2, gp2, mid, None, None, None, None, B, H, W, growth, H, W, mid, 3, 3, 1, 1, 1, 1,
                                  False, 1, 0, False)
-            gw2 = _wgrad(y1, mid, dy2, growth, layer.conv2.weight, B, H, W, mid, growth, 3, 1, sc2, sh2, groups, dt)
+            gw2 = _wgrad(y1, mid, dy2, ld2, layer.conv2.weight, B, H, W, mid, growth, 3, 1, sc2, sh2, groups, dt)
             # (3) through relu + norm2's affine, (4) norm2's statistics, (5) into y1
             if fuse2:
                 _, _, dg2, db2 = ops._bn_act_backward(gp2, mid, y1, mid, sc2, sh2, mu2, iv2, layer.norm2.weight, layer.norm2.bias,

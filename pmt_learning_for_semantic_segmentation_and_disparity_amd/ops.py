@@ -142,7 +142,8 @@ class StepContext:
         # single GPU: the queue is flushed onto the side stream, with grids limited to part of the chip, when the backward pass
         # reaches the DenseNet towers (overlap_point) — their ~400 small dependent kernels leave most CUs idle
         self.overlap = False
-        # eval step only (evalstep.EvalStep): a FoldState switches conv_bn_act / _bn_finalize to the folded eval path
+        # a FoldState switches conv_bn_act / _bn_finalize to the folded path: every eval-mode BatchNorm of an eval step
+        # (evalstep.EvalStep), the frozen BatchNorms of a training step (train.TrainStep(freeze_bn=True))
         self.fold = None
 
     def flush_wgrads(self, max_wg=0):
@@ -422,8 +423,12 @@ class FoldState:
     scale / shift tables; afterwards the records are fixed: a layer or BatchNorm the pass did not meet runs as it does without
     an eval step."""
 
-    def __init__(self, dtype, device):
+    def __init__(self, dtype, device, train=False, fold=True):
         self.dtype, self.device = dtype, device
+        # train: the state of a training step (train.TrainStep).  It serves FROZEN BatchNorms (bn_frozen) of grad-enabled passes,
+        # and only while `live`: between the batched launch at the head of a step and the end of its backward pass, when packs
+        # and tables hold the current weights.  fold False: tables only (TrainStep(fold_bn=False))
+        self.train, self.fold, self.live = train, fold, not train
         self.measuring = True
         self.layers = {}       # (id(weight), id(bn), kind) -> FoldLayer
         self.tables = {}       # (id(bn), groups) -> [bn, groups, scale view, shift view]
@@ -435,6 +440,8 @@ class FoldState:
         call("sdhip_conv_pack_fold_batch", ptr(desc), len(rows), _lib.BF16 if self.dtype == torch.bfloat16 else _lib.F32, stream_ptr())
 
     def layer(self, weight, bn, kind):
+        if not self.fold:
+            return None
         key = (id(weight), id(bn), kind)
         rec = self.layers.get(key)
         if rec is None and self.measuring:
@@ -480,18 +487,32 @@ class FoldState:
         return rows
 
 
+def bn_frozen(bn):
+    """`-freeze_bn 1` (torch_implementation.py:235-241) as a property of the module: eval mode and neither affine parameter
+    requires a gradient.  Such a norm is a constant per-channel scale / shift of the step."""
+    return not bn.training and not _wants_grad(bn.weight, bn.bias)
+
+
+def _wants_grad(gamma, beta):
+    return (gamma is not None and gamma.requires_grad) or (beta is not None and beta.requires_grad)
+
+
 def _fold_state(bn=None):
-    """The FoldState of the installed context when the folded eval path applies (eval-mode BatchNorm, no autograd)."""
+    """The FoldState of the installed context when a folded path applies: an eval step's for an eval-mode BatchNorm without
+    autograd, a training step's for a frozen BatchNorm while that step's pass runs (`live`; the grad mode says nothing
+    there: it is off inside every autograd node's forward)."""
     c = _ctx[0]
-    if c is None or c.fold is None or torch.is_grad_enabled() or (bn is not None and bn.training):
+    if c is None or c.fold is None or (bn is not None and bn.training):
         return None
-    return c.fold
+    if c.fold.train:
+        return c.fold if c.fold.live and bn is not None and bn_frozen(bn) else None
+    return None if torch.is_grad_enabled() else c.fold
 
 
-def _folded_conv_bn_act(fold, x, weight, bn, spec, act, residual, groups):
+def _folded_conv_bn_act(fold, x, weight, bn, spec, act, residual, groups, views=None):
     """act(BatchNorm_eval(conv(x))) (+ residual) as ONE sdhip_conv2d_fwd over the folded pack (+ one copy that seeds the output
     with the residual: never more launches than the unfolded path's three).  None: this layer does not fold (the caller runs
-    the unfolded path)."""
+    the unfolded path).  views: a list that receives (xv, ldx, ldy) of the launch (the training node saves them)."""
     if act not in FOLD_ACTS or spec.D != 1 or spec.Do != 1 or weight.dim() != 4 or bn.running_mean is None or x.dtype != fold.dtype:
         return None
     rec = fold.layer(weight, bn, spec.kind)
@@ -517,7 +538,57 @@ def _folded_conv_bn_act(fold, x, weight, bn, spec, act, residual, groups):
         rec.ok = False      # no kernel with this epilogue for the shape: the layer stays on the unfolded path for good
         return None
     fold.calls += 1
+    if views is not None:
+        views.append((xv, ldx, ldy))
     return y
+
+
+class _NoFold(Exception):
+    """The folded kernel does not take this layer's shape: conv_bn_act runs the table form instead (once; the record remembers)."""
+
+
+class _FoldedConvBNActFn(torch.autograd.Function):
+    """y = act(BatchNorm(conv(x))) with a FROZEN BatchNorm (bn_frozen) inside a training step: ONE sdhip_conv2d_fwd over the
+    pack the step's batched launch folded the norm into, with the shift as bias and the activation in the epilogue.  The node
+    keeps x and the activated y; the raw convolution output never exists.  Backward: sdhip_act_out_bwd turns gy into the
+    gradient of the raw output, g * act'(y) * scale, and the data and weight gradients run on that with the RAW weight
+    (dW_raw = wgrad(x, g act' s) exactly: the fold scales whole output channels).  No residual: with a skip the epilogue
+    rounds act(.) + skip once and the activated value the backward needs is never stored (conv_bn_act keeps the table form)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, fold, spec, bn, act, groups, in_slot, in_bn):
+        views = []
+        y = _folded_conv_bn_act(fold, x, weight, bn, spec, act, None, groups, views)
+        if y is None:
+            raise _NoFold()
+        (xv, ldx, ldy), = views
+        # scale [1][Cout] of the same norm: a row of the step's table once the step is armed (no launch)
+        scale = _bn_finalize(None, 1, bn, 0, 1)[0]
+        ctx.spec, ctx.act, ctx.ldx, ctx.ldy, ctx.in_slot, ctx.in_bn = spec, act, ldx, ldy, in_slot, in_bn
+        ctx.save_for_backward(xv, weight, y, scale)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xv, weight, y, scale = ctx.saved_tensors
+        spec = ctx.spec
+        B, Cout = y.shape[0], y.shape[1]
+        g, ldg = nhwc_view(gy)
+        graw, ldgr = alloc_nhwc(B, Cout, spec.Ho, spec.Wo, y.dtype, y.device)
+        call("sdhip_act_out_bwd", ptr(g), ldg, ptr(y), ctx.ldy, ptr(graw), ldgr, ptr(scale), B * spec.Ho * spec.Wo, Cout, 1, ctx.act,
+             dtype_code(y), stream_ptr())
+        acc = addend = None
+        if ctx.in_slot is not None and ctx.in_slot.g is not None and ctx.needs_input_grad[0]:
+            parked, ctx.in_slot.g = ctx.in_slot.g, None       # the skip consumer of x already ran: add to its contribution
+            if parked.shape != xv.shape or parked.dtype != xv.dtype:
+                raise _lib.SdhipError("GradSlot: parked gradient does not match the input it belongs to")
+            if ctx.in_slot.exclusive:
+                acc = parked
+            else:
+                addend = parked
+        gx, gw, _ = _conv_backward(spec, xv, ctx.ldx, weight, graw, ldgr, None, None, False, 1, ctx.needs_input_grad[0],
+                                   ctx.needs_input_grad[1], acc_into=acc, addend=addend, bn_slot=ctx.in_bn)
+        return gx, gw, None, None, None, None, None, None, None
 
 
 class ConvSpec:
@@ -577,7 +648,7 @@ def _bn_finalize(stats, nrep, bn, count, groups, synced=False):
     C = bn.num_features
     dev = bn.weight.device
     if stats is None:
-        fold = _fold_state()
+        fold = _fold_state(bn)
         t = fold.table(bn, groups) if fold is not None else None
         if t is not None:   # eval step: constants, written by the step's batched launch (mean / invstd serve a backward only)
             return [t[0], t[1], None, None]
@@ -653,6 +724,12 @@ def _bn_backward(gy, ldg, x, ldx, gx, ldgx, scale, shift, mean, invstd, gamma, n
     Writes gx (+)= gy*act'*scale and returns (dgamma, dbeta, dstats[groups][2][C]); the caller still has to add the
     statistics path dstats[0] + 2*x*dstats[1] (sdhip_stats_fix) to the gradient of whatever produced x."""
     dev = scale.device
+    if not train and not _wants_grad(gamma, beta):
+        # frozen BatchNorm: a constant scale / shift.  No reductions, no replica buffers, no finalize, and the parameters'
+        # slices of the flat gradient buffer are not touched (torch: their .grad stays None)
+        call("sdhip_affine_act_bwd", ptr(gy), ldg, ptr(x), ldx, ptr(gx), ldgx, ptr(scale), ptr(shift), None, None, 1,
+             npix, C, groups, act, int(accumulate_gx), 0, dt, stream_ptr())
+        return None, None, None
     both, pz = _zeros((2, NREP, groups, C), torch.float32, dev)
     dsc, dsh = both[0], both[1]
     call("sdhip_affine_act_bwd", ptr(gy), ldg, ptr(x), ldx, ptr(gx), ldgx, ptr(scale), ptr(shift), ptr(dsc), ptr(dsh), NREP,
@@ -1217,7 +1294,15 @@ def conv_bn_act(x, weight, bn, *, kind='conv', stride=1, dilation=1, padding=0, 
     in_bn / out_bn (BNSlot, optional): x is the output of the convbn + ReLU node that owns in_bn / this node's output has
     exactly one consumer, which holds out_bn as its in_bn."""
     fold = _fold_state(bn)
-    if fold is not None:     # eval step: conv with the folded pack, bias and activation epilogue (FoldState)
+    if fold is not None and fold.train:
+        # training step, frozen BatchNorm: the folded node when the layer has no skip, else the table form of _ConvBNActFn
+        if fold.fold and residual is None and act in FOLD_ACTS and weight.dim() == 4 and x.dtype == fold.dtype:
+            try:
+                return _FoldedConvBNActFn.apply(x, weight, fold, conv_spec(x, weight, kind, stride, dilation, padding), bn, act,
+                                                groups, in_slot, in_bn)
+            except _NoFold:
+                pass
+    elif fold is not None:   # eval step: conv with the folded pack, bias and activation epilogue (FoldState)
         y = _folded_conv_bn_act(fold, x, weight, bn, conv_spec(x, weight, kind, stride, dilation, padding), act, residual, groups)
         if y is not None:
             return y

@@ -14,7 +14,7 @@ early, as the reference does at the last batch of an epoch (torch_implementation
 import os
 import torch
 
-from . import _lib, multitask, ops, parallel
+from . import _lib, densenet, multitask, ops, parallel
 from ._lib import call, ptr, stream_ptr
 
 
@@ -27,6 +27,24 @@ def poly_lr(epoch, itr, total_iter, base_lr=0.005, epoch_total=2400):
     if epoch >= epoch_total:
         T = N - 1
     return base_lr * (1 - T / float(N))
+
+
+def freeze_bn(model):
+    """`-freeze_bn 1` (torch_implementation.py:235-241): every nn.BatchNorm2d goes into eval mode and its weight and bias stop
+    requiring a gradient; returns those modules.  BatchNorm3d (PSMNet's volume stack) is left alone, as upstream.  Unlike
+    upstream this holds under data parallelism too: the reference converts to SyncBatchNorm first (:739), which is not a
+    BatchNorm2d, so its flag freezes nothing there; here the norms are nn.BatchNorm2d on every world size."""
+    mods = [m for m in model.modules() if isinstance(m, torch.nn.BatchNorm2d)]
+    for m in mods:
+        m.eval()
+        if m.weight is not None:
+            m.weight.requires_grad_(False)
+        if m.bias is not None:
+            m.bias.requires_grad_(False)
+    return mods
+
+
+_freeze_bn = freeze_bn      # TrainStep.__init__ has a keyword of the same name
 
 
 def live_ranges(model, idle):
@@ -115,7 +133,7 @@ def reset_capture_generator(device, state, who):
 class TrainStep:
     def __init__(self, model, dtype=torch.bfloat16, lr=None, betas=(0.9, 0.999), eps=1e-7, use_lovasz=True,
                  use_graph=True, world_size=1, process_group=None, use_side_stream=None, loss_fn=None, metrics=None, accumulate=1,
-                 optimizer='adam', momentum=0.9, weight_decay=None, loss=None, class_weights=None):
+                 optimizer='adam', momentum=0.9, weight_decay=None, freeze_bn=False, fold_bn=True, loss=None, class_weights=None):
         self.model, self.dtype, self.use_lovasz = model, dtype, use_lovasz
         # `-optimType` (torch_implementation.py:715-724): the defaults of lr and weight_decay are those of the reference's optimizer
         if optimizer not in ("adam", "sgd"):
@@ -150,6 +168,13 @@ class TrainStep:
         # gradients of K micro-batches add up in the flat buffer, the K-th call all-reduces, steps with their mean and clears
         self.accumulate = max(1, int(accumulate))
         self._micro = 0
+        # `-freeze_bn 1`: the state is established here and again before every pass that runs Python modules (the reference's
+        # epoch loop calls model.train(), which would silently unfreeze); "frozen" itself is a property of the modules
+        # (ops.bn_frozen), so a model frozen by hand computes the same.  fold_bn False: frozen arithmetic, never folded
+        self.freeze_bn, self.fold_bn = bool(freeze_bn), bool(fold_bn)
+        if self.freeze_bn:
+            _freeze_bn(model)
+        self._dense_blocks = densenet.dense_blocks(model)
         self.graphs = {}            # (first, last) call of an accumulation cycle -> (hipGraph, its loss tensor)
         self.world_size, self.pg = world_size, process_group
         parallel.configure(process_group, world_size)     # sync-BN statistics exchange + gradient all-reduce
@@ -190,7 +215,11 @@ class TrainStep:
         # per-step services (ops.StepContext): the first eager step measures / records, later steps use them
         self.ctx = ops.StepContext(self.flat_p.device)
         self.ctx.nbt = []
-        self.pack_desc = None
+        if self.freeze_bn:
+            # frozen norms are constants of a step: one batched launch at its head writes every folded pack, bias and
+            # scale / shift table from the live parameters (recorded during the measuring step)
+            self.ctx.fold = ops.FoldState(dtype, self.flat_p.device, train=True, fold=self.fold_bn)
+        self.pack_desc = self.fold_desc = None
         self.steps_done = 0       # optimizer steps actually EXECUTED (eager steps + graph replays; the recording pass of a capture runs nothing)
         self._capture_fault = None   # tests: a callable invoked inside the capture to make it fail
         self.debug_graph = False     # tests: keep the captured hipGraph inspectable (_lib.graph_node_counts)
@@ -226,21 +255,45 @@ class TrainStep:
         if self.use_side_stream:
             self.ctx.side = torch.cuda.Stream()
             self.ctx.overlap = self.overlap_wgrad
+        fold = self.ctx.fold
+        if fold is not None:
+            fold.finish()
+            frows = fold.rows()
+            for r in frows:     # as above: weight, gamma and beta of every row are slices of this step's parameter buffer
+                if not all(a == 0 or lo <= a < hi for a in ([r[1]] if r[0] == 0 else []) + [r[10], r[11]]):
+                    raise _lib.SdhipError("fold table holds a source outside this step's parameter buffer")
+            self.fold_desc = torch.tensor(frows, dtype=torch.int64, device=self.flat_p.device) if frows else None
         self.nbt_tensors = [t for t, _ in self.ctx.nbt]
         self.nbt_incs = [int(i) for _, i in self.ctx.nbt]
 
     def pack_all(self):
+        if self.fold_desc is not None:      # weights change every step: the folds are rewritten at the head of each one
+            call("sdhip_conv_pack_fold_batch", ptr(self.fold_desc), self.fold_desc.shape[0],
+                 _lib.BF16 if self.dtype == torch.bfloat16 else _lib.F32, stream_ptr())
         if self.ctx.frozen_pack:
             call("sdhip_conv_pack_batch", ptr(self.pack_desc), self.pack_desc.shape[0],
                  _lib.BF16 if self.dtype == torch.bfloat16 else _lib.F32, stream_ptr())
 
     def forward_backward(self, left, right, seg, disp, first=True):
         """first: this call opens an accumulation cycle — the flat gradient buffer is cleared; later calls of the cycle add."""
+        if self.freeze_bn:
+            freeze_bn(self.model)           # a model.train() since the last pass must not unfreeze
+        for name, blk in self._dense_blocks:
+            densenet.block_training(blk, name)      # a half-frozen dense block raises here, before any launch
         ops.set_step_context(self.ctx)
         self.ctx.begin_step()       # one memset clears every zero-initialised workspace of the step
         if first:
             self.flat_g.zero_()
         self.pack_all()             # one launch packs every weight (forward and data-grad orientation)
+        if self.ctx.fold is not None:
+            self.ctx.fold.live = True       # packs and tables hold this step's weights until the optimizer moves them
+        try:
+            return self._forward_backward(left, right, seg, disp)
+        finally:
+            if self.ctx.fold is not None:
+                self.ctx.fold.live = False
+
+    def _forward_backward(self, left, right, seg, disp):
         mt = getattr(self.model, "multiTaskLoss", 0)
         three = getattr(self.model, "three_outputs", False)
         if mt:    # the reference harness's call (torch_implementation.py:146-149): labels from the full one-hot (ATen argmax)
@@ -256,7 +309,7 @@ class TrainStep:
             # (torch_implementation.py:157-158,298); Lovasz stays on outs[2], which the metrics score as well
             loss = ops.train_loss(outs[0], outs[1], outs[2], seg, disp, self.use_lovasz, seg3=outs[4] if three else None,
                                   loss=self.seg_loss, class_weights=self.class_weights)
-        if self.grad_free is None and (mt or three or (self.optimizer == "sgd" and self.weight_decay != 0)):
+        if self.grad_free is None and (mt or three or self.freeze_bn or (self.optimizer == "sgd" and self.weight_decay != 0)):
             self.grad_free = _unreached_parameters(self.model, loss)
         if self.metrics is not None and self.loss_fn is None:
             self.metrics.update(outs[2].detach(), seg, outs[1].detach(), disp)
