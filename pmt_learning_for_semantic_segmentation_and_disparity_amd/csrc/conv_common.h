@@ -47,6 +47,17 @@ struct ConvGeom {
   int D, Do, kd, sd, pad_d;
 };
 
+// Host-side dispatch (conv_fwd.hip, conv_wgrad.hip): what a path function or a launch helper returns, next to SDHIP_OK
+// and the negative SDHIP_ERR_* codes, when the problem is not its own (predicate false, tile does not fit LDS, grid
+// limit): the caller goes on to the next path in its chain.
+constexpr int kNotTaken = 1;
+
+// The image extents and paddings that every family's argument struct carries under these names.
+template <typename Args>
+inline void set_extent(Args& a, const ConvGeom& g) {
+  a.B = g.B; a.H = g.H; a.W = g.W; a.Ho = g.Ho; a.Wo = g.Wo; a.pad_t = g.pad_t; a.pad_l = g.pad_l;
+}
+
 // Stage one input tile (npx = IH*IW pixels, `1<<sh` 16-byte chunks per pixel of channel chunk q) into LDS with
 // the fused prologue.  Loads are issued NB at a time before any LDS store so that NB global loads are in flight
 // per lane (a load->store->load chain would expose the full HBM latency once per chunk).

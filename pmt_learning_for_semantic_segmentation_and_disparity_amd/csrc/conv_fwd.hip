@@ -416,7 +416,7 @@ size_t halo_bytes_of(const ConvGeom& g, int th, int tw, int per_tap) {
   return ((size_t)IH * IW * 128 + 15) & ~(size_t)15;
 }
 
-}  // namespace
+// ---- host-side dispatch ---------------------------------------------------------
 
 // consumer-side BatchNorm finalize of the input prologue (sdhip_conv2d_fwd_bnpro; FastArgs::pin_*)
 struct ProStats {
@@ -427,234 +427,333 @@ struct ProStats {
   const double* pend; double* fold; int pend_ld, pend_nrep, pend_c0, pend_n;
 };
 
-static int conv2d_fwd_impl(const void* x, const void* wpacked, void* y,
-                           const float* bias, const float* in_scale, const float* in_shift,
-                           double* stats, int stats_ld, int stats_nrep,
-                           int B, int H, int W, int Cin, int ldx,
-                           int Ho, int Wo, int Cout, int ldy,
-                           int kh, int kw, int stride, int dil, int pad_t, int pad_l,
-                           int D, int Do, int kd, int sd, int pad_d,
-                           int in_relu, int groups, int act, int accumulate,
-                           int dtype, void* stream, int omul, int ooz, int ooy, int oox,
-                           const void* bx = nullptr, int ldbx = 0, const float* bsc = nullptr, const float* bsh = nullptr,
-                           const void* addend = nullptr, int ldadd = 0, int bx_mode = 0, const ProStats* ps = nullptr) {
-  SDHIP_CHECK_ARG(x && wpacked && y, "conv2d_fwd: null pointer");
-  SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "conv2d_fwd: unknown dtype %d", dtype);
-  SDHIP_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Ho > 0 && Wo > 0, "conv2d_fwd: empty tensor");
-  SDHIP_CHECK_ARG(ldx >= Cin && ldy >= Cout, "conv2d_fwd: pixel stride smaller than channel count");
-  SDHIP_CHECK_ARG(kh >= 1 && kw >= 1 && stride >= 1 && dil >= 1, "conv2d_fwd: bad kernel geometry");
-  SDHIP_CHECK_ARG(groups >= 1 && B % groups == 0, "conv2d_fwd: batch %d not divisible by %d stat groups", B, groups);
-  SDHIP_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "conv2d_fwd: in_scale/in_shift must come together");
-  SDHIP_CHECK_ARG(((uintptr_t)wpacked & 15) == 0, "conv2d_fwd: packed weights must be 16-byte aligned");
-  const int V = dtype == SDHIP_BF16 ? 8 : 4;
-  const int es = conv_esize(dtype);
-  FwdArgs a;
-  a.x = x; a.wp = wpacked; a.y = y; a.bias = bias; a.in_scale = in_scale; a.in_shift = in_shift; a.stats = stats;
-  SDHIP_CHECK_ARG(D >= 1 && Do >= 1 && kd >= 1 && sd >= 1 && (long)B * Do <= 65535, "conv2d_fwd: bad depth geometry");
-  a.g = ConvGeom{B, H, W, Ho, Wo, kh, kw, stride, dil, pad_t, pad_l, D, Do, kd, sd, pad_d};
-  a.Cin = Cin; a.ldx = ldx; a.Cout = Cout; a.Mpad = (Cout + 15) & ~15; a.ldy = ldy;
-  a.in_relu = in_relu; a.groups = groups; a.act = act; a.accumulate = accumulate;
-  a.stats_ld = stats_ld > 0 ? stats_ld : Cout;
-  a.nrep = stats_nrep > 0 ? stats_nrep : 1;
-  a.rep_stride = (long)groups * 2 * a.stats_ld;
-  a.vec_in = (ldx % V == 0) && (((uintptr_t)x & 15) == 0);   // channel tails are masked in stage_tile
-  a.vec_out = (ldy % 4 == 0) && (((uintptr_t)y % (4 * es)) == 0);
+// One call of any of the extern "C" entry points below (never a kernel parameter).  The defaults are the plain
+// convolution: an entry point sets the operands and, of the variant fields, only those that make it differ.
+struct ConvCall {
+  const void* x = nullptr; const void* wp = nullptr; void* y = nullptr;
+  const float* bias = nullptr; const float* in_scale = nullptr; const float* in_shift = nullptr;
+  double* stats = nullptr; int stats_ld = 0, stats_nrep = 1;
+  ConvGeom g{};
+  int Cin = 0, ldx = 0, Cout = 0, ldy = 0;
+  int in_relu = 0, groups = 1, act = 0, accumulate = 0;
+  int dtype = SDHIP_F32;
+  hipStream_t stream = nullptr;
+  // ---- variants ----
+  int omul = 1, ooz = 0, ooy = 0, oox = 0;       // _phase: interleaved output (FastArgs::omul)
+  const void* bx = nullptr; int ldbx = 0;        // _bnbwd: BatchNorm-backward epilogue (FastArgs::bx)
+  const float* bsc = nullptr; const float* bsh = nullptr; int bx_mode = 0;
+  const void* addend = nullptr; int ldadd = 0;   // _add, _bnbwd: y = conv(x) + addend
+  const ProStats* ps = nullptr;                  // _bnpro
+  bool plain() const { return !ps && !bx && !addend && omul == 1; }    // no variant: every kernel family may take it
+  bool flat() const { return g.kd == 1 && g.D == 1 && g.Do == 1; }     // no depth axis
+};
+
+ConvGeom geom2d(int B, int H, int W, int Ho, int Wo, int kh, int kw, int stride, int dil, int pad_t, int pad_l) {
+  return ConvGeom{B, H, W, Ho, Wo, kh, kw, stride, dil, pad_t, pad_l, 1, 1, 1, 1, 0};
+}
+
+// the fields every entry point sets, in the order every entry point receives them
+ConvCall conv_call(const void* x, const void* wpacked, void* y, const ConvGeom& g, int Cin, int ldx, int Cout, int ldy, int dtype, void* stream) {
+  ConvCall c;
+  c.x = x; c.wp = wpacked; c.y = y; c.g = g;
+  c.Cin = Cin; c.ldx = ldx; c.Cout = Cout; c.ldy = ldy;
+  c.dtype = dtype; c.stream = (hipStream_t)stream;
+  return c;
+}
+
+// What the paths share, computed once per call.
+struct ConvPlan {
+  int V, es, Mpad;                       // elements per 16 bytes, element size, Cout rounded up to 16
+  int stats_ld, nrep; long rep_stride;   // normalised statistics layout
+  int vec_in, vec_out;
+  int T, bn; bool big;                   // taps; output channels per workgroup; 8x32 (or 4x16) pixel tiles
+  int rows, chunks_per_row, per_tap_any;
+};
+
+constexpr size_t kLdsMax = 160 * 1024, kLdsSoft = 80 * 1024;   // kLdsSoft: two workgroups per CU
+
+ConvPlan conv_plan(const ConvCall& c) {
+  const ConvGeom& g = c.g;
+  const SdhipDiag& dg = sdhip_diag();
+  ConvPlan d;
+  d.V = c.dtype == SDHIP_BF16 ? 8 : 4;
+  d.es = conv_esize(c.dtype);
+  d.Mpad = (c.Cout + 15) & ~15;
+  d.stats_ld = c.stats_ld > 0 ? c.stats_ld : c.Cout;
+  d.nrep = c.stats_nrep > 0 ? c.stats_nrep : 1;
+  d.rep_stride = (long)c.groups * 2 * d.stats_ld;
+  d.vec_in = (c.ldx % d.V == 0) && (((uintptr_t)c.x & 15) == 0);   // channel tails are masked in stage_tile
+  d.vec_out = (c.ldy % 4 == 0) && (((uintptr_t)c.y % (4 * d.es)) == 0);
   // output channels per workgroup: the widest block that wastes at most a quarter of its MFMA rows on padding
   int bn = 16;
   for (int cand = 128; cand >= 32; cand >>= 1)
-    if ((long)sdhip_cdiv(a.Mpad, cand) * cand * 4 <= (long)a.Mpad * 5) { bn = cand; break; }
+    if ((long)sdhip_cdiv(d.Mpad, cand) * cand * 4 <= (long)d.Mpad * 5) { bn = cand; break; }
   // short reductions (1x1 over <= 128 channels ...) are bound by staging the input tile, not by MFMA rows: one pass
-  if ((long)kh * kw * kd * Cin <= 128 && a.Mpad <= 128) bn = a.Mpad > 64 ? 128 : (a.Mpad > 32 ? 64 : (a.Mpad > 16 ? 32 : 16));
-  const int T = kh * kw;
-  const long blocks_big = (long)sdhip_cdiv(Ho, 8) * sdhip_cdiv(Wo, 32) * B * Do * sdhip_cdiv(a.Mpad, bn);
-  const SdhipDiag& dg = sdhip_diag();
-  const int tune_big = dg.tune_big, tune_split = dg.tune_split;
-  const int tune_ksoft_small = 80, tune_ksoft_big = 80;
-  bool big = (blocks_big >= tune_big && Wo >= 24) || dg.conv_big;
+  if ((long)g.kh * g.kw * g.kd * c.Cin <= 128 && d.Mpad <= 128) bn = d.Mpad > 64 ? 128 : (d.Mpad > 32 ? 64 : (d.Mpad > 16 ? 32 : 16));
+  d.T = g.kh * g.kw;
+  const long blocks_big = (long)sdhip_cdiv(g.Ho, 8) * sdhip_cdiv(g.Wo, 32) * g.B * g.Do * sdhip_cdiv(d.Mpad, bn);
+  d.big = (blocks_big >= dg.tune_big && g.Wo >= 24) || dg.conv_big;
   // stride-2 volumes (hourglass conv1 / conv3 and the adjoint of conv5 / conv6, stackhourglass.py:13-29): the 8x32 tile's halo is
   // 17 x 72 rows per depth tap — 78 KB single-buffered, one workgroup per CU, staging and arithmetic in turn (0.26 PFLOP/s);
   // the 4x16 tile's 9 x 40 rows double-buffer and leave room for a second workgroup
-  if (stride == 2 && kd > 1 && !dg.conv_big && dg.tune_s2_small) big = false;
-  if (!big) {
+  if (g.stride == 2 && g.kd > 1 && !dg.conv_big && dg.tune_s2_small) d.big = false;
+  if (!d.big) {
     // small feature maps (DenseNet blocks 2-4, pooled pyramids): the launch cannot fill 256 CUs with pixel tiles alone,
     // so split the output channels over more workgroups (the input tile is re-read from L2, the serial
     // chunk-by-chunk latency chain per workgroup gets shorter and more of them overlap per CU).
-    const long px_blocks = (long)sdhip_cdiv(Ho, 4) * sdhip_cdiv(Wo, 16) * B * Do;
-    while (bn > 32 && px_blocks * sdhip_cdiv(a.Mpad, bn) < tune_split) bn >>= 1;
+    const long px_blocks = (long)sdhip_cdiv(g.Ho, 4) * sdhip_cdiv(g.Wo, 16) * g.B * g.Do;
+    while (bn > 32 && px_blocks * sdhip_cdiv(d.Mpad, bn) < dg.tune_split) bn >>= 1;
   }
-  const int rows = a.Mpad < bn ? a.Mpad : bn;
-  const size_t kMax = 160 * 1024, kSoft = 80 * 1024;   // kSoft: two workgroups per CU
-  const int CKh = (dtype == SDHIP_BF16 ? 64 : 32);
-  const int chunks_per_row = Cin <= CKh / 2 ? 4 : 8;
-  hipStream_t s = (hipStream_t)stream;
-  const int per_tap_any = (kh > 1 || kw > 1) && dil >= 4 && kd == 1;
-  // ---- thin path (conv_thin.h): <= 8 input channels -> 1 output channel on the vector ALUs ----
-  if (!ps && !bx && !addend && omul == 1 && Cout == 1 && Cin <= V && ldx % V == 0 && ((uintptr_t)x & 15) == 0 && stride == 1 && kd == 1 && D == 1 && Do == 1 && !in_scale &&
-      !accumulate && kh * kw <= kThinMaxT && Ho == H + 2 * pad_t - dil * (kh - 1) && Wo == W + 2 * pad_l - dil * (kw - 1) &&
-      pad_t >= 0 && pad_l >= 0 && !dg.conv_no_thin) {
-    ThinArgs t;
-    t.x = x; t.wp = wpacked; t.y = y; t.bias = bias; t.stats = stats;
-    t.B = B; t.H = H; t.W = W; t.Ho = Ho; t.Wo = Wo; t.kh = kh; t.kw = kw; t.dil = dil; t.pad_t = pad_t; t.pad_l = pad_l;
-    t.Cin = Cin; t.ldx = ldx; t.ldy = ldy; t.Mpad = a.Mpad; t.act = act; t.bpg = B / groups;
-    t.stats_ld = a.stats_ld; t.nrep = a.nrep; t.rep_stride = a.rep_stride;
-    dim3 grid(sdhip_cdiv(Wo, 256), Ho, B);
-    if (dtype == SDHIP_BF16) hipLaunchKernelGGL(conv_thin_fwd_kernel<bf16_t>, grid, dim3(256), 0, s, t);
-    else hipLaunchKernelGGL(conv_thin_fwd_kernel<float>, grid, dim3(256), 0, s, t);
-    SDHIP_LAUNCH_CHECK();
-    return SDHIP_OK;
+  d.bn = bn;
+  d.rows = d.Mpad < bn ? d.Mpad : bn;
+  d.chunks_per_row = c.Cin <= 8 * d.V / 2 ? 4 : 8;   // the whole reduction fits one half row of 8 * V channels
+  d.per_tap_any = (g.kh > 1 || g.kw > 1) && g.dil >= 4 && g.kd == 1;
+  return d;
+}
+
+// Each path below holds its own predicate and the filling of its kernel's argument struct, and returns the launch's
+// status or kNotTaken.  conv2d_fwd_impl calls them in order.
+
+// ---- thin path (conv_thin.h): <= 8 input channels -> 1 output channel on the vector ALUs ----
+int path_thin(const ConvCall& c, const ConvPlan& d) {
+  const ConvGeom& g = c.g;
+  if (!(c.plain() && c.Cout == 1 && c.Cin <= d.V && d.vec_in && g.stride == 1 && c.flat() && !c.in_scale && !c.accumulate &&
+        d.T <= kThinMaxT && g.Ho == g.H + 2 * g.pad_t - g.dil * (g.kh - 1) && g.Wo == g.W + 2 * g.pad_l - g.dil * (g.kw - 1) &&
+        g.pad_t >= 0 && g.pad_l >= 0 && !sdhip_diag().conv_no_thin))
+    return kNotTaken;
+  ThinArgs t{};
+  t.x = c.x; t.wp = c.wp; t.y = c.y; t.bias = c.bias; t.stats = c.stats;
+  set_extent(t, g);
+  t.kh = g.kh; t.kw = g.kw; t.dil = g.dil;
+  t.Cin = c.Cin; t.ldx = c.ldx; t.ldy = c.ldy; t.Mpad = d.Mpad; t.act = c.act; t.bpg = g.B / c.groups;
+  t.stats_ld = d.stats_ld; t.nrep = d.nrep; t.rep_stride = d.rep_stride;
+  dim3 grid(sdhip_cdiv(g.Wo, 256), g.Ho, g.B);
+  if (c.dtype == SDHIP_BF16) hipLaunchKernelGGL(conv_thin_fwd_kernel<bf16_t>, grid, dim3(256), 0, c.stream, t);
+  else hipLaunchKernelGGL(conv_thin_fwd_kernel<float>, grid, dim3(256), 0, c.stream, t);
+  SDHIP_LAUNCH_CHECK_AS("conv2d_fwd_impl");
+  return SDHIP_OK;
+}
+
+// ---- 16..64 input channels into ONE output map (conv_thin.h): taps as the MFMA rows, fixed-order sum over taps ----
+int path_fanin(const ConvCall& c, const ConvPlan& d) {
+  const ConvGeom& g = c.g;
+  if (!(c.plain() && c.dtype == SDHIP_BF16 && fanin_ok(c.Cin, c.Cout, g.kh, g.kw, g.stride, g.dil, g.kd, g.sd, c.ldx, c.x) && !c.in_scale &&
+        !c.accumulate && !c.stats && (long)g.H * g.W * c.ldx < (1L << 31) && !sdhip_diag().conv_no_thin))
+    return kNotTaken;
+  FaninArgs t{};
+  t.x = c.x; t.wp = c.wp; t.y = c.y; t.bias = c.bias;
+  set_extent(t, g);
+  t.kh = g.kh; t.kw = g.kw;
+  t.D = g.D; t.Do = g.Do; t.pad_d = g.pad_d;
+  t.Cin = c.Cin; t.ldx = c.ldx; t.ldy = c.ldy; t.Mpad = d.Mpad; t.act = c.act;
+  t.dpw = 1; t.zsegs = g.Do; t.npxp = 0; t.pitch = 0;
+  return launch_fanin(t, g.kd, c.stream);   // kNotTaken: not launchable (LDS / grid limits) -> the kernels below
+}
+
+// ---- one input channel fanned out to <= 64 output channels (conv_thin.h): taps as the MFMA reduction axis ----
+int path_fanout(const ConvCall& c, const ConvPlan& d) {
+  const ConvGeom& g = c.g;
+  if (!(c.plain() && c.dtype == SDHIP_BF16 && fanout_ok(c.Cin, c.Cout, d.T, g.stride, g.kd, g.sd, c.ldy, c.y) && !c.in_scale &&
+        !c.accumulate && !c.stats && !c.bias && c.act == 0 && (g.kh - 1) * g.dil <= 31 && (g.kw - 1) * g.dil <= 31 &&
+        (long)sdhip_cdiv(g.Ho, 8) * sdhip_cdiv(g.Wo, 32) < (1L << 31) && g.B <= 65535 && !sdhip_diag().conv_no_thin))
+    return kNotTaken;
+  FanArgs t{};
+  t.x = c.x; t.wp = c.wp; t.y = c.y;
+  set_extent(t, g);
+  t.kh = g.kh; t.kw = g.kw; t.dil = g.dil;
+  t.ldx = c.ldx; t.Cout = c.Cout; t.Mpad = d.Mpad; t.ldy = c.ldy;
+  t.D = g.D; t.Do = g.Do; t.kd = g.kd; t.pad_d = g.pad_d; t.dpw = 1; t.zsegs = g.Do;
+  return launch_fanout(t, c.stream);
+}
+
+// ---- 1x1 as a streaming GEMM (conv_gemm.h): bf16, plain stride-1 1x1 over whole images ----
+int path_gemm(const ConvCall& c, const ConvPlan& d) {
+  const ConvGeom& g = c.g;
+  const SdhipDiag& dg = sdhip_diag();
+  if (!(c.plain() && c.dtype == SDHIP_BF16 && g.kh == 1 && g.kw == 1 && c.flat() && g.stride == 1 && g.pad_t == 0 && g.pad_l == 0 &&
+        g.Ho == g.H && g.Wo == g.W && !c.accumulate && !dg.conv_generic && !dg.conv_no_gemm))
+    return kNotTaken;
+  GemmArgs a{};
+  a.seg[0] = GemmSeg{c.x, c.ldx, c.Cin, 0};
+  a.seg[1] = GemmSeg{nullptr, 0, 0, 0};
+  a.nseg = 1;
+  a.wp = c.wp; a.y = c.y; a.bias = c.bias; a.in_scale = c.in_scale; a.in_shift = c.in_shift; a.stats = c.stats;
+  a.ldy = c.ldy; a.Cout = c.Cout; a.Mpad = d.Mpad; a.K = c.Cin; a.in_relu = c.in_relu; a.act = c.act;
+  a.M = (long)g.B * g.H * g.W; a.H = g.H; a.W = g.W; a.ppg = a.M / c.groups;
+  a.stats_ld = d.stats_ld; a.nrep = d.nrep; a.rep_stride = d.rep_stride;
+  if (!gemm1x1_ok(a, (c.in_scale || c.stats) ? c.groups : 1)) return kNotTaken;
+  return launch_gemm_any(a, c.stream);
+}
+
+// ---- persistent whole-CU kernel (conv_band.h), bf16, weights resident in LDS.  What its 2-D and 3-D forms share: ----
+bool band_common_ok(const ConvCall& c) {
+  const ConvGeom& g = c.g;
+  return !c.ps && !c.bx && c.omul == 1 && c.dtype == SDHIP_BF16 && g.stride == 1 && g.dil == 1 && !c.in_scale &&
+         !((c.accumulate || c.addend) && c.stats) && !(c.accumulate && c.addend) &&
+         (!c.addend || (c.ldadd % 8 == 0 && ((uintptr_t)c.addend & 15) == 0)) && c.Cin % 8 == 0 &&
+         c.ldx % 8 == 0 && ((uintptr_t)c.x & 15) == 0 && c.ldy % 8 == 0 && ((uintptr_t)c.y & 15) == 0 &&
+         (long)g.B * g.D * g.H * g.W * c.ldx * 2 < (long)kBandOob && band_ok(sdhip_cdiv(g.Ho, 16) * sdhip_cdiv(g.Wo, 32) * g.B * g.Do) &&
+         !sdhip_diag().conv_generic && !sdhip_diag().conv_no_band;
+}
+
+BandArgs band_args(const ConvCall& c, const ConvPlan& d) {
+  const ConvGeom& g = c.g;
+  BandArgs f{};
+  f.x = c.x; f.wp = c.wp; f.y = c.y; f.bias = c.bias; f.stats = c.stats;
+  set_extent(f, g);
+  f.D = g.D; f.Do = g.Do; f.pad_d = g.pad_d;
+  f.Cin = c.Cin; f.ldx = c.ldx; f.Cout = c.Cout; f.Mpad = d.Mpad; f.ldy = c.ldy;
+  f.bpg = (g.B / c.groups) * g.Do; f.act = c.act; f.stats_ld = d.stats_ld; f.nrep = d.nrep; f.rep_stride = d.rep_stride;
+  f.res = c.addend ? c.addend : (c.accumulate ? c.y : nullptr); f.ldres = c.addend ? c.ldadd : c.ldy;
+  return f;
+}
+
+// the full-resolution 5x5 layers (<= 64 channels either side) and the 3x3 layers with <= 32 input channels
+int path_band2d(const ConvCall& c, const ConvPlan& d) {
+  const ConvGeom& g = c.g;
+  const bool band5 = g.kh == 5 && g.kw == 5 && (c.Cin <= 32 || c.Cin == 64);
+  const bool band3 = g.kh == 3 && g.kw == 3 && c.Cin <= 32 && !sdhip_diag().conv_no_band3;
+  if (!((band5 || band3) && c.flat() && d.Mpad <= 64 && d.Mpad >= 32 && band_common_ok(c))) return kNotTaken;
+  BandArgs f = band_args(c, d);
+  f.pad_d = 0;   // no depth axis: whatever the caller passed for it
+  return band5 ? launch_band<5>(f, c.stream) : launch_band<3>(f, c.stream);
+}
+
+// the same kernel over volumes: 3x3x3, <= 32 channels on both sides (PSMNet's 32 -> 32 stack, stackhourglass.py:59-102):
+// every depth tap is a chunk of its tile (its own input slice and 3x3 weights), z runs fastest over a workgroup's tiles
+int path_band3d(const ConvCall& c, const ConvPlan& d) {
+  const ConvGeom& g = c.g;
+  if (!(g.kh == 3 && g.kw == 3 && g.kd == 3 && g.sd == 1 && c.Cin <= 32 && d.Mpad == 32 && band_common_ok(c) && !sdhip_diag().conv_no_band3))
+    return kNotTaken;
+  BandArgs f = band_args(c, d);
+  return launch_band<3, 3>(f, c.stream);
+}
+
+// ---- fast path (conv_fast.h): 16-byte-aligned pixels on both sides, halo-tile mode.  The only path that takes the
+//      variants (phase output, BatchNorm-backward epilogue, consumer-side BatchNorm finalize) ----
+int path_fast(const ConvCall& c, const ConvPlan& d) {
+  const ConvGeom& g = c.g;
+  if (!(!d.per_tap_any && d.vec_in && d.vec_out && (long)g.H * g.W * c.ldx < (1L << 31) && !sdhip_diag().conv_generic)) return kNotTaken;
+  const int tune_ksoft_small = 80, tune_ksoft_big = 80;
+  const int CKh = 8 * d.V, T = d.T, bn = d.bn;
+  const int ks = d.chunks_per_row == 4 ? 1 : 2;
+  const int rb = 64 * ks, px_per_round = 256 / (4 * ks);
+  const ProStats* ps = c.ps;
+  FastArgs f{};
+  f.x = c.x; f.wp = c.wp; f.y = c.y; f.bias = c.bias; f.in_scale = c.in_scale; f.in_shift = c.in_shift; f.stats = c.stats;
+  set_extent(f, g);
+  f.kh = g.kh; f.kw = g.kw; f.stride = g.stride; f.dil = g.dil;
+  f.D = g.D; f.Do = g.Do; f.kd = g.kd; f.sd = g.sd; f.pad_d = g.pad_d;
+  f.Cin = c.Cin; f.ldx = c.ldx; f.Cout = c.Cout; f.Mpad = d.Mpad; f.ldy = c.ldy;
+  f.in_relu = c.in_relu; f.bpg = g.B / c.groups; f.act = c.act; f.accumulate = c.accumulate;
+  f.stats_ld = d.stats_ld; f.nrep = d.nrep; f.rep_stride = d.rep_stride; f.tail = (c.Cin % d.V) != 0;
+  f.omul = c.omul; f.ooz = c.ooz; f.ooy = c.ooy; f.oox = c.oox;
+  f.bx = c.bx; f.ldbx = c.ldbx; f.bsc = c.bsc; f.bsh = c.bsh;
+  f.res = c.bx ? c.addend : nullptr; f.ldres = c.ldadd; f.bx_mode = c.bx_mode; f.bx_groups = c.groups;
+  f.dma = !c.in_scale && !f.tail && !ps;
+  if (ps) {
+    f.pin_stats = ps->stats; f.pin_ld = ps->ld; f.pin_nrep = ps->nrep; f.pin_groups = c.groups; f.pin_gamma = ps->gamma; f.pin_beta = ps->beta;
+    f.pin_scale = ps->scale; f.pin_shift = ps->shift; f.pin_mean = ps->mean; f.pin_invstd = ps->invstd; f.pin_rmean = ps->rmean; f.pin_rvar = ps->rvar;
+    f.pin_eps = ps->eps; f.pin_momentum = ps->momentum; f.pin_count = ps->count;
+    f.pend_stats = ps->pend; f.pin_fold = ps->fold; f.pend_ld = ps->pend_ld; f.pend_nrep = ps->pend_nrep; f.pend_c0 = ps->pend_c0; f.pend_n = ps->pend ? ps->pend_n : 0;
   }
-  // ---- 16..64 input channels into ONE output map (conv_thin.h): taps as the MFMA rows, fixed-order sum over taps ----
-  if (!ps && !bx && !addend && omul == 1 && dtype == SDHIP_BF16 && fanin_ok(Cin, Cout, kh, kw, stride, dil, kd, sd, ldx, x) && !in_scale && !accumulate &&
-      !stats && (long)H * W * ldx < (1L << 31) && !dg.conv_no_thin) {
-    FaninArgs t;
-    t.x = x; t.wp = wpacked; t.y = y; t.bias = bias;
-    t.B = B; t.H = H; t.W = W; t.Ho = Ho; t.Wo = Wo; t.kh = kh; t.kw = kw; t.pad_t = pad_t; t.pad_l = pad_l;
-    t.D = D; t.Do = Do; t.pad_d = pad_d;
-    t.Cin = Cin; t.ldx = ldx; t.ldy = ldy; t.Mpad = a.Mpad; t.act = act;
-    t.dpw = 1; t.zsegs = Do; t.npxp = 0; t.pitch = 0;
-    const int rc = launch_fanin(t, kd, s);
-    if (rc != 1) return rc;                     // 1: not launchable (LDS / grid limits) -> the kernels below
-  }
-  // ---- one input channel fanned out to <= 64 output channels (conv_thin.h): taps as the MFMA reduction axis ----
-  if (!ps && !bx && !addend && omul == 1 && dtype == SDHIP_BF16 && fanout_ok(Cin, Cout, kh * kw, stride, kd, sd, ldy, y) && !in_scale &&
-      !accumulate && !stats && !bias && act == 0 && (kh - 1) * dil <= 31 && (kw - 1) * dil <= 31 && (long)sdhip_cdiv(Ho, 8) * sdhip_cdiv(Wo, 32) < (1L << 31) &&
-      B <= 65535 && !dg.conv_no_thin) {
-    FanArgs t;
-    t.x = x; t.wp = wpacked; t.y = y;
-    t.B = B; t.H = H; t.W = W; t.Ho = Ho; t.Wo = Wo; t.kh = kh; t.kw = kw; t.dil = dil; t.pad_t = pad_t; t.pad_l = pad_l;
-    t.ldx = ldx; t.Cout = Cout; t.Mpad = a.Mpad; t.ldy = ldy;
-    t.D = D; t.Do = Do; t.kd = kd; t.pad_d = pad_d; t.dpw = 1; t.zsegs = Do;
-    return launch_fanout(t, s);
-  }
-  // ---- 1x1 as a streaming GEMM (conv_gemm.h): bf16, plain stride-1 1x1 over whole images ----
-  if (!ps && !bx && !addend && omul == 1 && dtype == SDHIP_BF16 && kh == 1 && kw == 1 && kd == 1 && stride == 1 && pad_t == 0 && pad_l == 0 && D == 1 && Do == 1 &&
-      Ho == H && Wo == W && !accumulate && !dg.conv_generic && !dg.conv_no_gemm) {
-    GemmArgs g;
-    g.seg[0] = GemmSeg{x, ldx, Cin, 0};
-    g.seg[1] = GemmSeg{nullptr, 0, 0, 0};
-    g.nseg = 1;
-    g.wp = wpacked; g.y = y; g.bias = bias; g.in_scale = in_scale; g.in_shift = in_shift; g.stats = stats;
-    g.ldy = ldy; g.Cout = Cout; g.Mpad = a.Mpad; g.K = Cin; g.in_relu = in_relu; g.act = act;
-    g.M = (long)B * H * W; g.H = H; g.W = W; g.ppg = g.M / groups;
-    g.stats_ld = a.stats_ld; g.nrep = a.nrep; g.rep_stride = a.rep_stride;
-    if (gemm1x1_ok(g, (in_scale || stats) ? groups : 1)) return launch_gemm_any(g, s);
-  }
-  // ---- persistent whole-CU kernel (conv_band.h): the full-resolution 5x5 layers (<= 64 channels either side) and the 3x3
-  //      layers with <= 32 input channels (weights resident in LDS), bf16 ----
-  const bool band5 = kh == 5 && kw == 5 && (Cin <= 32 || Cin == 64);
-  const bool band3 = kh == 3 && kw == 3 && Cin <= 32 && !dg.conv_no_band3;
-  if (!ps && !bx && omul == 1 && dtype == SDHIP_BF16 && (band5 || band3) && kd == 1 && stride == 1 && dil == 1 && D == 1 && Do == 1 && !in_scale &&
-      !((accumulate || addend) && stats) && !(accumulate && addend) && (!addend || (ldadd % 8 == 0 && ((uintptr_t)addend & 15) == 0)) && Cin % 8 == 0 && a.Mpad <= 64 && a.Mpad >= 32 && ldx % 8 == 0 && ((uintptr_t)x & 15) == 0 && ldy % 8 == 0 && ((uintptr_t)y & 15) == 0 &&
-      (long)B * H * W * ldx * 2 < (long)kBandOob && band_ok(sdhip_cdiv(Ho, 16) * sdhip_cdiv(Wo, 32) * B) && !dg.conv_generic && !dg.conv_no_band) {
-    BandArgs f;
-    f.x = x; f.wp = wpacked; f.y = y; f.bias = bias; f.stats = stats;
-    f.B = B; f.H = H; f.W = W; f.Ho = Ho; f.Wo = Wo; f.pad_t = pad_t; f.pad_l = pad_l;
-    f.Cin = Cin; f.ldx = ldx; f.Cout = Cout; f.Mpad = a.Mpad; f.ldy = ldy;
-    f.bpg = B / groups; f.act = act; f.stats_ld = a.stats_ld; f.nrep = a.nrep; f.rep_stride = a.rep_stride;
-    f.res = addend ? addend : (accumulate ? y : nullptr); f.ldres = addend ? ldadd : ldy;
-    f.D = 1; f.Do = 1; f.pad_d = 0;
-    return band5 ? launch_band<5>(f, s) : launch_band<3>(f, s);
-  }
-  // ---- the same kernel over volumes: 3x3x3, <= 32 channels on both sides (PSMNet's 32 -> 32 stack, stackhourglass.py:59-102):
-  //      every depth tap is a chunk of its tile (its own input slice and 3x3 weights), z runs fastest over a workgroup's tiles ----
-  if (!ps && !bx && omul == 1 && dtype == SDHIP_BF16 && kh == 3 && kw == 3 && kd == 3 && sd == 1 && stride == 1 && dil == 1 && Cin <= 32 && Cin % 8 == 0 &&
-      a.Mpad == 32 && !in_scale && !((accumulate || addend) && stats) && !(accumulate && addend) &&
-      (!addend || (ldadd % 8 == 0 && ((uintptr_t)addend & 15) == 0)) && ldx % 8 == 0 && ((uintptr_t)x & 15) == 0 && ldy % 8 == 0 && ((uintptr_t)y & 15) == 0 &&
-      (long)B * D * H * W * ldx * 2 < (long)kBandOob && band_ok(sdhip_cdiv(Ho, 16) * sdhip_cdiv(Wo, 32) * B * Do) && !dg.conv_generic && !dg.conv_no_band && !dg.conv_no_band3) {
-    BandArgs f;
-    f.x = x; f.wp = wpacked; f.y = y; f.bias = bias; f.stats = stats;
-    f.B = B; f.H = H; f.W = W; f.Ho = Ho; f.Wo = Wo; f.pad_t = pad_t; f.pad_l = pad_l;
-    f.D = D; f.Do = Do; f.pad_d = pad_d;
-    f.Cin = Cin; f.ldx = ldx; f.Cout = Cout; f.Mpad = a.Mpad; f.ldy = ldy;
-    f.bpg = (B / groups) * Do; f.act = act; f.stats_ld = a.stats_ld; f.nrep = a.nrep; f.rep_stride = a.rep_stride;
-    f.res = addend ? addend : (accumulate ? y : nullptr); f.ldres = addend ? ldadd : ldy;
-    return launch_band<3, 3>(f, s);
-  }
-  if (addend && !bx) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_add: only the persistent 5x5 kernel adds a second tensor in its epilogue (bf16, <= 64 channels, >= 192 tiles of 16x32)");
-  // ---- fast path (conv_fast.h): 16-byte-aligned pixels on both sides, halo-tile mode ----
-  if (!per_tap_any && ldx % V == 0 && ((uintptr_t)x & 15) == 0 && a.vec_out &&
-      (long)H * W * ldx < (1L << 31) && !dg.conv_generic) {
-    const int ks = chunks_per_row == 4 ? 1 : 2;
-    const int rb = 64 * ks, px_per_round = 256 / (4 * ks);
-    FastArgs f;
-    f.x = x; f.wp = wpacked; f.y = y; f.bias = bias; f.in_scale = in_scale; f.in_shift = in_shift; f.stats = stats;
-    f.B = B; f.H = H; f.W = W; f.Ho = Ho; f.Wo = Wo; f.kh = kh; f.kw = kw; f.stride = stride; f.dil = dil; f.pad_t = pad_t; f.pad_l = pad_l;
-    f.D = D; f.Do = Do; f.kd = kd; f.sd = sd; f.pad_d = pad_d;
-    f.Cin = Cin; f.ldx = ldx; f.Cout = Cout; f.Mpad = a.Mpad; f.ldy = ldy;
-    f.in_relu = in_relu; f.bpg = B / groups; f.act = act; f.accumulate = accumulate;
-    f.stats_ld = a.stats_ld; f.nrep = a.nrep; f.rep_stride = a.rep_stride; f.tail = (Cin % V) != 0;
-    f.omul = omul; f.ooz = ooz; f.ooy = ooy; f.oox = oox;
-    f.bx = bx; f.ldbx = ldbx; f.bsc = bsc; f.bsh = bsh;
-    f.res = bx ? addend : nullptr; f.ldres = ldadd; f.bx_mode = bx_mode; f.bx_groups = groups;
-    f.dma = !in_scale && !f.tail && !ps;
-    f.pin_stats = nullptr;
-    if (ps) {
-      f.pin_stats = ps->stats; f.pin_ld = ps->ld; f.pin_nrep = ps->nrep; f.pin_groups = groups; f.pin_gamma = ps->gamma; f.pin_beta = ps->beta;
-      f.pin_scale = ps->scale; f.pin_shift = ps->shift; f.pin_mean = ps->mean; f.pin_invstd = ps->invstd; f.pin_rmean = ps->rmean; f.pin_rvar = ps->rvar;
-      f.pin_eps = ps->eps; f.pin_momentum = ps->momentum; f.pin_count = ps->count;
-      f.pend_stats = ps->pend; f.pin_fold = ps->fold; f.pend_ld = ps->pend_ld; f.pend_nrep = ps->pend_nrep; f.pend_c0 = ps->pend_c0; f.pend_n = ps->pend ? ps->pend_n : 0;
+  bool fbig = d.big;   // this path's own copy: the generic path starts from d.big again
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    const int th = fbig ? 8 : 4, tw = fbig ? 32 : 16;
+    const int IH = (th - 1) * g.stride + (g.kh - 1) * g.dil + 1, IW = (tw - 1) * g.stride + (g.kw - 1) * g.dil + 1;
+    const int IWp = (IW + 7) & ~7;
+    const int hrows = ((IH * IWp + px_per_round - 1) / px_per_round) * px_per_round;   // whole load rounds
+    const int nqq_f = g.kd * (ks == 2 ? sdhip_cdiv(c.Cin, CKh) : 1);
+    const size_t hb = (size_t)hrows * rb * ((fbig || nqq_f == 1) ? 1 : 2);   // small tiles double-buffer the halo across chunks
+    if (!fbig && hrows > ((f.dma && ks == 1) ? 6 : 5) * px_per_round) { fbig = true; continue; }   // small-tile halo prefetch plan: 5 / 6 rounds (conv_fast.h HPF)
+    auto wbuf = [&](int tgv) { return (size_t)(((tgv * bn + px_per_round - 1) / px_per_round) * px_per_round) * rb; };
+    int tg = T;
+    const size_t ksoft_f = (size_t)(fbig ? tune_ksoft_big : tune_ksoft_small) * 1024;
+    size_t lds;
+    if (nqq_f == 1 && hb + wbuf(T) <= ksoft_f) {
+      lds = hb + wbuf(T);              // the whole kernel is ONE stage: all taps resident, no second weight buffer
+    } else {
+      while (tg > 1 && hb + 2 * wbuf(tg) > ksoft_f) --tg;
+      lds = hb + 2 * wbuf(tg);
     }
-    bool fbig = big;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-      const int th = fbig ? 8 : 4, tw = fbig ? 32 : 16;
-      const int IH = (th - 1) * stride + (kh - 1) * dil + 1, IW = (tw - 1) * stride + (kw - 1) * dil + 1;
-      const int IWp = (IW + 7) & ~7;
-      const int hrows = ((IH * IWp + px_per_round - 1) / px_per_round) * px_per_round;   // whole load rounds
-      const int nqq_f = kd * (ks == 2 ? sdhip_cdiv(Cin, CKh) : 1);
-      const size_t hb = (size_t)hrows * rb * ((fbig || nqq_f == 1) ? 1 : 2);   // small tiles double-buffer the halo across chunks
-      if (!fbig && hrows > ((f.dma && ks == 1) ? 6 : 5) * px_per_round) { fbig = true; continue; }   // small-tile halo prefetch plan: 5 / 6 rounds (conv_fast.h HPF)
-      auto wbuf = [&](int tgv) { return (size_t)(((tgv * bn + px_per_round - 1) / px_per_round) * px_per_round) * rb; };
-      int tg = T;
-      const size_t ksoft_f = (size_t)(fbig ? tune_ksoft_big : tune_ksoft_small) * 1024;
-      size_t lds;
-      if (nqq_f == 1 && hb + wbuf(T) <= ksoft_f) {
-        lds = hb + wbuf(T);              // the whole kernel is ONE stage: all taps resident, no second weight buffer
-      } else {
-        while (tg > 1 && hb + 2 * wbuf(tg) > ksoft_f) --tg;
-        lds = hb + 2 * wbuf(tg);
-      }
-      if (lds < 4096) lds = 4096;
-      f.pin_off = 0; f.pin_cs = 0;
-      if (ps) { f.pin_off = (int)lds; f.pin_cs = (Cin + 63) & ~63; lds += 2 * (size_t)f.pin_cs * sizeof(float); }   // the finalize table sits behind everything else
-      if (lds > kMax) { if (!fbig) break; fbig = false; continue; }
-      f.tg = tg;
-      f.magic_iwp = IWp > 1 ? (unsigned)(0x100000000ULL / (unsigned)IWp) + 1u : 0u;
-      f.tiles_w = sdhip_cdiv(Wo, tw);
-      f.magic_tw = f.tiles_w > 1 ? (unsigned)(0x100000000ULL / (unsigned)f.tiles_w) + 1u : 0u;
-      f.ntg = sdhip_cdiv(T, tg);
-      if ((long)f.tiles_w * sdhip_cdiv(Ho, th) >= 65536) break;   // fast_div range: general kernel for gigantic images
-      return dtype == SDHIP_BF16 ? launch_fast_any<bf16_t>(f, fbig, ks, bn, lds, s) : launch_fast_any<float>(f, fbig, ks, bn, lds, s);
-    }
+    if (lds < 4096) lds = 4096;
+    f.pin_off = 0; f.pin_cs = 0;
+    if (ps) { f.pin_off = (int)lds; f.pin_cs = (c.Cin + 63) & ~63; lds += 2 * (size_t)f.pin_cs * sizeof(float); }   // the finalize table sits behind everything else
+    if (lds > kLdsMax) { if (!fbig) break; fbig = false; continue; }
+    f.tg = tg;
+    f.magic_iwp = IWp > 1 ? (unsigned)(0x100000000ULL / (unsigned)IWp) + 1u : 0u;
+    f.tiles_w = sdhip_cdiv(g.Wo, tw);
+    f.magic_tw = f.tiles_w > 1 ? (unsigned)(0x100000000ULL / (unsigned)f.tiles_w) + 1u : 0u;
+    f.ntg = sdhip_cdiv(T, tg);
+    if ((long)f.tiles_w * sdhip_cdiv(g.Ho, th) >= 65536) break;   // fast_div range: general kernel for gigantic images
+    return c.dtype == SDHIP_BF16 ? launch_fast_any<bf16_t>(f, fbig, ks, bn, lds, c.stream) : launch_fast_any<float>(f, fbig, ks, bn, lds, c.stream);
   }
-  if (omul != 1) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_phase: interleaved output needs the aligned fast path (ldx %% 8, ldy %% 4)");
-  if (ps) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_bnpro: needs the aligned fast path (ldx %% 8, ldy %% 4, halo tile within LDS)");
-  if (bx) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_bnbwd: needs the aligned fast path (ldx %% 8, ldy %% 4, halo tile within LDS)");
+  return kNotTaken;
+}
+
+// ---- general kernel (this file): any layout, per-tap mode for strongly dilated kernels.  The last path: never kNotTaken ----
+int path_generic(const ConvCall& c, const ConvPlan& d) {
+  const ConvGeom& g = c.g;
+  const int bn = d.bn;
+  FwdArgs a{};
+  a.x = c.x; a.wp = c.wp; a.y = c.y; a.bias = c.bias; a.in_scale = c.in_scale; a.in_shift = c.in_shift; a.stats = c.stats;
+  a.g = g;
+  a.Cin = c.Cin; a.ldx = c.ldx; a.Cout = c.Cout; a.Mpad = d.Mpad; a.ldy = c.ldy;
+  a.in_relu = c.in_relu; a.groups = c.groups; a.act = c.act; a.accumulate = c.accumulate;
+  a.vec_in = d.vec_in; a.vec_out = d.vec_out;
+  a.stats_ld = d.stats_ld; a.nrep = d.nrep; a.rep_stride = d.rep_stride;
+  bool big = d.big;
   for (int attempt = 0; attempt < 2; ++attempt) {
     const int th = big ? 8 : 4, tw = big ? 32 : 16;
-    const int per_tap = per_tap_any;   // halo would be >= 4x the tile in each direction's holes
-    const size_t halo = halo_bytes_of(a.g, th, tw, per_tap);
-    const long halo_loads = (long)(halo / 128) * chunks_per_row;
+    const int per_tap = d.per_tap_any;   // halo would be >= 4x the tile in each direction's holes
+    const size_t halo = halo_bytes_of(g, th, tw, per_tap);
+    const long halo_loads = (long)(halo / 128) * d.chunks_per_row;
     // register-prefetched (double-buffered) halo: small tiles, at most 4 loads per lane, vector loads only
-    const int pf = !per_tap && !big && a.vec_in && (Cin % V == 0) && halo_loads <= 4 * 256 && 2 * halo + 2 * (size_t)bn * 128 <= kSoft;
+    const int pf = !per_tap && !big && d.vec_in && (c.Cin % d.V == 0) && halo_loads <= 4 * 256 && 2 * halo + 2 * (size_t)bn * 128 <= kLdsSoft;
     // weights: at most 4 loads per lane per stage => tg*rows*chunks_per_row <= 1024
-    int tg = per_tap ? 1 : 1024 / (rows * chunks_per_row);
+    int tg = per_tap ? 1 : 1024 / (d.rows * d.chunks_per_row);
     if (tg < 1) tg = 1;
-    if (tg > T) tg = T;
+    if (tg > d.T) tg = d.T;
     const size_t hb = halo * (pf ? 2 : 1);
-    while (tg > 1 && hb + 2 * (size_t)tg * bn * 128 > kSoft) --tg;
+    while (tg > 1 && hb + 2 * (size_t)tg * bn * 128 > kLdsSoft) --tg;
     size_t lds = hb + 2 * (size_t)tg * bn * 128;
     if (lds < 4096) lds = 4096;   // stats reduction scratch
-    if (lds > kMax) {
+    if (lds > kLdsMax) {
       if (big) { big = false; continue; }
-      SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd: halo tile of a %dx%d kernel with dilation %d does not fit LDS", kh, kw, dil);
+      SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd: halo tile of a %dx%d kernel with dilation %d does not fit LDS", g.kh, g.kw, g.dil);
     }
-    a.tg = tg; a.pf_halo = pf; a.sh = chunks_per_row == 4 ? 2 : 3; a.per_tap = per_tap;
-    if (dtype == SDHIP_BF16)
-      return big ? launch_bn<bf16_t, 8, 32>(a, bn, lds, s) : launch_bn<bf16_t, 4, 16>(a, bn, lds, s);
-    return big ? launch_bn<float, 8, 32>(a, bn, lds, s) : launch_bn<float, 4, 16>(a, bn, lds, s);
+    a.tg = tg; a.pf_halo = pf; a.sh = d.chunks_per_row == 4 ? 2 : 3; a.per_tap = per_tap;
+    if (c.dtype == SDHIP_BF16)
+      return big ? launch_bn<bf16_t, 8, 32>(a, bn, lds, c.stream) : launch_bn<bf16_t, 4, 16>(a, bn, lds, c.stream);
+    return big ? launch_bn<float, 8, 32>(a, bn, lds, c.stream) : launch_bn<float, 4, 16>(a, bn, lds, c.stream);
   }
   SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd: no tile configuration fits");
 }
+
+int conv2d_fwd_impl(const ConvCall& c) {
+  const ConvGeom& g = c.g;
+  SDHIP_CHECK_ARG(c.x && c.wp && c.y, "conv2d_fwd: null pointer");
+  SDHIP_CHECK_ARG(c.dtype == SDHIP_F32 || c.dtype == SDHIP_BF16, "conv2d_fwd: unknown dtype %d", c.dtype);
+  SDHIP_CHECK_ARG(g.B > 0 && g.H > 0 && g.W > 0 && c.Cin > 0 && c.Cout > 0 && g.Ho > 0 && g.Wo > 0, "conv2d_fwd: empty tensor");
+  SDHIP_CHECK_ARG(c.ldx >= c.Cin && c.ldy >= c.Cout, "conv2d_fwd: pixel stride smaller than channel count");
+  SDHIP_CHECK_ARG(g.kh >= 1 && g.kw >= 1 && g.stride >= 1 && g.dil >= 1, "conv2d_fwd: bad kernel geometry");
+  SDHIP_CHECK_ARG(c.groups >= 1 && g.B % c.groups == 0, "conv2d_fwd: batch %d not divisible by %d stat groups", g.B, c.groups);
+  SDHIP_CHECK_ARG((c.in_scale == nullptr) == (c.in_shift == nullptr), "conv2d_fwd: in_scale/in_shift must come together");
+  SDHIP_CHECK_ARG(((uintptr_t)c.wp & 15) == 0, "conv2d_fwd: packed weights must be 16-byte aligned");
+  SDHIP_CHECK_ARG(g.D >= 1 && g.Do >= 1 && g.kd >= 1 && g.sd >= 1 && (long)g.B * g.Do <= 65535, "conv2d_fwd: bad depth geometry");
+  const ConvPlan d = conv_plan(c);
+  int rc;
+  for (auto path : {path_thin, path_fanin, path_fanout, path_gemm, path_band2d, path_band3d})
+    if ((rc = path(c, d)) != kNotTaken) return rc;
+  if (c.addend && !c.bx) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_add: only the persistent 5x5 kernel adds a second tensor in its epilogue (bf16, <= 64 channels, >= 192 tiles of 16x32)");
+  if ((rc = path_fast(c, d)) != kNotTaken) return rc;
+  if (c.omul != 1) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_phase: interleaved output needs the aligned fast path (ldx %% 8, ldy %% 4)");
+  if (c.ps) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_bnpro: needs the aligned fast path (ldx %% 8, ldy %% 4, halo tile within LDS)");
+  if (c.bx) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_bnbwd: needs the aligned fast path (ldx %% 8, ldy %% 4, halo tile within LDS)");
+  return path_generic(c, d);
+}
+
+}  // namespace
 
 // 1x1 convolution over the channel concatenation of up to two tensors, either of which may be a nearest-neighbour
 // upsampled map (see include/sdhip.h).  bf16 only: the f32 parity path materialises the concatenation.
@@ -664,18 +763,17 @@ extern "C" int sdhip_conv1x1_cat_fwd(const void* x0, int ld0, int c0, int us0, c
   SDHIP_CHECK_ARG(x0 && wpacked && y && c0 > 0 && B > 0 && H > 0 && W > 0 && Cout > 0, "conv1x1_cat_fwd: bad arguments");
   SDHIP_CHECK_ARG(dtype == SDHIP_BF16, "conv1x1_cat_fwd: bf16 only");
   SDHIP_CHECK_ARG((x1 == nullptr) == (c1 == 0) && us0 >= 0 && us1 >= 0 && us0 < 8 && us1 < 8, "conv1x1_cat_fwd: bad second segment");
-  GemmArgs g;
+  GemmArgs g{};
   g.seg[0] = GemmSeg{x0, ld0, c0, us0};
   g.seg[1] = GemmSeg{x1, ld1, c1, us1};
   g.nseg = x1 ? 2 : 1;
-  g.wp = wpacked; g.y = y; g.bias = bias; g.in_scale = nullptr; g.in_shift = nullptr; g.stats = nullptr;
-  g.ldy = ldy; g.Cout = Cout; g.Mpad = (Cout + 15) & ~15; g.K = c0 + c1; g.in_relu = 0; g.act = act;
+  g.wp = wpacked; g.y = y; g.bias = bias;
+  g.ldy = ldy; g.Cout = Cout; g.Mpad = (Cout + 15) & ~15; g.K = c0 + c1; g.act = act;
   g.M = (long)B * H * W; g.H = H; g.W = W; g.ppg = g.M;
   g.stats_ld = Cout; g.nrep = 1; g.rep_stride = 0;
   if (!gemm1x1_ok(g, 1, true)) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv1x1_cat_fwd: operands not 16-byte aligned / grid not divisible by the upsampling factor");
   return launch_gemm_any(g, (hipStream_t)stream);
 }
-
 
 extern "C" int sdhip_conv2d_fwd(const void* x, const void* wpacked, void* y,
                                 const float* bias, const float* in_scale, const float* in_shift,
@@ -686,8 +784,12 @@ extern "C" int sdhip_conv2d_fwd(const void* x, const void* wpacked, void* y,
                                 int D, int Do, int kd, int sd, int pad_d,
                                 int in_relu, int groups, int act, int accumulate,
                                 int dtype, void* stream) {
-  return conv2d_fwd_impl(x, wpacked, y, bias, in_scale, in_shift, stats, stats_ld, stats_nrep, B, H, W, Cin, ldx, Ho, Wo, Cout, ldy,
-                         kh, kw, stride, dil, pad_t, pad_l, D, Do, kd, sd, pad_d, in_relu, groups, act, accumulate, dtype, stream, 1, 0, 0, 0);
+  ConvCall c = conv_call(x, wpacked, y, ConvGeom{B, H, W, Ho, Wo, kh, kw, stride, dil, pad_t, pad_l, D, Do, kd, sd, pad_d},
+                         Cin, ldx, Cout, ldy, dtype, stream);
+  c.bias = bias; c.in_scale = in_scale; c.in_shift = in_shift;
+  c.stats = stats; c.stats_ld = stats_ld; c.stats_nrep = stats_nrep;
+  c.in_relu = in_relu; c.groups = groups; c.act = act; c.accumulate = accumulate;
+  return conv2d_fwd_impl(c);
 }
 
 // y = conv(relu(BatchNorm_train(x))) with the BatchNorm finalized inside the launch (see include/sdhip.h).
@@ -708,9 +810,11 @@ extern "C" int sdhip_conv2d_fwd_bnpro(const void* x, const void* wpacked, void* 
                   "conv2d_fwd_bnpro: bad pending-statistics slice (folding needs single-replica slab statistics)");
   ProStats ps{in_stats, in_stats_ld, in_stats_nrep, gamma, beta, scale_out, shift_out, mean_out, invstd_out, running_mean, running_var,
               eps, momentum, count, pend_stats, in_stats, pend_ld, pend_nrep, pend_c0, pend_n};
-  return conv2d_fwd_impl(x, wpacked, y, nullptr, nullptr, nullptr, out_stats, out_stats_ld, out_stats_nrep, B, H, W, Cin, ldx, Ho, Wo, Cout, ldy,
-                         kh, kw, 1, 1, pad_t, pad_l, 1, 1, 1, 1, 0, 1, groups, 0, 0, dtype, stream, 1, 0, 0, 0, nullptr, 0, nullptr, nullptr,
-                         nullptr, 0, 0, &ps);
+  ConvCall c = conv_call(x, wpacked, y, geom2d(B, H, W, Ho, Wo, kh, kw, 1, 1, pad_t, pad_l), Cin, ldx, Cout, ldy, dtype, stream);
+  c.stats = out_stats; c.stats_ld = out_stats_ld; c.stats_nrep = out_stats_nrep;
+  c.in_relu = 1; c.groups = groups;
+  c.ps = &ps;
+  return conv2d_fwd_impl(c);
 }
 
 // y = conv(x) + addend (see include/sdhip.h).
@@ -718,8 +822,9 @@ extern "C" int sdhip_conv2d_fwd_add(const void* x, const void* wpacked, void* y,
                                     int B, int H, int W, int Cin, int ldx, int Ho, int Wo, int Cout, int ldy,
                                     int kh, int kw, int pad_t, int pad_l, int dtype, void* stream) {
   SDHIP_CHECK_ARG(addend && ldadd >= Cout, "conv2d_fwd_add: addend missing / pixel stride smaller than Cout");
-  return conv2d_fwd_impl(x, wpacked, y, nullptr, nullptr, nullptr, nullptr, 0, 1, B, H, W, Cin, ldx, Ho, Wo, Cout, ldy,
-                         kh, kw, 1, 1, pad_t, pad_l, 1, 1, 1, 1, 0, 0, 1, 0, 0, dtype, stream, 1, 0, 0, 0, nullptr, 0, nullptr, nullptr, addend, ldadd);
+  ConvCall c = conv_call(x, wpacked, y, geom2d(B, H, W, Ho, Wo, kh, kw, 1, 1, pad_t, pad_l), Cin, ldx, Cout, ldy, dtype, stream);
+  c.addend = addend; c.ldadd = ldadd;
+  return conv2d_fwd_impl(c);
 }
 
 // Data gradient of a stride-1 convolution whose input was relu(BatchNorm(u)): y = the gradient w.r.t. that input, and the
@@ -734,9 +839,12 @@ extern "C" int sdhip_conv2d_fwd_bnbwd(const void* x, const void* wpacked, void* 
                   ((uintptr_t)scale & 15) == 0 && ((uintptr_t)shift & 15) == 0,
                   "conv2d_fwd_bnbwd: sums / u / scale / shift missing or misaligned (Cout %% 4, ldu %% 4)");
   SDHIP_CHECK_ARG(!addend || (ldadd >= Cout && ldadd % 4 == 0 && ((uintptr_t)addend & 7) == 0), "conv2d_fwd_bnbwd: addend misaligned");
-  return conv2d_fwd_impl(x, wpacked, y, nullptr, nullptr, nullptr, sums, sums_ld, sums_nrep, B, H, W, Cin, ldx, Ho, Wo, Cout, ldy,
-                         kh, kw, 1, dil, pad_t, pad_l, 1, 1, 1, 1, 0, 0, groups, 0, 0, dtype, stream, 1, 0, 0, 0, u, ldu, scale, shift,
-                         addend, ldadd, mode);
+  ConvCall c = conv_call(x, wpacked, y, geom2d(B, H, W, Ho, Wo, kh, kw, 1, dil, pad_t, pad_l), Cin, ldx, Cout, ldy, dtype, stream);
+  c.stats = sums; c.stats_ld = sums_ld; c.stats_nrep = sums_nrep;
+  c.groups = groups;
+  c.bx = u; c.ldbx = ldu; c.bsc = scale; c.bsh = shift; c.bx_mode = mode;
+  c.addend = addend; c.ldadd = ldadd;
+  return conv2d_fwd_impl(c);
 }
 
 // One sub-pixel phase of a stride-2 transposed convolution (see include/sdhip.h): a stride-1 correlation whose outputs are
@@ -745,6 +853,10 @@ extern "C" int sdhip_conv2d_fwd_phase(const void* x, const void* wpacked, void* 
                                       int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int kh, int kw,
                                       int D, int kd, int groups, int off_d, int off_h, int off_w, int dtype, void* stream) {
   SDHIP_CHECK_ARG(off_d >= 0 && off_d < 2 && off_h >= 0 && off_h < 2 && off_w >= 0 && off_w < 2, "conv2d_fwd_phase: phase offsets are 0 or 1");
-  return conv2d_fwd_impl(x, wpacked, y, nullptr, nullptr, nullptr, stats, stats_ld, stats_nrep, B, H, W, Cin, ldx, H, W, Cout, ldy,
-                         kh, kw, 1, 1, 0, 0, D, D, kd, 1, 0, 0, groups, 0, 0, dtype, stream, 2, off_d, off_h, off_w);
+  ConvCall c = conv_call(x, wpacked, y, ConvGeom{B, H, W, H, W, kh, kw, 1, 1, 0, 0, D, D, kd, 1, 0}, Cin, ldx, Cout, ldy, dtype, stream);
+  c.stats = stats; c.stats_ld = stats_ld; c.stats_nrep = stats_nrep;
+  c.groups = groups;
+  c.omul = 2; c.ooz = off_d; c.ooy = off_h; c.oox = off_w;
+  return conv2d_fwd_impl(c);
 }
+

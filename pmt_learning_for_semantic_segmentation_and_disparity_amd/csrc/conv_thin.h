@@ -481,13 +481,13 @@ inline int launch_fanin(FaninArgs a, int kd, hipStream_t s) {
   a.npxp = (npx + 15) & ~15;
   a.pitch = a.npxp + 4;
   const size_t lds = (size_t)a.kh * a.kw * kd * a.pitch * sizeof(float);
-  if (lds > 64 * 1024) return 1;                                    // (the caller takes another kernel)
+  if (lds > 64 * 1024) return kNotTaken;                                    // (the caller takes another kernel)
   int dpw = kd == 1 ? 1 : 12;
   if (dpw > a.Do) dpw = a.Do;
   const long tiles = (long)sdhip_cdiv(a.Ho, 8) * sdhip_cdiv(a.Wo, 32) * a.B;
   while (dpw > 4 && tiles * sdhip_cdiv(a.Do, dpw) < 1024) --dpw;
   a.dpw = dpw; a.zsegs = sdhip_cdiv(a.Do, dpw);
-  if ((long)a.B * a.zsegs > 65535) return 1;
+  if ((long)a.B * a.zsegs > 65535) return kNotTaken;
   dim3 grid(sdhip_cdiv(a.Ho, 8) * sdhip_cdiv(a.Wo, 32), a.B * a.zsegs);
   if (kd == 3 && a.kh == 3 && a.kw == 3) hipLaunchKernelGGL((conv_fanin_kernel<3, 1, 3>), grid, dim3(256), lds, s, a);
   else if (kd == 3) hipLaunchKernelGGL((conv_fanin_kernel<3, 1>), grid, dim3(256), lds, s, a);

@@ -229,7 +229,7 @@ int launch(const WgArgs& a, hipStream_t s) {
   const ConvGeom& g = a.g;
   const int IH = (TH - 1) * g.stride + (g.kh - 1) * g.dil + 1, IW = (TW - 1) * g.stride + (g.kw - 1) * g.dil + 1;
   const size_t lds = (((size_t)IH * IW * 128 + 15) & ~(size_t)15) + (size_t)TH * TW * 128;
-  if (lds > 160 * 1024) return 1;  // caller falls back to a smaller tile
+  if (lds > 160 * 1024) return kNotTaken;  // caller falls back to a smaller tile
   static size_t attr_set = 0;
   if (lds > 64 * 1024 && attr_set == 0) {
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
@@ -252,12 +252,12 @@ template <typename T, int MAXT, int MB>
 int launch_tile(const WgArgs& a, bool wide, hipStream_t s) {
   if (wide) {
     const int rc = launch<T, 8, 32, MAXT, MB>(a, s);
-    if (rc != 1) return rc;
+    if (rc != kNotTaken) return rc;
     const int rc2 = launch<T, 4, 32, MAXT, MB>(a, s);
-    if (rc2 != 1) return rc2;
+    if (rc2 != kNotTaken) return rc2;
   }
   const int rc = launch<T, 4, 16, MAXT, MB>(a, s);
-  if (rc == 1) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_wgrad: halo tile does not fit LDS (k=%dx%d dil=%d)", a.g.kh, a.g.kw, a.g.dil);
+  if (rc == kNotTaken) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_wgrad: halo tile does not fit LDS (k=%dx%d dil=%d)", a.g.kh, a.g.kw, a.g.dil);
   return rc;
 }
 
@@ -393,128 +393,154 @@ extern "C" int sdhip_conv_unpack_wgrad(const float* acc, float* grad, int M, int
   return SDHIP_OK;
 }
 
+namespace {
+
+// The paths of one layer, in the order wgrad_one tries them.  Each takes the layer as wgrad_one has put it into the general
+// kernel's WgArgs (operands, geometry, Mpad, tap grouping, vector flags), holds its own predicate and the filling of its
+// kernel's argument struct, and returns the launch's status or kNotTaken.
+
+// ---- thin path (conv_thin.h): <= 8 input channels -> 1 output channel ----
+int wg_thin(const WgArgs& a, int dtype, hipStream_t s) {
+  const ConvGeom& g = a.g;
+  const int V = dtype == SDHIP_BF16 ? 8 : 4, T = g.kh * g.kw;
+  if (!(a.Cout == 1 && a.Cin <= V && a.vec_x && g.stride == 1 && g.kd == 1 && g.D == 1 && g.Do == 1 && !a.in_scale && T <= 25 &&
+        g.Ho == g.H + 2 * g.pad_t - g.dil * (g.kh - 1) && g.Wo == g.W + 2 * g.pad_l - g.dil * (g.kw - 1) && g.pad_t >= 0 && g.pad_l >= 0 &&
+        !sdhip_diag().conv_no_thin))
+    return kNotTaken;
+  ThinWgArgs t{};
+  t.x = a.x; t.dy = a.dy; t.dwp = a.dwp; t.dbias = a.dbias;
+  set_extent(t, g);
+  t.kh = g.kh; t.kw = g.kw; t.dil = g.dil;
+  t.Cin = a.Cin; t.ldx = a.ldx; t.lddy = a.lddy; t.Mpad = a.Mpad;
+  const long npix = (long)g.B * g.Ho * g.Wo;
+  // large maps, bf16: the LDS-tiled kernel (lanes = (tap, channel pair), 8 x 64 pixel tiles)
+  {
+    const int IHt = 8 + (g.kh - 1) * g.dil, IWt = 64 + (g.kw - 1) * g.dil, P = IWt + 2;
+    const size_t lds = (size_t)IHt * P * 16 + 8 * 64 * 2;
+    const bool no_tiled = sdhip_diag().thin_wgrad_reg;   // diagnostics: A/B against the register kernel
+    if (dtype == SDHIP_BF16 && T > 9 && 8 * T <= 256 && lds <= 60 * 1024 && g.Wo >= 64 && g.Ho >= 8 && npix >= 65536 && !no_tiled) {
+      const int th = sdhip_cdiv(g.Ho, 8), tw = sdhip_cdiv(g.Wo, 64);
+      const int ntiles = g.B * th * tw;
+      // measured at 8 x 256 x 512 (tools/gpu_thinwg.py): 128 / 256 / 512 / 1024 / 2048 workgroups -> 96 / 51 / 33 / 33 / 38 us:
+      // the single-buffered tiles want several workgroups per CU; past 1024 the T x 8 flush atomics per workgroup show
+      const int cap = sdhip_diag().tune_thin_blocks;
+      const int blocks = ntiles < cap ? ntiles : cap;
+      hipLaunchKernelGGL((conv_thin_wgrad_tiled_kernel<25>), dim3(blocks), dim3(256), lds, s, t, th, tw, IHt, IWt, P);
+      SDHIP_LAUNCH_CHECK_AS("wgrad_one");
+      return SDHIP_OK;
+    }
+  }
+  const int blocks = (int)(npix / 256 < 1024 ? (npix + 255) / 256 : 1024);   // measured: 128 / 1024 workgroups -> 150 / 95 us
+  if (dtype == SDHIP_BF16) {
+    if (T <= 9) hipLaunchKernelGGL((conv_thin_wgrad_kernel<bf16_t, 9>), dim3(blocks), dim3(256), 0, s, t);
+    else hipLaunchKernelGGL((conv_thin_wgrad_kernel<bf16_t, 25>), dim3(blocks), dim3(256), 0, s, t);
+  } else {
+    if (T <= 9) hipLaunchKernelGGL((conv_thin_wgrad_kernel<float, 9>), dim3(blocks), dim3(256), 0, s, t);
+    else hipLaunchKernelGGL((conv_thin_wgrad_kernel<float, 25>), dim3(blocks), dim3(256), 0, s, t);
+  }
+  SDHIP_LAUNCH_CHECK_AS("wgrad_one");
+  return SDHIP_OK;
+}
+
+// ---- one output map, 9..32 input channels, <= 32 taps (conv_wgrad_single.h): taps as the MFMA row axis ----
+int wg_single(const WgArgs& a, int dtype, hipStream_t s) {
+  const ConvGeom& g = a.g;
+  if (!(dtype == SDHIP_BF16 && single_wgrad_ok(a.Cin, a.Cout, g.kh * g.kw, g.stride, g.dil, g.kd, g.sd, a.ldx, a.x) && !a.in_scale && !a.dbias &&
+        !sdhip_diag().conv_no_thin))
+    return kNotTaken;
+  SingleWgArgs t{};
+  t.x = a.x; t.dy = a.dy; t.dwp = a.dwp;
+  set_extent(t, g);
+  t.kh = g.kh; t.kw = g.kw;
+  t.D = g.D; t.Do = g.Do; t.kd = g.kd; t.pad_d = g.pad_d;
+  t.Cin = a.Cin; t.ldx = a.ldx; t.lddy = a.lddy; t.Mpad = a.Mpad; t.dpw = 1; t.zsegs = g.D;
+  return launch_single_wgrad(t, s);   // kNotTaken: halo does not fit -> the kernels below
+}
+
+// ---- bf16 fast path (conv_wgrad_fast.h): 16-byte-aligned pixels on both operands.  plan != nullptr: the layer is only
+//      PLANNED (*planned = true, nothing launched) ----
+int wg_fast(const WgArgs& a, int dtype, hipStream_t s, WgfPlan* plan, bool* planned) {
+  const ConvGeom& g = a.g;
+  if (!(dtype == SDHIP_BF16 && a.vec_x && a.vec_dy && (long)g.H * g.W * a.ldx < (1L << 31) && (long)g.Ho * g.Wo * a.lddy < (1L << 31) &&
+        !sdhip_diag().wgrad_generic))
+    return kNotTaken;
+  const int T = g.kh * g.kw;
+  WgfArgs f{};
+  f.x = a.x; f.dy = a.dy; f.dwp = a.dwp; f.dbias = a.dbias; f.in_scale = a.in_scale; f.in_shift = a.in_shift;
+  set_extent(f, g);
+  f.kh = g.kh; f.kw = g.kw; f.stride = g.stride; f.dil = g.dil;
+  f.D = g.D; f.Do = g.Do; f.kd = g.kd; f.sd = g.sd; f.pad_d = g.pad_d;
+  f.Cin = a.Cin; f.ldx = a.ldx; f.Cout = a.Cout; f.Mpad = a.Mpad; f.lddy = a.lddy;
+  f.in_relu = a.in_relu; f.bpg = g.B / a.groups;
+  f.tpb = a.tpb; f.ntg = a.ntg; f.nq = a.nq;
+  if (T == 1 && a.tpb == 1) { f.tpb = 1; f.ntg = 1; }
+  f.qb = 0; f.qsh = 0; f.nq_tot = a.nq;
+  // <= 32 channels on both sides, 3x3 (x3), stride 1: 64-byte LDS rows, all depth taps per workgroup (conv_wgrad_half.h)
+  if (a.Cin <= 32 && a.Cout <= 32 && g.kh == 3 && g.kw == 3 && g.stride == 1 && g.dil == 1 && g.sd == 1 && (g.kd == 1 || g.kd == 3) && !a.in_scale &&
+      !a.dbias && g.Wo >= 24 && !sdhip_diag().wgrad_no_half32) {
+    WgfPlan pl;
+    const int rc = g.kd == 3 ? plan_wg32<3>(f, pl) : plan_wg32<1>(f, pl);
+    if (rc != SDHIP_OK) return rc;
+    if (plan) { *plan = pl; *planned = true; return SDHIP_OK; }
+    return launch_wgf_plan(pl, s);
+  }
+  // 1x1 with many input channels (DenseNet bottlenecks / transitions): pack 2 or 4 channel chunks per workgroup
+  const bool no_pack = sdhip_diag().wgrad_no_pack;   // diagnostics: A/B against the unpacked kernel
+  // Measured (tools/gpu_wgrad1x1_ab.sh): it pays on large maps and wide outputs (192->128 at 16x64x128: 88 -> 52 us,
+  // 1024->512 at 16x16x32: 62 -> 54 us); on the small maps of the deep DenseNet blocks the sweep is bound by the
+  // per-tile DMA latency either way and the unpacked kernel's smaller tiles win (1024->128 at 16x16x32: 21 vs 31 us).
+  const bool pack_pays = a.Cout >= 256 || (long)g.B * g.H * g.W >= 100000;
+  if (T == 1 && g.kd == 1 && g.stride == 1 && g.pad_t == 0 && g.pad_l == 0 && g.Ho == g.H && g.Wo == g.W && a.nq >= 2 && a.Cout > 32 && !no_pack &&
+      (pack_pays || sdhip_diag().wgrad_force_pack)) {
+    WgfArgs p = f;
+    p.qb = a.nq >= 3 ? 4 : 2; p.qsh = p.qb == 4 ? 2 : 1;
+    p.kh = 1; p.kw = p.qb; p.tpb = p.qb; p.ntg = 1; p.nq = sdhip_cdiv(a.nq, p.qb);
+    const int rc = a.in_scale ? launch_wgf_packed<false>(p, s, plan) : launch_wgf_packed<true>(p, s, plan);
+    if (rc != kNotTaken) { if (plan && rc == SDHIP_OK) *planned = true; return rc; }
+  }
+  // MB = 32 regroups the taps over two wave groups: the tap grouping must match the instantiation (see launch_wgf_taps)
+  const int rc = a.in_scale ? launch_wgf_taps<false>(f, T, s, plan) : launch_wgf_taps<true>(f, T, s, plan);
+  if (plan && rc == SDHIP_OK) *planned = true;
+  return rc;   // kNotTaken: no tile fits LDS -> general kernel
+}
+
+}  // namespace
+
 // One layer.  plan == nullptr: launch now.  plan != nullptr: a layer of the bf16 fast path is only PLANNED (*planned = true,
 // nothing launched) so that the caller can group it with others; every other path launches as usual.
-static int wgrad_one(const void* x, const void* dy, float* dw_packed, float* dbias,
-                     const float* in_scale, const float* in_shift,
-                     int B, int H, int W, int Cin, int ldx,
-                     int Ho, int Wo, int Cout, int lddy,
-                     int kh, int kw, int stride, int dil, int pad_t, int pad_l,
-                     int D, int Do, int kd, int sd, int pad_d,
-                     int in_relu, int groups, int prezeroed, int dtype, void* stream, WgfPlan* plan, bool* planned) {
-  SDHIP_CHECK_ARG(x && dy && dw_packed, "conv2d_wgrad: null pointer");
+static int wgrad_one(const SdhipWgradItem& it, int prezeroed, int dtype, void* stream, WgfPlan* plan, bool* planned) {
+  SDHIP_CHECK_ARG(it.x && it.dy && it.dw_packed, "conv2d_wgrad: null pointer");
   SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "conv2d_wgrad: unknown dtype %d", dtype);
-  SDHIP_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Ho > 0 && Wo > 0, "conv2d_wgrad: empty tensor");
-  SDHIP_CHECK_ARG(ldx >= Cin && lddy >= Cout, "conv2d_wgrad: pixel stride smaller than channel count");
-  SDHIP_CHECK_ARG(groups >= 1 && B % groups == 0, "conv2d_wgrad: batch %d not divisible by %d stat groups", B, groups);
-  SDHIP_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "conv2d_wgrad: in_scale/in_shift must come together");
-  const int V = dtype == SDHIP_BF16 ? 8 : 4, CK = 8 * V, T = kh * kw;
-  WgArgs a;
-  a.x = x; a.dy = dy; a.dwp = dw_packed; a.dbias = dbias; a.in_scale = in_scale; a.in_shift = in_shift;
-  SDHIP_CHECK_ARG(D >= 1 && Do >= 1 && kd >= 1 && sd >= 1, "conv2d_wgrad: bad depth geometry");
-  a.g = ConvGeom{B, H, W, Ho, Wo, kh, kw, stride, dil, pad_t, pad_l, D, Do, kd, sd, pad_d};
-  a.Cin = Cin; a.ldx = ldx; a.Cout = Cout; a.Mpad = (Cout + 15) & ~15; a.lddy = lddy;
-  a.in_relu = in_relu; a.groups = groups;
-  a.nq = sdhip_cdiv(Cin, CK);
+  SDHIP_CHECK_ARG(it.B > 0 && it.H > 0 && it.W > 0 && it.Cin > 0 && it.Cout > 0 && it.Ho > 0 && it.Wo > 0, "conv2d_wgrad: empty tensor");
+  SDHIP_CHECK_ARG(it.ldx >= it.Cin && it.lddy >= it.Cout, "conv2d_wgrad: pixel stride smaller than channel count");
+  SDHIP_CHECK_ARG(it.groups >= 1 && it.B % it.groups == 0, "conv2d_wgrad: batch %d not divisible by %d stat groups", it.B, it.groups);
+  SDHIP_CHECK_ARG((it.in_scale == nullptr) == (it.in_shift == nullptr), "conv2d_wgrad: in_scale/in_shift must come together");
+  SDHIP_CHECK_ARG(it.D >= 1 && it.Do >= 1 && it.kd >= 1 && it.sd >= 1, "conv2d_wgrad: bad depth geometry");
+  const int V = dtype == SDHIP_BF16 ? 8 : 4, CK = 8 * V, T = it.kh * it.kw;
+  WgArgs a{};
+  a.x = it.x; a.dy = it.dy; a.dwp = it.dw_packed; a.dbias = it.dbias; a.in_scale = it.in_scale; a.in_shift = it.in_shift;
+  a.g = ConvGeom{it.B, it.H, it.W, it.Ho, it.Wo, it.kh, it.kw, it.stride, it.dil, it.pad_t, it.pad_l, it.D, it.Do, it.kd, it.sd, it.pad_d};
+  a.Cin = it.Cin; a.ldx = it.ldx; a.Cout = it.Cout; a.Mpad = (it.Cout + 15) & ~15; a.lddy = it.lddy;
+  a.in_relu = it.in_relu; a.groups = it.groups;
+  a.nq = sdhip_cdiv(it.Cin, CK);
   const int maxt = T <= 9 ? 9 : 25;          // taps a workgroup keeps in registers
   a.ntg = sdhip_cdiv(T, maxt);
   a.tpb = sdhip_cdiv(T, a.ntg);              // balanced tap groups (49 -> 25, 24)
   a.ntg = sdhip_cdiv(T, a.tpb);
-  a.vec_x = (ldx % V == 0) && (((uintptr_t)x & 15) == 0);      // channel tails are masked in stage_tile
-  a.vec_dy = (lddy % V == 0) && (((uintptr_t)dy & 15) == 0);
+  a.vec_x = (it.ldx % V == 0) && (((uintptr_t)it.x & 15) == 0);      // channel tails are masked in stage_tile
+  a.vec_dy = (it.lddy % V == 0) && (((uintptr_t)it.dy & 15) == 0);
   hipStream_t s = (hipStream_t)stream;
-  const long n = (long)kd * sdhip_conv_packed_elems(Cout, Cin, T, dtype);
+  const long n = (long)it.kd * sdhip_conv_packed_elems(it.Cout, it.Cin, T, dtype);
   if (!prezeroed) {
-    if (sdhip_zero_async(dw_packed, n * sizeof(float), s) != hipSuccess) SDHIP_FAIL(SDHIP_ERR_LAUNCH, "conv2d_wgrad: memset failed");
-    if (dbias && sdhip_zero_async(dbias, (size_t)Cout * sizeof(float), s) != hipSuccess) SDHIP_FAIL(SDHIP_ERR_LAUNCH, "conv2d_wgrad: memset failed");
+    if (sdhip_zero_async(it.dw_packed, n * sizeof(float), s) != hipSuccess) SDHIP_FAIL(SDHIP_ERR_LAUNCH, "conv2d_wgrad: memset failed");
+    if (it.dbias && sdhip_zero_async(it.dbias, (size_t)it.Cout * sizeof(float), s) != hipSuccess) SDHIP_FAIL(SDHIP_ERR_LAUNCH, "conv2d_wgrad: memset failed");
   }
-  // ---- thin path (conv_thin.h): <= 8 input channels -> 1 output channel ----
-  if (Cout == 1 && Cin <= V && a.vec_x && stride == 1 && kd == 1 && D == 1 && Do == 1 && !in_scale && T <= 25 &&
-      Ho == H + 2 * pad_t - dil * (kh - 1) && Wo == W + 2 * pad_l - dil * (kw - 1) && pad_t >= 0 && pad_l >= 0 &&
-      !sdhip_diag().conv_no_thin) {
-    ThinWgArgs t;
-    t.x = x; t.dy = dy; t.dwp = dw_packed; t.dbias = dbias;
-    t.B = B; t.H = H; t.W = W; t.Ho = Ho; t.Wo = Wo; t.kh = kh; t.kw = kw; t.dil = dil; t.pad_t = pad_t; t.pad_l = pad_l;
-    t.Cin = Cin; t.ldx = ldx; t.lddy = lddy; t.Mpad = a.Mpad;
-    const long npix = (long)B * Ho * Wo;
-    // large maps, bf16: the LDS-tiled kernel (lanes = (tap, channel pair), 8 x 64 pixel tiles)
-    {
-      const int IHt = 8 + (kh - 1) * dil, IWt = 64 + (kw - 1) * dil, P = IWt + 2;
-      const size_t lds = (size_t)IHt * P * 16 + 8 * 64 * 2;
-      const bool no_tiled = sdhip_diag().thin_wgrad_reg;   // diagnostics: A/B against the register kernel
-      if (dtype == SDHIP_BF16 && T > 9 && 8 * T <= 256 && lds <= 60 * 1024 && Wo >= 64 && Ho >= 8 && npix >= 65536 && !no_tiled) {
-        const int th = sdhip_cdiv(Ho, 8), tw = sdhip_cdiv(Wo, 64);
-        const int ntiles = B * th * tw;
-        // measured at 8 x 256 x 512 (tools/gpu_thinwg.py): 128 / 256 / 512 / 1024 / 2048 workgroups -> 96 / 51 / 33 / 33 / 38 us:
-        // the single-buffered tiles want several workgroups per CU; past 1024 the T x 8 flush atomics per workgroup show
-        const int cap = sdhip_diag().tune_thin_blocks;
-        const int blocks = ntiles < cap ? ntiles : cap;
-        hipLaunchKernelGGL((conv_thin_wgrad_tiled_kernel<25>), dim3(blocks), dim3(256), lds, s, t, th, tw, IHt, IWt, P);
-        SDHIP_LAUNCH_CHECK();
-        return SDHIP_OK;
-      }
-    }
-    const int blocks = (int)(npix / 256 < 1024 ? (npix + 255) / 256 : 1024);   // measured: 128 / 1024 workgroups -> 150 / 95 us
-    if (dtype == SDHIP_BF16) {
-      if (T <= 9) hipLaunchKernelGGL((conv_thin_wgrad_kernel<bf16_t, 9>), dim3(blocks), dim3(256), 0, s, t);
-      else hipLaunchKernelGGL((conv_thin_wgrad_kernel<bf16_t, 25>), dim3(blocks), dim3(256), 0, s, t);
-    } else {
-      if (T <= 9) hipLaunchKernelGGL((conv_thin_wgrad_kernel<float, 9>), dim3(blocks), dim3(256), 0, s, t);
-      else hipLaunchKernelGGL((conv_thin_wgrad_kernel<float, 25>), dim3(blocks), dim3(256), 0, s, t);
-    }
-    SDHIP_LAUNCH_CHECK();
-    return SDHIP_OK;
-  }
-  // ---- one output map, 9..32 input channels, <= 32 taps (conv_wgrad_single.h): taps as the MFMA row axis ----
-  if (dtype == SDHIP_BF16 && single_wgrad_ok(Cin, Cout, T, stride, dil, kd, sd, ldx, x) && !in_scale && !dbias && !sdhip_diag().conv_no_thin) {
-    SingleWgArgs t;
-    t.x = x; t.dy = dy; t.dwp = dw_packed;
-    t.B = B; t.H = H; t.W = W; t.Ho = Ho; t.Wo = Wo; t.kh = kh; t.kw = kw; t.pad_t = pad_t; t.pad_l = pad_l;
-    t.D = D; t.Do = Do; t.kd = kd; t.pad_d = pad_d;
-    t.Cin = Cin; t.ldx = ldx; t.lddy = lddy; t.Mpad = a.Mpad; t.dpw = 1; t.zsegs = D;
-    const int rc = launch_single_wgrad(t, s);
-    if (rc != 1) return rc;                     // 1: halo does not fit -> the kernels below
-  }
-  // ---- bf16 fast path (conv_wgrad_fast.h): 16-byte-aligned pixels on both operands ----
-  if (dtype == SDHIP_BF16 && a.vec_x && a.vec_dy && (long)H * W * ldx < (1L << 31) && (long)Ho * Wo * lddy < (1L << 31) &&
-      !sdhip_diag().wgrad_generic) {
-    WgfArgs f;
-    f.x = x; f.dy = dy; f.dwp = dw_packed; f.dbias = dbias; f.in_scale = in_scale; f.in_shift = in_shift;
-    f.B = B; f.H = H; f.W = W; f.Ho = Ho; f.Wo = Wo; f.kh = kh; f.kw = kw; f.stride = stride; f.dil = dil; f.pad_t = pad_t; f.pad_l = pad_l;
-    f.D = D; f.Do = Do; f.kd = kd; f.sd = sd; f.pad_d = pad_d;
-    f.Cin = Cin; f.ldx = ldx; f.Cout = Cout; f.Mpad = a.Mpad; f.lddy = lddy;
-    f.in_relu = in_relu; f.bpg = B / groups;
-    f.tpb = a.tpb; f.ntg = a.ntg; f.nq = a.nq;
-    if (T == 1 && a.tpb == 1) { f.tpb = 1; f.ntg = 1; }
-    f.qb = 0; f.qsh = 0; f.nq_tot = a.nq;
-    // <= 32 channels on both sides, 3x3 (x3), stride 1: 64-byte LDS rows, all depth taps per workgroup (conv_wgrad_half.h)
-    if (Cin <= 32 && Cout <= 32 && kh == 3 && kw == 3 && stride == 1 && dil == 1 && sd == 1 && (kd == 1 || kd == 3) && !in_scale && !dbias &&
-        Wo >= 24 && !sdhip_diag().wgrad_no_half32) {
-      WgfPlan pl;
-      const int rc = kd == 3 ? plan_wg32<3>(f, pl) : plan_wg32<1>(f, pl);
-      if (rc != SDHIP_OK) return rc;
-      if (plan) { *plan = pl; *planned = true; return SDHIP_OK; }
-      return launch_wgf_plan(pl, s);
-    }
-    // 1x1 with many input channels (DenseNet bottlenecks / transitions): pack 2 or 4 channel chunks per workgroup
-    const bool no_pack = sdhip_diag().wgrad_no_pack;   // diagnostics: A/B against the unpacked kernel
-    // Measured (tools/gpu_wgrad1x1_ab.sh): it pays on large maps and wide outputs (192->128 at 16x64x128: 88 -> 52 us,
-    // 1024->512 at 16x16x32: 62 -> 54 us); on the small maps of the deep DenseNet blocks the sweep is bound by the
-    // per-tile DMA latency either way and the unpacked kernel's smaller tiles win (1024->128 at 16x16x32: 21 vs 31 us).
-    const bool pack_pays = Cout >= 256 || (long)B * H * W >= 100000;
-    if (T == 1 && kd == 1 && stride == 1 && pad_t == 0 && pad_l == 0 && Ho == H && Wo == W && a.nq >= 2 && Cout > 32 && !no_pack &&
-        (pack_pays || sdhip_diag().wgrad_force_pack)) {
-      WgfArgs g = f;
-      g.qb = a.nq >= 3 ? 4 : 2; g.qsh = g.qb == 4 ? 2 : 1;
-      g.kh = 1; g.kw = g.qb; g.tpb = g.qb; g.ntg = 1; g.nq = sdhip_cdiv(a.nq, g.qb);
-      const int rc = in_scale ? launch_wgf_packed<false>(g, s, plan) : launch_wgf_packed<true>(g, s, plan);
-      if (rc != 1) { if (plan && rc == SDHIP_OK) *planned = true; return rc; }
-    }
-    // MB = 32 regroups the taps over two wave groups: the tap grouping must match the instantiation (see launch_wgf_taps)
-    const int rc = in_scale ? launch_wgf_taps<false>(f, T, s, plan) : launch_wgf_taps<true>(f, T, s, plan);
-    if (rc != 1) { if (plan && rc == SDHIP_OK) *planned = true; return rc; }   // 1: no tile fits LDS -> general kernel below
-  }
-  const bool wide = Wo >= 24;
+  int rc;
+  if ((rc = wg_thin(a, dtype, s)) != kNotTaken) return rc;
+  if ((rc = wg_single(a, dtype, s)) != kNotTaken) return rc;
+  if ((rc = wg_fast(a, dtype, s, plan, planned)) != kNotTaken) return rc;
+  // ---- general kernel (this file) ----
+  const bool wide = it.Wo >= 24;
   // bf16, 25 taps: 25 x (64 x 64) partial sums do not fit 8 waves' registers -> 32 output channels per workgroup
   if (dtype == SDHIP_BF16) return maxt == 9 ? launch_tile<bf16_t, 9, 64>(a, wide, s) : launch_tile<bf16_t, 25, 32>(a, wide, s);
   return maxt == 9 ? launch_tile<float, 9, 32>(a, wide, s) : launch_tile<float, 25, 32>(a, wide, s);
@@ -525,28 +551,24 @@ static int wgrad_one(const void* x, const void* dy, float* dw_packed, float* dbi
 // halves of the same pixels — x + 32 elements, the same pixel stride — whose gradients are the column halves [0,32) / [32,64)
 // of the same packed rows [kd][1][9][Mpad][64]: both halves run on the 64-byte-row kernel (conv_wgrad_half.h) instead of the
 // 128-byte-row one (2.04 -> 2 x 0.3 ms at 4 x 48 x 128 x 240).  plans == nullptr: launch now; otherwise fast-path layers are planned.
-static int wgrad_layer(const void* x, const void* dy, float* dw_packed, float* dbias,
-                       const float* in_scale, const float* in_shift,
-                       int B, int H, int W, int Cin, int ldx,
-                       int Ho, int Wo, int Cout, int lddy,
-                       int kh, int kw, int stride, int dil, int pad_t, int pad_l,
-                       int D, int Do, int kd, int sd, int pad_d,
-                       int in_relu, int groups, int prezeroed, int dtype, void* stream, std::vector<WgfPlan>* plans) {
-  auto one = [&](const void* xx, float* dw, int cin, int prez) {
+static int wgrad_layer(const SdhipWgradItem& it, int prezeroed, int dtype, void* stream, std::vector<WgfPlan>* plans) {
+  auto one = [&](const SdhipWgradItem& item, int prez) {
     WgfPlan pl;
     bool planned = false;
-    const int rc = wgrad_one(xx, dy, dw, dbias, in_scale, in_shift, B, H, W, cin, ldx, Ho, Wo, Cout, lddy, kh, kw, stride, dil, pad_t, pad_l,
-                             D, Do, kd, sd, pad_d, in_relu, groups, prez, dtype, stream, plans ? &pl : nullptr, plans ? &planned : nullptr);
+    const int rc = wgrad_one(item, prez, dtype, stream, plans ? &pl : nullptr, plans ? &planned : nullptr);
     if (rc == SDHIP_OK && planned) plans->push_back(pl);
     return rc;
   };
-  const bool halves = dtype == SDHIP_BF16 && x && dw_packed && Cin == 64 && Cout <= 32 && kh == 3 && kw == 3 && stride == 1 && dil == 1 && sd == 1 &&
-                      (kd == 3 || (kd == 1 && sdhip_diag().wgrad_split2d)) && !in_scale && !dbias && Wo >= 24 && ldx % 8 == 0 && ((uintptr_t)x & 15) == 0 &&
-                      !sdhip_diag().wgrad_no_half32;
-  if (!halves) return one(x, dw_packed, Cin, prezeroed);
-  const int rc = one(x, dw_packed, 32, prezeroed);           // (clears all 64 columns when asked to: one 64-channel chunk either way)
+  const bool halves = dtype == SDHIP_BF16 && it.x && it.dw_packed && it.Cin == 64 && it.Cout <= 32 && it.kh == 3 && it.kw == 3 && it.stride == 1 &&
+                      it.dil == 1 && it.sd == 1 && (it.kd == 3 || (it.kd == 1 && sdhip_diag().wgrad_split2d)) && !it.in_scale && !it.dbias &&
+                      it.Wo >= 24 && it.ldx % 8 == 0 && ((uintptr_t)it.x & 15) == 0 && !sdhip_diag().wgrad_no_half32;
+  if (!halves) return one(it, prezeroed);
+  SdhipWgradItem half = it;
+  half.Cin = 32;
+  const int rc = one(half, prezeroed);           // (clears all 64 columns when asked to: one 64-channel chunk either way)
   if (rc != SDHIP_OK) return rc;
-  return one((const bf16_t*)x + 32, dw_packed + 32, 32, 1);
+  half.x = (const bf16_t*)it.x + 32; half.dw_packed = it.dw_packed + 32;
+  return one(half, 1);
 }
 
 extern "C" int sdhip_conv2d_wgrad(const void* x, const void* dy, float* dw_packed, float* dbias,
@@ -556,9 +578,11 @@ extern "C" int sdhip_conv2d_wgrad(const void* x, const void* dy, float* dw_packe
                                   int kh, int kw, int stride, int dil, int pad_t, int pad_l,
                                   int D, int Do, int kd, int sd, int pad_d,
                                   int in_relu, int groups, int prezeroed, int dtype, void* stream) {
-  return wgrad_layer(x, dy, dw_packed, dbias, in_scale, in_shift, B, H, W, Cin, ldx, Ho, Wo, Cout, lddy, kh, kw, stride, dil, pad_t, pad_l,
-                     D, Do, kd, sd, pad_d, in_relu, groups, prezeroed, dtype, stream, nullptr);
+  const SdhipWgradItem it{x, dy, dw_packed, dbias, in_scale, in_shift, B, H, W, Cin, ldx, Ho, Wo, Cout, lddy,
+                          kh, kw, stride, dil, pad_t, pad_l, D, Do, kd, sd, pad_d, in_relu, groups};   // field order = argument order
+  return wgrad_layer(it, prezeroed, dtype, stream, nullptr);
 }
+
 
 namespace {
 
@@ -647,10 +671,7 @@ extern "C" int sdhip_conv2d_wgrad_group(const SdhipWgradItem* items, int n, int 
   std::vector<WgfPlan> plans;
   plans.reserve(n);
   for (int i = 0; i < n; ++i) {
-    const SdhipWgradItem& it = items[i];
-    const int rc = wgrad_layer(it.x, it.dy, it.dw_packed, it.dbias, it.in_scale, it.in_shift, it.B, it.H, it.W, it.Cin, it.ldx, it.Ho, it.Wo,
-                               it.Cout, it.lddy, it.kh, it.kw, it.stride, it.dil, it.pad_t, it.pad_l, it.D, it.Do, it.kd, it.sd, it.pad_d,
-                               it.in_relu, it.groups, 1, dtype, stream, &plans);
+    const int rc = wgrad_layer(items[i], 1, dtype, stream, &plans);   // the group's buffers arrive zeroed
     if (rc != SDHIP_OK) return rc;
   }
   // buckets = instantiations, in order of first appearance; <= kWgfGroupMax layers per grid

@@ -480,7 +480,7 @@ struct WgfPlan {
   WgfArgs a;
 };
 
-// Returns 0 and fills `pl` (gx = the stand-alone grid), 1 when the tile does not fit (caller tries a smaller one).
+// Returns 0 and fills `pl` (gx = the stand-alone grid), kNotTaken when the tile does not fit (caller tries a smaller one).
 template <int TH, int TW, int MAXT, int MB, bool DMAX, int CIT = 4>
 int plan_wgf(const WgfArgs& a, WgfPlan& pl) {
   auto kern = wgrad_fast_kernel<TH, TW, MAXT, MB, DMAX, CIT>;
@@ -489,9 +489,9 @@ int plan_wgf(const WgfArgs& a, WgfPlan& pl) {
   const int IWp = (IW + 15) & ~15;
   const int hrounds = (IH * IWp + 63) / 64;
   const size_t lds = 2 * ((size_t)hrounds * 8192 + (size_t)TH * TW * 128);
-  if (lds > 160 * 1024) return 1;                 // caller tries a smaller tile
-  if (!DMAX && hrounds > (MAXT == 1 ? (TH * TW) / 64 : 5)) return 1;             // register-path prefetch plan (XPF in the kernel)
-  if (a.qb && (IWp % 64) && (64 % IWp)) return 1;   // packed rows: a lane must meet the same chunk in every load round
+  if (lds > 160 * 1024) return kNotTaken;                 // caller tries a smaller tile
+  if (!DMAX && hrounds > (MAXT == 1 ? (TH * TW) / 64 : 5)) return kNotTaken;             // register-path prefetch plan (XPF in the kernel)
+  if (a.qb && (IWp % 64) && (64 % IWp)) return kNotTaken;   // packed rows: a lane must meet the same chunk in every load round
   static bool attr_set = false;
   if (lds > 64 * 1024 && !attr_set) {
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
@@ -547,12 +547,12 @@ int launch_wgf(const WgfArgs& a, hipStream_t s, WgfPlan* out) {
   return launch_wgf_plan(pl, s);
 }
 
-// tile choice: wide maps 4x32, else 4x16; 1 = nothing fits (caller falls back to the general kernel)
+// tile choice: wide maps 4x32, else 4x16; kNotTaken = nothing fits (caller falls back to the general kernel)
 template <int MAXT, int MB, bool DMAX, int CIT = 4>
 int launch_wgf_tile(const WgfArgs& a, hipStream_t s, WgfPlan* out) {
   if (a.Wo >= 24) {
     const int rc = launch_wgf<4, 32, MAXT, MB, DMAX, CIT>(a, s, out);
-    if (rc != 1) return rc;
+    if (rc != kNotTaken) return rc;
   }
   return launch_wgf<4, 16, MAXT, MB, DMAX, CIT>(a, s, out);
 }

@@ -150,9 +150,9 @@ inline int launch_single_wgrad(SingleWgArgs a, hipStream_t s) {
   if (dpw > a.D) dpw = a.D;
   const long tiles = (long)sdhip_cdiv(a.H, 8) * sdhip_cdiv(a.W, 32) * a.B;
   while (dpw > 1 && tiles * sdhip_cdiv(a.D, dpw) < 1024) --dpw;
-  if (dpw < 1) return 1;                        // halo does not fit: the caller takes another kernel
+  if (dpw < 1) return kNotTaken;                        // halo does not fit: the caller takes another kernel
   a.dpw = dpw; a.zsegs = sdhip_cdiv(a.D, dpw);
-  if ((long)a.B * a.zsegs > 65535) return 1;
+  if ((long)a.B * a.zsegs > 65535) return kNotTaken;
   dim3 grid(sdhip_cdiv(a.H, 8) * sdhip_cdiv(a.W, 32), a.B * a.zsegs);
   hipLaunchKernelGGL(conv_single_wgrad_kernel, grid, dim3(256), 0, s, a);
   SDHIP_LAUNCH_CHECK();

@@ -26,8 +26,10 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 void sdhip_set_error(const char* fmt, ...);
 #define SDHIP_FAIL(code, ...) do { sdhip_set_error(__VA_ARGS__); return (code); } while (0)
 #define SDHIP_CHECK_ARG(cond, ...) do { if (!(cond)) SDHIP_FAIL(SDHIP_ERR_ARG, __VA_ARGS__); } while (0)
-#define SDHIP_LAUNCH_CHECK() do { hipError_t e__ = hipGetLastError(); \
-    if (e__ != hipSuccess) SDHIP_FAIL(SDHIP_ERR_LAUNCH, "%s: launch failed: %s", __func__, hipGetErrorString(e__)); } while (0)
+// `who` names the launch in the message: a dispatch split into per-path functions keeps reporting under one name
+#define SDHIP_LAUNCH_CHECK_AS(who) do { hipError_t e__ = hipGetLastError(); \
+    if (e__ != hipSuccess) SDHIP_FAIL(SDHIP_ERR_LAUNCH, "%s: launch failed: %s", (who), hipGetErrorString(e__)); } while (0)
+#define SDHIP_LAUNCH_CHECK() SDHIP_LAUNCH_CHECK_AS(__func__)
 
 // ---- diagnostic / tuning switches (runtime.hip): environment read once at library load ----
 struct SdhipDiag {

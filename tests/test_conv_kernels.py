@@ -211,7 +211,7 @@ def _addr_ok(lay, dtype, align):
 
 
 def fwd_path(c, dtype, env=None):
-    """Mirror of conv2d_fwd_impl (csrc/conv_fwd.hip, from `const int V = ...` to the final SDHIP_FAIL: the block-width choice,
+    """Mirror of conv2d_fwd_impl (csrc/conv_fwd.hip, conv_plan and the chain of path_* functions: the block-width choice,
     `big`, the thin / fan-in / fan-out / GEMM / band conditions, the fast path's tile loop and the generic kernel's) with
     the default tuning values of csrc/runtime.hip (tune_big 512, tune_split 1024, tune_s2_small 1) and fanin_ok / fanout_ok
     (csrc/conv_thin.h), gemm1x1_ok (csrc/conv_gemm.h), band_ok (csrc/conv_band.h).  Returns (name, tile (th, tw))."""
