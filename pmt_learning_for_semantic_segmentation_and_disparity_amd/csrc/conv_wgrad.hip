@@ -17,6 +17,7 @@
 // into the packed f32 gradient buffer.
 #include "conv_common.h"
 #include "conv_wgrad_fast.h"
+#include "conv_wgrad_gemm1x1.h"
 #include "conv_wgrad_half.h"
 #include "conv_wgrad_single.h"
 #include "conv_thin.h"
@@ -484,8 +485,18 @@ int wg_fast(const WgArgs& a, int dtype, hipStream_t s, WgfPlan* plan, bool* plan
     if (plan) { *plan = pl; *planned = true; return SDHIP_OK; }
     return launch_wgf_plan(pl, s);
   }
-  // 1x1 with many input channels (DenseNet bottlenecks / transitions): pack 2 or 4 channel chunks per workgroup
   const bool no_pack = sdhip_diag().wgrad_no_pack;   // diagnostics: A/B against the unpacked kernel
+  // 1x1 with a BatchNorm prologue, >= 96 input channels into a multiple of 128 outputs (DenseNet bottlenecks / transitions):
+  // the pixel-contraction GEMM of conv_wgrad_gemm1x1.h, a [128 x 256] output tile per workgroup.  It stands aside for the
+  // switches that name one of the kernels below (and for its own, SDHIP_WGRAD_NO_GEMM: A/B runs).
+  if (wgrad_gemm1x1_ok(f, T) && !no_pack && !sdhip_diag().wgrad_force_pack && !sdhip_diag().wgrad_no_gemm) {
+    WgfPlan pl;
+    const int rc = plan_wg1(f, pl);
+    if (rc != SDHIP_OK) return rc;
+    if (plan) { *plan = pl; *planned = true; return SDHIP_OK; }
+    return launch_wgf_plan(pl, s);
+  }
+  // 1x1 with many input channels (the same layers without a prologue, or under the switches): pack 2 or 4 channel chunks per workgroup
   // Measured (tools/gpu_wgrad1x1_ab.sh): it pays on large maps and wide outputs (192->128 at 16x64x128: 88 -> 52 us,
   // 1024->512 at 16x16x32: 62 -> 54 us); on the small maps of the deep DenseNet blocks the sweep is bound by the
   // per-tile DMA latency either way and the unpacked kernel's smaller tiles win (1024->128 at 16x16x32: 21 vs 31 us).

@@ -40,6 +40,7 @@ static void diag_fill() {
   g_diag.wgrad_generic = env_set("SDHIP_WGRAD_GENERIC");
   g_diag.wgrad_no_pack = env_set("SDHIP_WGRAD_NO_PACK");
   g_diag.wgrad_force_pack = env_set("SDHIP_WGRAD_FORCE_PACK");
+  g_diag.wgrad_no_gemm = env_set("SDHIP_WGRAD_NO_GEMM");
   g_diag.wgrad_no_half = env_set("SDHIP_WGRAD_NO_HALF");
   g_diag.thin_wgrad_reg = env_set("SDHIP_THIN_WGRAD_REG");
   g_diag.corr_no_tiled = env_set("SDHIP_CORR_NO_TILED");
@@ -53,6 +54,7 @@ static void diag_fill() {
   g_diag.tune_gemm_dbg = env_int("SDHIP_TUNE_GEMM_DBG", 0);
   g_diag.tune_band_dbg = env_int("SDHIP_TUNE_BAND_DBG", 0);
   g_diag.tune_atomic_tbs = getenv("SDHIP_TUNE_ATOMIC_TBS") ? atof(getenv("SDHIP_TUNE_ATOMIC_TBS")) : 1.3;
+  g_diag.tune_wg1_tile = getenv("SDHIP_TUNE_WG1_TILE") ? atof(getenv("SDHIP_TUNE_WG1_TILE")) : 1.0;
   g_diag_init = true;
 }
 const SdhipDiag& sdhip_diag() {
