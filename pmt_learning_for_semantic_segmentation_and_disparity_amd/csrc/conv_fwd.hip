@@ -16,6 +16,7 @@
 // sum / sum-of-squares for the BatchNorm that follows).
 #include "conv_common.h"
 #include "conv_fast.h"
+#include "conv_point.h"
 #include "conv_band.h"
 #include "conv_gemm.h"
 #include "conv_thin.h"
@@ -629,8 +630,41 @@ int path_band3d(const ConvCall& c, const ConvPlan& d) {
   return launch_band<3, 3>(f, c.stream);
 }
 
-// ---- fast path (conv_fast.h): 16-byte-aligned pixels on both sides, halo-tile mode.  The only path that takes the
-//      variants (phase output, BatchNorm-backward epilogue, consumer-side BatchNorm finalize) ----
+// ---- pointwise split-K kernel (conv_point.h): bf16 1x1 with an input prologue (given, or the consumer-side BatchNorm
+//      finalize) over >= 128 channels on the small maps where the tower is a latency chain (<= 32768 pixels, the
+//      TUNE_PRO_MAX_PIX range of densenet.py).  The rest of the predicate is what was measured (tools/gpu_conv1x1_small.py,
+//      16 images): dense blocks 3 and 4 (16x32 and 8x16 maps, 512 and 128 workgroups) are faster on it; block 2 and
+//      transition 2 (32x64 maps, 2048 and 4096 workgroups) and transition 3 (512 output channels: the pixel tile is re-read
+//      once per 32 of them) are bound by load throughput, not latency, and faster on the halo-tile kernel.  So: maps of at
+//      most kPointMaxMap pixels, a grid that is resident at once (<= 2 workgroups on each of 256 CUs), <= 256 outputs.
+//      A given prologue WITHOUT a statistics epilogue is an inference call: it keeps the halo-tile kernel, whose summation
+//      order the eval-mode goldens were checked against (two of their caps sit within one change of f32 summation order) ----
+int path_point(const ConvCall& c, const ConvPlan& d) {
+  const ConvGeom& g = c.g;
+  const SdhipDiag& dg = sdhip_diag();
+  if (!(c.dtype == SDHIP_BF16 && !c.bx && !c.addend && c.omul == 1 && (c.ps || (c.in_scale && c.stats)) && !c.bias && c.act == 0 && !c.accumulate &&
+        g.kh == 1 && g.kw == 1 && c.flat() && g.stride == 1 && g.pad_t == 0 && g.pad_l == 0 && g.Ho == g.H && g.Wo == g.W &&
+        c.Cin >= 128 && c.Cin <= kPinMaxC && c.Cin % 8 == 0 && c.Cout % kPointBN == 0 && c.Cout <= 256 && (long)g.B * g.H * g.W <= 32768 && (long)g.H * g.W <= kPointMaxMap &&
+        (long)g.B * sdhip_cdiv((long)g.H * g.W, kPointPix) * (c.Cout / kPointBN) <= kPointMaxWG &&
+        d.vec_in && d.vec_out && (long)g.H * g.W * c.ldx < (1L << 31) && !dg.conv_generic && !dg.conv_no_point))
+    return kNotTaken;
+  const ProStats* ps = c.ps;
+  PointArgs f{};
+  f.x = c.x; f.wp = c.wp; f.y = c.y; f.in_scale = c.in_scale; f.in_shift = c.in_shift; f.stats = c.stats;
+  f.HW = g.H * g.W; f.Cin = c.Cin; f.ldx = c.ldx; f.Cout = c.Cout; f.Mpad = d.Mpad; f.ldy = c.ldy;
+  f.in_relu = c.in_relu; f.bpg = g.B / c.groups;
+  f.stats_ld = d.stats_ld; f.nrep = d.nrep; f.rep_stride = d.rep_stride;
+  if (ps) {
+    f.pin_stats = ps->stats; f.pin_ld = ps->ld; f.pin_nrep = ps->nrep; f.pin_groups = c.groups; f.pin_gamma = ps->gamma; f.pin_beta = ps->beta;
+    f.pin_scale = ps->scale; f.pin_shift = ps->shift; f.pin_mean = ps->mean; f.pin_invstd = ps->invstd; f.pin_rmean = ps->rmean; f.pin_rvar = ps->rvar;
+    f.pin_eps = ps->eps; f.pin_momentum = ps->momentum; f.pin_count = ps->count;
+    f.pend_stats = ps->pend; f.pin_fold = ps->fold; f.pend_ld = ps->pend_ld; f.pend_nrep = ps->pend_nrep; f.pend_c0 = ps->pend_c0; f.pend_n = ps->pend ? ps->pend_n : 0;
+  }
+  return launch_point(f, g.B, c.stream);
+}
+
+// ---- fast path (conv_fast.h): 16-byte-aligned pixels on both sides, halo-tile mode.  It takes every variant (phase
+//      output, BatchNorm-backward epilogue, consumer-side BatchNorm finalize) ----
 int path_fast(const ConvCall& c, const ConvPlan& d) {
   const ConvGeom& g = c.g;
   if (!(!d.per_tap_any && d.vec_in && d.vec_out && (long)g.H * g.W * c.ldx < (1L << 31) && !sdhip_diag().conv_generic)) return kNotTaken;
@@ -746,6 +780,7 @@ int conv2d_fwd_impl(const ConvCall& c) {
   for (auto path : {path_thin, path_fanin, path_fanout, path_gemm, path_band2d, path_band3d})
     if ((rc = path(c, d)) != kNotTaken) return rc;
   if (c.addend && !c.bx) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_add: only the persistent 5x5 kernel adds a second tensor in its epilogue (bf16, <= 64 channels, >= 192 tiles of 16x32)");
+  if ((rc = path_point(c, d)) != kNotTaken) return rc;
   if ((rc = path_fast(c, d)) != kNotTaken) return rc;
   if (c.omul != 1) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_phase: interleaved output needs the aligned fast path (ldx %% 8, ldy %% 4)");
   if (c.ps) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_bnpro: needs the aligned fast path (ldx %% 8, ldy %% 4, halo tile within LDS)");
