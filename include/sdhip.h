@@ -458,6 +458,24 @@ int sdhip_seg_finish(void* workspace, long workspace_bytes, const float* class_w
                      float ce_weight, int terms, void* stream);
 int sdhip_seg_terms_bwd(const void* logits, int ldy, const float* target, int ldt, void* grad, int ldg, const void* workspace,
                         long workspace_bytes, int B, long hw, int C, int dtype, void* stream);
+/* smoothing_gradients (util/utilTorchLoss.py:41-101), the `smooth_grad` term of lossDisp_fn (losses/multiLosses.py:143-146):
+ * an edge-aware smoothness penalty on the predicted disparity d, gated by the one-hot target (values 0 or 1, at most one 1
+ * per pixel; an all-zero row has no label).  With Y = 0.2126 R + 0.7152 G + 0.0722 B of the left image, Ys = Y filtered by
+ * the 7x7, sigma 2 Gaussian (zero padding 3), M(p) = 1 iff p has a label and its eight neighbours lie inside the image and
+ * carry the same label, w_v(p) = M(p) exp(1 - |Ys(y,x) - Ys(y+1,x)|), w_h(p) = M(p) exp(1 - |Ys(y,x) - Ys(y,x+1)|):
+ *   loss += s * sum_p [ w_v(p) |d(y,x) - d(y+1,x)| + w_h(p) |d(y,x) - d(y,x+1)| ],   s = weight * 0.7 / (128 B H W)
+ *   grad  = d(that)/d d, WRITTEN (not accumulated), with sgn(0) = 0; the image and the target get no gradient.
+ * left: f32 ONLY (the image a step is fed, before any cast), channel c of pixel (y, x) of image b at
+ *       left[b*left_bs + c*left_cs + (y*W + x)*left_ps]; channels 0..2 are read, later ones ignored.
+ * target: f32, pixel stride ldt >= C (may be a channel slice of a wider slab), 1 <= C <= 32.
+ * disp, grad: dense (B,1,H,W) of `dtype`.  H < 3 or W < 3: value 0, gradient 0.
+ * One stencil launch that stores a f64 partial per workgroup into the workspace (sdhip_disp_smooth_workspace_bytes(B, H, W)
+ * bytes, 8-byte aligned, no initialisation needed; < 0 for an unsupported shape) and a one-workgroup launch that folds the
+ * partials in a fixed order: no float atomics, value and gradient are bitwise reproducible. */
+long sdhip_disp_smooth_workspace_bytes(int B, int H, int W);
+int sdhip_disp_smooth(const float* left, long left_bs, long left_cs, int left_ps, const float* target, int ldt,
+                      const void* disp, int dtype, void* grad, double* loss, int B, int H, int W, int C, float weight,
+                      void* workspace, long workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Uncertainty-weighted multitask loss (`-multaskloss 1|2`: multiTask_loss, util/utilTorchLoss.py:521-540, called at

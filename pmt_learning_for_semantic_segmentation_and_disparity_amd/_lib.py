@@ -97,6 +97,14 @@ def seg_terms_workspace_bytes(B, hw, C):
     return n
 
 
+def disp_smooth_workspace_bytes(B, H, W):
+    """Workspace of sdhip_disp_smooth for this shape (include/sdhip.h)."""
+    n = _lib.sdhip_disp_smooth_workspace_bytes(B, H, W)
+    if n <= 0:
+        raise SdhipError("sdhip_disp_smooth_workspace_bytes: unsupported shape (B %d, H %d, W %d)" % (B, H, W))
+    return n
+
+
 def dw_pool_parts(H, W, C, k, stride, dt):
     """Pool slots of sdhip_dw_conv_fwd for this input (include/sdhip.h)."""
     n = _lib.sdhip_dw_pool_parts(H, W, C, k, stride, dt)

@@ -2017,6 +2017,88 @@ def train_loss(seg1, disp, seg2, seg_target, disp_target, use_lovasz=True, mask_
     return _TrainLossFn.apply(seg1, disp, seg2, seg_target, disp_target, use_lovasz, mask_invalid_disp, ignore_void, seg3, plan, cw)
 
 
+_disp_smooth_ws = {}
+
+
+def _image_strides(left):
+    """(batch, channel, pixel) strides of a (B,>=3,H,W) image whose rows follow one another pixel by pixel (NCHW, channels-last
+    or a channel slice of either), or None."""
+    B, C, H, W = left.shape
+    sb, sc, sh, sw = left.stride()
+    if W == 1:
+        sw = sh
+    if min(sb, sc, sw) < 1 or (H > 1 and sh != W * sw):
+        return None
+    return sb, sc, sw
+
+
+class _DispSmoothFn(torch.autograd.Function):
+    """smoothing_gradients (util/utilTorchLoss.py:41-101) on one disparity map: value and gradient in one stencil pass."""
+
+    @staticmethod
+    def forward(ctx, left, disp, seg_t, weight):
+        B, _, H, W = disp.shape
+        C = seg_t.shape[1]
+        strides = _image_strides(left)
+        if strides is None:
+            left = left.contiguous()
+            strides = _image_strides(left)
+        tv, ldt = nhwc_view(seg_t)
+        dv, ldd = nhwc_view(disp)
+        if ldd != 1:      # 1-channel map inside a padded pixel stride (direct conv output): densify
+            dv = disp.contiguous()
+        nbytes = _lib.disp_smooth_workspace_bytes(B, H, W)
+        key = (B, H, W, str(disp.device))
+        ws = _disp_smooth_ws.get(key)
+        if ws is None or ws.numel() * 8 < nbytes:
+            ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=disp.device)
+            _disp_smooth_ws[key] = ws
+        loss = torch.zeros(1, dtype=torch.float64, device=disp.device)
+        g = torch.empty((B, 1, H, W), dtype=dv.dtype, device=dv.device)
+        call("sdhip_disp_smooth", ptr(left), strides[0], strides[1], strides[2], ptr(tv), ldt, ptr(dv), dtype_code(dv), ptr(g),
+             ptr(loss), B, H, W, C, weight, ptr(ws), ws.numel() * 8, stream_ptr())
+        ctx.save_for_backward(g)
+        return loss.float().reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        g, = ctx.saved_tensors
+        return None, g * gout.to(g.dtype), None, None
+
+
+def disp_smooth_loss(left, disp_pred, seg_target, weight=1.0):
+    """The reference's smoothing_gradients(left, disp_pred, seg_target) (util/utilTorchLoss.py:41-101; `smooth_grad` of
+    lossDisp_fn, losses/multiLosses.py:143-146) times `weight`: an edge-aware smoothness penalty on the predicted disparity
+    that acts where a pixel's whole 3x3 neighbourhood has the pixel's own class, weighted by exp(1 - |grad of the smoothed
+    luma|) of the left image (include/sdhip.h has the closed form).  weight = 1 is the reference's value, its 0.7 inside.
+      left       — (B,>=3,H,W) f32 image (channels 0..2 are read); NCHW or channels-last, no copy is made of either
+      disp_pred  — (B,1,H,W) f32 or bf16; the only input that gets a gradient (in its dtype)
+      seg_target — one-hot f32 (B,C,H,W), C <= 32; an all-zero row has no class and gets no term.  Upstream passes the full
+                   one-hot including the void channel, so void regions smooth as a class of their own; a caller who dropped
+                   that channel gets no term there.
+    Returns an f32 scalar; value and gradient are reproducible bit for bit."""
+    if left.dim() != 4 or disp_pred.dim() != 4 or seg_target.dim() != 4:
+        raise _lib.SdhipError("disp_smooth_loss: image, disparity and target must be 4-D (B,C,H,W), got %s, %s and %s"
+                              % (tuple(left.shape), tuple(disp_pred.shape), tuple(seg_target.shape)))
+    B, C1, H, W = disp_pred.shape
+    if C1 != 1 or left.shape[1] < 3 or (left.shape[0],) + tuple(left.shape[2:]) != (B, H, W) or \
+            (seg_target.shape[0],) + tuple(seg_target.shape[2:]) != (B, H, W):
+        raise _lib.SdhipError("disp_smooth_loss: need a (B,>=3,H,W) image, a (B,1,H,W) disparity and a (B,C,H,W) target, got %s, %s "
+                              "and %s" % (tuple(left.shape), tuple(disp_pred.shape), tuple(seg_target.shape)))
+    if min(B, H, W) < 1 or not 1 <= seg_target.shape[1] <= SEG_MAX_CLASSES:
+        raise _lib.SdhipError("disp_smooth_loss: empty tensor, or a target of %d channels (1 to %d are served)"
+                              % (seg_target.shape[1], SEG_MAX_CLASSES))
+    _require_gpu(left, disp_pred, seg_target)
+    if not left.device == disp_pred.device == seg_target.device:
+        raise _lib.SdhipError("disp_smooth_loss: image, disparity and target live on different devices")
+    if left.dtype != torch.float32:
+        raise _lib.SdhipError("disp_smooth_loss: the image must be f32, the input a step is fed (got %s)" % left.dtype)
+    if seg_target.dtype != torch.float32:
+        raise _lib.SdhipError("disp_smooth_loss: the one-hot segmentation target must be f32 (got %s)" % seg_target.dtype)
+    dtype_code(disp_pred)
+    return _DispSmoothFn.apply(left, disp_pred, seg_target, float(weight))
+
+
 # ============================================================================ dropout / global average pool
 _rng = {"seed": None, "layers": 0}
 

@@ -145,12 +145,22 @@ def model_outputs(model, dtype, left, right, seg, disp, extra=()):
     return model(x, y, *extra)
 
 
-def default_loss(model, outs, seg, disp, **train_loss_kwargs):
+def default_loss(model, outs, seg, disp, *, left=None, smooth_grad=0.0, **train_loss_kwargs):
     """The loss of the reference step on the outputs of model_outputs.  Multitask: the sum of the three maps' means
-    (torch_implementation.py:173-176,285-325), from the loss kernels' own sums."""
+    (torch_implementation.py:173-176,285-325), from the loss kernels' own sums.
+    smooth_grad (non-zero): the weight of the `smooth_grad` disparity regulariser of lossDisp_fn (losses/multiLosses.py:143-146),
+    ops.disp_smooth_loss(left, outs[1], seg, smooth_grad), added to the rest; `left` is the f32 left image of the batch."""
+    if smooth_grad:
+        if getattr(model, "multiTaskLoss", 0):
+            raise _lib.SdhipError("default_loss: the multitask loss is the three maps' means; smooth_grad has no place in it")
+        if left is None:
+            raise _lib.SdhipError("default_loss: smooth_grad needs the left image (left=...)")
     if getattr(model, "multiTaskLoss", 0):
         return multitask.step_loss(outs[4], outs[5], outs[6])
     # the `ThreeOutPuts` networks (warp.minidsnetDivide*) add the cross-entropy of their third segmentation map, outs[4]
     # (torch_implementation.py:157-158,298); Lovasz stays on outs[2], which the metrics score as well
     seg3 = outs[4] if getattr(model, "three_outputs", False) else None
-    return ops.train_loss(outs[0], outs[1], outs[2], seg, disp, seg3=seg3, **train_loss_kwargs)
+    loss = ops.train_loss(outs[0], outs[1], outs[2], seg, disp, seg3=seg3, **train_loss_kwargs)
+    if smooth_grad:
+        loss = loss + ops.disp_smooth_loss(left, outs[1], seg, smooth_grad)
+    return loss

@@ -80,6 +80,29 @@ def flatten_parameters(model):
     return flat_p, flat_g
 
 
+class StepLoss:
+    """`TrainStep(model, loss_fn=StepLoss(model, smooth_grad=w, ...))`: the default loss of the step (step.default_loss) with the
+    options TrainStep.__init__ has no keyword for.  smooth_grad: the weight of the reference's `smooth_grad` disparity
+    regulariser (ops.disp_smooth_loss; 1 is the reference's value) on the disparity output, the f32 left image and the full
+    one-hot target of the batch.  use_lovasz, loss and class_weights are TrainStep's keywords of the same names: the list is
+    checked and the table uploaded here, once, so that the step captures into the hipGraph.  `wants_images` makes TrainStep
+    hand over the input images; `metrics=` is scored as with the default loss, the heads being the same."""
+    wants_images = True
+
+    def __init__(self, model, smooth_grad=1.0, use_lovasz=True, loss=None, class_weights=None):
+        if getattr(model, "multiTaskLoss", 0) and (smooth_grad or loss is not None or class_weights is not None):
+            raise _lib.SdhipError("StepLoss: the multitask modes have their own loss; smooth_grad / loss / class_weights do not apply to them")
+        self.model, self.smooth_grad, self.use_lovasz = model, float(smooth_grad), use_lovasz
+        self.seg_loss = None if loss is None else tuple([loss] if isinstance(loss, str) else loss)
+        if self.seg_loss is not None:
+            ops.seg_loss_plan(self.seg_loss)
+        self.class_weights = ops.seg_class_weights(class_weights, device=next(model.parameters()).device)
+
+    def __call__(self, outs, seg, disp, left=None, right=None):
+        return step.default_loss(self.model, outs, seg, disp, left=left, smooth_grad=self.smooth_grad, use_lovasz=self.use_lovasz,
+                                 loss=self.seg_loss, class_weights=self.class_weights)
+
+
 class TrainStep:
     def __init__(self, model, dtype=torch.bfloat16, lr=None, betas=(0.9, 0.999), eps=1e-7, use_lovasz=True,
                  use_graph=True, world_size=1, process_group=None, use_side_stream=None, loss_fn=None, metrics=None, accumulate=1,
@@ -232,14 +255,16 @@ class TrainStep:
     def _forward_backward(self, left, right, seg, disp):
         mt, three = getattr(self.model, "multiTaskLoss", 0), getattr(self.model, "three_outputs", False)
         outs = step.model_outputs(self.model, self.dtype, left, right, seg, disp)
-        if self.loss_fn is not None:
+        if self.loss_fn is not None and getattr(self.loss_fn, "wants_images", False):
+            loss = self.loss_fn(outs, seg, disp, left=left, right=right)      # StepLoss: terms that read the input images
+        elif self.loss_fn is not None:
             loss = self.loss_fn(outs, seg, disp)
         else:
             loss = step.default_loss(self.model, outs, seg, disp, use_lovasz=self.use_lovasz, loss=self.seg_loss,
                                      class_weights=self.class_weights)
         if self.grad_free is None and (mt or three or self.freeze_bn or (self.optimizer == "sgd" and self.weight_decay != 0)):
             self.grad_free = _unreached_parameters(self.model, loss)
-        if self.metrics is not None and self.loss_fn is None:
+        if self.metrics is not None and (self.loss_fn is None or isinstance(self.loss_fn, StepLoss)):    # the default heads
             self.metrics.update(outs[2].detach(), seg, outs[1].detach(), disp)
         loss.backward()
         self.ctx.join()             # weight gradients ran on the side stream
