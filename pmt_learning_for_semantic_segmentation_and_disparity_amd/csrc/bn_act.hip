@@ -44,10 +44,86 @@ inline RowGeom row_geom(int units) {
 #define ROW_TXTY(rg, tx, ty) const int ty = (rg).tx > 1 ? (int)__umulhi((unsigned)threadIdx.x, (rg).magic) : (int)threadIdx.x; \
                              const int tx = (int)threadIdx.x - ty * (rg).tx
 
+// ---- streaming bodies ----------------------------------------------------------------------------------------------
+// A thread owns the pixels first, first + stride, ... of its channel unit and visits them in ascending order, K per trip.
+// A trip ISSUES every load it needs (K pixels x every input tensor) into raw registers, and only then unpacks, computes
+// and stores: one HBM round trip per trip.  (Unit::load converts where it loads; inside `if (pix < npix_g)` each guarded
+// load then waits for its own data, and the compiler does not hoist loads over divergent branches: the 4-pixel trips
+// made seven dependent round trips.)  Full trips run in a loop without any guard; one last, ragged trip (FULL = false)
+// follows.  No branch surrounds a load there either: a pixel past the end is loaded from the trip's own first row instead
+// - inside the tensor - and its result dropped: the store is predicated, a sum keeps its old value by a select (not a
+// multiply by zero: the row that stands in may hold anything).  Rows are reached by pointer steps (the
+// uniform stride * ld), not by a 64-bit product per load: address arithmetic between the loads invites the scheduler to
+// start on the first pixel while the last loads are not yet out; issued() forbids it that outright.  The tensor pointers of
+// these kernels are not __restrict__: a load known not to alias the stores is sunk into the predicated block of its pixel,
+// behind the stores of the pixels before it - and waits there.
+template <int K, bool FULL> struct Trip {
+  bool ok[K];
+  __device__ __forceinline__ Trip(long pix0, long stride, long npix_g) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) ok[k] = FULL || pix0 + k * stride < npix_g;
+  }
+  // row k of the trip whose first row p points at; step = stride * ld elements
+  template <typename P> __device__ __forceinline__ P at(P p, int k, long step) const { return p + (ok[k] ? k * step : 0L); }
+};
+
+// every load above is issued before anything below is scheduled
+__device__ __forceinline__ void issued() { __builtin_amdgcn_sched_barrier(0); }
+
+// Pixels per trip.  The kernels that had 4 keep 4.  The others (affine_act, affine_act_bn, stats_fix, stats_fix_fin) were
+// measured with 4 on top of the issue-then-use trips and lost 2 - 12 % at every shape of the step (their grids are not
+// capped below the machine, so the workgroups already keep the memory system busy): they stay at 1, act_out_bwd at its 2.
+// A map so small that no thread has a second pixel takes the one-pixel trip in the 4-pixel kernels as well: nothing to
+// overlap, and the short body starts sooner.
+constexpr int kPixTrip = 1;
+
+// y = act(x*scale + shift) (+ res) over the thread's pixels
+template <typename T, bool VEC, bool HS, bool RES, int K = kPixTrip>
+__device__ __forceinline__ void affine_act_rows(const T* x, int ldx, T* y, int ldy,
+                                                const T* res, int ldr, const float* sc, const float* sf,
+                                                int c0, long base, long npix_g, long first, long stride, int act) {
+  using U = Unit<T, VEC>;
+  constexpr int N = U::N;
+  const long sx = stride * ldx, sy = stride * ldy, sr = stride * ldr;
+  const T* xp = x + (base + first) * ldx + c0;
+  const T* rp = RES ? res + (base + first) * ldr + c0 : nullptr;
+  T* yp = y + (base + first) * ldy + c0;
+  long pix0 = first;
+  auto trip = [&](auto full) {
+    const Trip<K, decltype(full)::value> t(pix0, stride, npix_g);
+    typename U::Raw xr[K], rr[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) xr[k] = U::raw(t.at(xp, k, sx));
+    if constexpr (RES) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) rr[k] = U::raw(t.at(rp, k, sr));
+    }
+    issued();
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float f[N], r[N];
+      U::unpack(xr[k], f);
+      if constexpr (RES) U::unpack(rr[k], r);
+#pragma unroll
+      for (int e = 0; e < N; ++e) {
+        float v = fmaf(f[e], sc[e], sf[e]);
+        if (act == 1) v = fmaxf(v, 0.f);
+        else if (act == 2) v = 1.f / (1.f + __expf(-v));
+        else if (HS && (act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID)) v = act_hs(v, act);
+        if constexpr (RES) v += r[e];
+        f[e] = v;
+      }
+      if (t.ok[k]) U::store(yp + k * sy, f);
+    }
+  };
+  for (; pix0 + (K - 1) * stride < npix_g; pix0 += K * stride, xp += K * sx, rp += RES ? K * sr : 0, yp += K * sy) trip(std::true_type{});
+  if (pix0 < npix_g) trip(std::false_type{});
+}
+
 // y = act(x*scale + shift) (+ res);  grid: (pixel slabs, unit groups, stat groups)
 template <typename T, bool VEC, bool HS = false>
-__global__ __launch_bounds__(256) void affine_act_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy,
-                                                         const T* __restrict__ res, int ldr,
+__global__ __launch_bounds__(256) void affine_act_kernel(const T* x, int ldx, T* y, int ldy,
+                                                         const T* res, int ldr,
                                                          const float* __restrict__ scale, const float* __restrict__ shift,
                                                          int C, long npix_g, int act, RowGeom rg) {
   constexpr int N = Unit<T, VEC>::N;
@@ -58,28 +134,67 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const T* __restrict__ x
   float sc[N], sf[N];
 #pragma unroll
   for (int e = 0; e < N; ++e) { sc[e] = scale ? scale[g * C + c0 + e] : 1.f; sf[e] = shift ? shift[g * C + c0 + e] : 0.f; }
-  const long base = (long)g * npix_g;
-  for (long pix = (long)blockIdx.x * rg.ty + ty; pix < npix_g; pix += (long)gridDim.x * rg.ty) {
-    float f[N], r[N];
-    Unit<T, VEC>::load(x + (base + pix) * ldx + c0, f);
-    if (res) Unit<T, VEC>::load(res + (base + pix) * ldr + c0, r);
+  const long base = (long)g * npix_g, first = (long)blockIdx.x * rg.ty + ty, stride = (long)gridDim.x * rg.ty;
+  if (res) affine_act_rows<T, VEC, HS, true>(x, ldx, y, ldy, res, ldr, sc, sf, c0, base, npix_g, first, stride, act);
+  else affine_act_rows<T, VEC, HS, false>(x, ldx, y, ldy, res, ldr, sc, sf, c0, base, npix_g, first, stride, act);
+}
+
+// the thread's pixels of affine_act_bwd.  GX 0: reductions only; 1: gx written; 2: gx += (its old value is one more input)
+template <typename T, bool VEC, bool HS, int GX>
+__device__ __forceinline__ void affine_act_bwd_rows(const T* gy, int ldg, const T* x, int ldx, T* gx, int ldgx,
+                                                    const float* sc, const float* sf, float* a1, float* a2,
+                                                    int c0, long base, long npix_g, long first, long stride, int act) {
+  using U = Unit<T, VEC>;
+  constexpr int N = U::N, K = 4;
+  const long sg = stride * ldg, sx = stride * ldx, so = stride * ldgx;
+  const T* gp = gy + (base + first) * ldg + c0;
+  const T* xp = x + (base + first) * ldx + c0;
+  T* op = GX ? gx + (base + first) * ldgx + c0 : nullptr;
+  long pix0 = first;
+  auto trip = [&](auto full) {
+    const Trip<K, decltype(full)::value> t(pix0, stride, npix_g);
+    typename U::Raw gr[K], xr[K], orw[K];
 #pragma unroll
-    for (int e = 0; e < N; ++e) {
-      float v = fmaf(f[e], sc[e], sf[e]);
-      if (act == 1) v = fmaxf(v, 0.f);
-      else if (act == 2) v = 1.f / (1.f + __expf(-v));
-      else if (HS && (act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID)) v = act_hs(v, act);
-      if (res) v += r[e];
-      f[e] = v;
+    for (int k = 0; k < K; ++k) { gr[k] = U::raw(t.at(gp, k, sg)); xr[k] = U::raw(t.at(xp, k, sx)); }
+    if constexpr (GX == 2) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) orw[k] = U::raw(t.at((const T*)op, k, so));
     }
-    Unit<T, VEC>::store(y + (base + pix) * ldy + c0, f);
-  }
+    issued();
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float gv[N], xv[N], old[N];
+      U::unpack(gr[k], gv);
+      U::unpack(xr[k], xv);
+      if constexpr (GX == 2) U::unpack(orw[k], old);
+#pragma unroll
+      for (int e = 0; e < N; ++e) {
+        const float z = fmaf(xv[e], sc[e], sf[e]);
+        float gm = gv[e];
+        if (act == 1) gm = z > 0.f ? gm : 0.f;
+        else if (act == 2) { const float sg = 1.f / (1.f + __expf(-z)); gm *= sg * (1.f - sg); }
+        else if (HS && (act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID)) gm *= act_hs_d(z, act);
+        else if (act == 4) gm *= z * (1.f - z);  // x holds the sigmoid OUTPUT
+        const float n1 = fmaf(gm, xv[e], a1[e]), n2 = a2[e] + gm;
+        a1[e] = t.ok[k] ? n1 : a1[e];
+        a2[e] = t.ok[k] ? n2 : a2[e];
+        {   // rounded on its own: gx += adds the old value to the PRODUCT, as it always did (no fused multiply-add)
+#pragma clang fp contract(off)
+          gv[e] = gm * sc[e];
+        }
+        if constexpr (GX == 2) gv[e] += old[e];
+      }
+      if constexpr (GX != 0) { if (t.ok[k]) U::store(op + k * so, gv); }
+    }
+  };
+  for (; pix0 + (K - 1) * stride < npix_g; pix0 += K * stride, gp += K * sg, xp += K * sx, op += GX ? K * so : 0) trip(std::true_type{});
+  if (pix0 < npix_g) trip(std::false_type{});
 }
 
 // gx = gy * act'(x*scale+shift) * scale;  dscale += sum gy*act'*x;  dshift += sum gy*act'
 // mode 0: both; mode 1: only the reductions (gx not written)
 template <typename T, bool VEC, bool HS = false>
-__global__ __launch_bounds__(256) void affine_act_bwd_kernel(const T* gy, int ldg, const T* __restrict__ x, int ldx,
+__global__ __launch_bounds__(256) void affine_act_bwd_kernel(const T* gy, int ldg, const T* x, int ldx,
                                                              T* gx, int ldgx,
                                                              const float* __restrict__ scale, const float* __restrict__ shift,
                                                              float* __restrict__ dscale, float* __restrict__ dshift, int nrep,
@@ -92,54 +207,22 @@ __global__ __launch_bounds__(256) void affine_act_bwd_kernel(const T* gy, int ld
   const int g = blockIdx.z, c0 = u * N;
   float sc[N], sf[N], a1[N], a2[N];
 #pragma unroll
-  for (int e = 0; e < N; ++e) {
-    sc[e] = (live && scale) ? scale[g * C + c0 + e] : 1.f;
-    sf[e] = (live && shift) ? shift[g * C + c0 + e] : 0.f;
-    a1[e] = 0.f; a2[e] = 0.f;
-  }
-  const long base = (long)g * npix_g;
+  for (int e = 0; e < N; ++e) { sc[e] = 1.f; sf[e] = 0.f; a1[e] = 0.f; a2[e] = 0.f; }
   if (live) {
-    // 4 pixels per trip, all 8 loads issued before the first use: with the grid kept small for the sake of the
-    // atomics below (see there) each thread has to keep more bytes in flight itself
-    const long stride = (long)gridDim.x * rg.ty;
-    for (long pix0 = (long)blockIdx.x * rg.ty + ty; pix0 < npix_g; pix0 += 4 * stride) {
-      float gv[4][N], xv[4][N];
+    if (scale) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const long pix = pix0 + k * stride;
-        if (pix < npix_g) {
-          Unit<T, VEC>::load(gy + (base + pix) * ldg + c0, gv[k]);
-          Unit<T, VEC>::load(x + (base + pix) * ldx + c0, xv[k]);
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const long pix = pix0 + k * stride;
-        if (pix < npix_g) {
-#pragma unroll
-          for (int e = 0; e < N; ++e) {
-            const float z = fmaf(xv[k][e], sc[e], sf[e]);
-            float gm = gv[k][e];
-            if (act == 1) gm = z > 0.f ? gm : 0.f;
-            else if (act == 2) { const float sg = 1.f / (1.f + __expf(-z)); gm *= sg * (1.f - sg); }
-            else if (HS && (act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID)) gm *= act_hs_d(z, act);
-            else if (act == 4) gm *= z * (1.f - z);  // x holds the sigmoid OUTPUT
-            a1[e] = fmaf(gm, xv[k][e], a1[e]);
-            a2[e] += gm;
-            gv[k][e] = gm * sc[e];
-          }
-          if (gx) {
-            if (accumulate) {
-              float old[N];
-              Unit<T, VEC>::load(gx + (base + pix) * ldgx + c0, old);
-#pragma unroll
-              for (int e = 0; e < N; ++e) gv[k][e] += old[e];
-            }
-            Unit<T, VEC>::store(gx + (base + pix) * ldgx + c0, gv[k]);
-          }
-        }
-      }
+      for (int e = 0; e < N; ++e) sc[e] = scale[g * C + c0 + e];
     }
+    if (shift) {
+#pragma unroll
+      for (int e = 0; e < N; ++e) sf[e] = shift[g * C + c0 + e];
+    }
+    // 4 pixels per trip, all 8 (12 when accumulating) loads issued before the first use: with the grid kept small for the
+    // sake of the atomics below (see there) each thread has to keep more bytes in flight itself
+    const long base = (long)g * npix_g, first = (long)blockIdx.x * rg.ty + ty, stride = (long)gridDim.x * rg.ty;
+    if (!gx) affine_act_bwd_rows<T, VEC, HS, 0>(gy, ldg, x, ldx, gx, ldgx, sc, sf, a1, a2, c0, base, npix_g, first, stride, act);
+    else if (!accumulate) affine_act_bwd_rows<T, VEC, HS, 1>(gy, ldg, x, ldx, gx, ldgx, sc, sf, a1, a2, c0, base, npix_g, first, stride, act);
+    else affine_act_bwd_rows<T, VEC, HS, 2>(gy, ldg, x, ldx, gx, ldgx, sc, sf, a1, a2, c0, base, npix_g, first, stride, act);
   }
   if (!dscale) return;  // uniform
   // Reduce over the ty rows of the block in LDS, then ONE atomic wave-instruction per sum with consecutive lanes on
@@ -162,13 +245,14 @@ __global__ __launch_bounds__(256) void affine_act_bwd_kernel(const T* gy, int ld
 
 // graw = gy * act'(y) * scale with the derivative taken from the activation's OUTPUT y (frozen BatchNorm folded into the
 // weight pack: the raw convolution output is never stored).  A pure stream of 2 reads and 1 write per element: 16 bytes per
-// lane in the vector form, 2 pixels per trip with both pairs of loads issued before the first use, ~20 VGPRs - the block
-// count, not the registers, bounds the bytes in flight.  grid: (pixel slabs, unit groups, scale groups)
+// lane in the vector form, all loads of a trip issued before the first use - the block count, not the registers, bounds the
+// bytes in flight.  grid: (pixel slabs, unit groups, scale groups)
 template <typename T, bool VEC>
-__global__ __launch_bounds__(256) void act_out_bwd_kernel(const T* __restrict__ gy, int ldg, const T* __restrict__ y, int ldy,
-                                                          T* __restrict__ graw, int ldgr, const float* __restrict__ scale,
+__global__ __launch_bounds__(256) void act_out_bwd_kernel(const T* gy, int ldg, const T* y, int ldy,
+                                                          T* graw, int ldgr, const float* __restrict__ scale,
                                                           int C, long npix_g, int act, RowGeom rg) {
-  constexpr int N = Unit<T, VEC>::N;
+  using U = Unit<T, VEC>;
+  constexpr int N = U::N, K = 2;
   ROW_TXTY(rg, tx, ty);
   const int u = blockIdx.y * rg.tx + tx;
   if (ty >= rg.ty || u >= rg.units) return;
@@ -176,38 +260,73 @@ __global__ __launch_bounds__(256) void act_out_bwd_kernel(const T* __restrict__ 
   float sc[N];
 #pragma unroll
   for (int e = 0; e < N; ++e) sc[e] = scale[g * C + c0 + e];
-  const long base = (long)g * npix_g;
+  const long base = (long)g * npix_g, first = (long)blockIdx.x * rg.ty + ty;
   const long stride = (long)gridDim.x * rg.ty;
-  for (long pix0 = (long)blockIdx.x * rg.ty + ty; pix0 < npix_g; pix0 += 2 * stride) {
-    float gv[2][N], yv[2][N];
+  const long sg = stride * ldg, sy = stride * ldy, so = stride * ldgr;
+  const T* gp = gy + (base + first) * ldg + c0;
+  const T* yp = y + (base + first) * ldy + c0;
+  T* op = graw + (base + first) * ldgr + c0;
+  long pix0 = first;
+  auto trip = [&](auto full) {
+    const Trip<K, decltype(full)::value> t(pix0, stride, npix_g);
+    typename U::Raw gr[K], yr[K];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const long pix = pix0 + k * stride;
-      if (pix < npix_g) {
-        Unit<T, VEC>::load(gy + (base + pix) * ldg + c0, gv[k]);
-        Unit<T, VEC>::load(y + (base + pix) * ldy + c0, yv[k]);
+    for (int k = 0; k < K; ++k) { gr[k] = U::raw(t.at(gp, k, sg)); yr[k] = U::raw(t.at(yp, k, sy)); }
+    issued();
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float gv[N], yv[N];
+      U::unpack(gr[k], gv);
+      U::unpack(yr[k], yv);
+#pragma unroll
+      for (int e = 0; e < N; ++e) {
+        float gm = gv[e];
+        if (act == 1) gm = yv[e] > 0.f ? gm : 0.f;          // -0.0 > 0 is false: an exact +0
+        else if (act == 2) gm *= fmaf(-yv[e], yv[e], yv[e]);   // y (1 - y), rounded once
+        gv[e] = gm * sc[e];
       }
+      if (t.ok[k]) U::store(op + k * so, gv);
     }
+  };
+  for (; pix0 + (K - 1) * stride < npix_g; pix0 += K * stride, gp += K * sg, yp += K * sy, op += K * so) trip(std::true_type{});
+  if (pix0 < npix_g) trip(std::false_type{});
+}
+
+// g_out = g_in + a + x * b2 over the thread's pixels (g_out may be g_in)
+template <typename T, bool VEC, int K = kPixTrip>
+__device__ __forceinline__ void stats_fix_rows(const T* gin, int ldgi, const T* x, int ldx, T* gout, int ldgo,
+                                               const float* a, const float* b2, int c0, long base, long npix_g, long first,
+                                               long stride) {
+  using U = Unit<T, VEC>;
+  constexpr int N = U::N;
+  const long sg = stride * ldgi, sx = stride * ldx, so = stride * ldgo;
+  const T* gp = gin + (base + first) * ldgi + c0;
+  const T* xp = x + (base + first) * ldx + c0;
+  T* op = gout + (base + first) * ldgo + c0;
+  long pix0 = first;
+  auto trip = [&](auto full) {
+    const Trip<K, decltype(full)::value> t(pix0, stride, npix_g);
+    typename U::Raw gr[K], xr[K];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const long pix = pix0 + k * stride;
-      if (pix < npix_g) {
+    for (int k = 0; k < K; ++k) { gr[k] = U::raw(t.at(gp, k, sg)); xr[k] = U::raw(t.at(xp, k, sx)); }
+    issued();
 #pragma unroll
-        for (int e = 0; e < N; ++e) {
-          float gm = gv[k][e];
-          if (act == 1) gm = yv[k][e] > 0.f ? gm : 0.f;          // -0.0 > 0 is false: an exact +0
-          else if (act == 2) gm *= fmaf(-yv[k][e], yv[k][e], yv[k][e]);   // y (1 - y), rounded once
-          gv[k][e] = gm * sc[e];
-        }
-        Unit<T, VEC>::store(graw + (base + pix) * ldgr + c0, gv[k]);
-      }
+    for (int k = 0; k < K; ++k) {
+      float gv[N], xv[N];
+      U::unpack(gr[k], gv);
+      U::unpack(xr[k], xv);
+#pragma unroll
+      for (int e = 0; e < N; ++e) gv[e] = gv[e] + fmaf(xv[e], b2[e], a[e]);
+      if (t.ok[k]) U::store(op + k * so, gv);
     }
-  }
+  };
+  for (; pix0 + (K - 1) * stride < npix_g; pix0 += K * stride, gp += K * sg, xp += K * sx, op += K * so) trip(std::true_type{});
+  if (pix0 < npix_g) trip(std::false_type{});
 }
 
 // g_out = g_in + dS1 + 2 * x * dS2   (dS is [G][2][C], f64 like the statistics it is the gradient of)
 template <typename T, bool VEC>
-__global__ __launch_bounds__(256) void stats_fix_kernel(const T* gin, int ldgi, const T* __restrict__ x, int ldx,
+__global__ __launch_bounds__(256) void stats_fix_kernel(const T* gin, int ldgi, const T* x, int ldx,
                                                         T* gout, int ldgo, const double* __restrict__ dS, int ldc,
                                                         int C, long npix_g, RowGeom rg) {
   constexpr int N = Unit<T, VEC>::N;
@@ -218,23 +337,56 @@ __global__ __launch_bounds__(256) void stats_fix_kernel(const T* gin, int ldgi, 
   float a[N], b2[N];
 #pragma unroll
   for (int e = 0; e < N; ++e) { a[e] = (float)dS[((long)g * 2 + 0) * ldc + c0 + e]; b2[e] = (float)(2.0 * dS[((long)g * 2 + 1) * ldc + c0 + e]); }
-  const long base = (long)g * npix_g;
-  for (long pix = (long)blockIdx.x * rg.ty + ty; pix < npix_g; pix += (long)gridDim.x * rg.ty) {
-    float gv[N], xv[N];
-    Unit<T, VEC>::load(gin + (base + pix) * ldgi + c0, gv);
-    Unit<T, VEC>::load(x + (base + pix) * ldx + c0, xv);
+  stats_fix_rows<T, VEC>(gin, ldgi, x, ldx, gout, ldgo, a, b2, c0, (long)g * npix_g, npix_g, (long)blockIdx.x * rg.ty + ty,
+                         (long)gridDim.x * rg.ty);
+}
+
+// gx = rnd(gy * act'(x*scale+shift) * scale) + a + x * b2 over the thread's pixels, 4 per trip (gx may be gy)
+template <typename T, bool VEC, bool HS, int K>
+__device__ __forceinline__ void bn_bwd_rows(const T* gy, int ldg, const T* x, int ldx, T* gx, int ldgx,
+                                            const float* sc, const float* sf, const float* a, const float* b2,
+                                            int c0, long base, long npix_g, long first, long stride, int act) {
+  using U = Unit<T, VEC>;
+  constexpr int N = U::N;
+  const long sg = stride * ldg, sx = stride * ldx, so = stride * ldgx;
+  const T* gp = gy + (base + first) * ldg + c0;
+  const T* xp = x + (base + first) * ldx + c0;
+  T* op = gx + (base + first) * ldgx + c0;
+  long pix0 = first;
+  auto trip = [&](auto full) {
+    const Trip<K, decltype(full)::value> t(pix0, stride, npix_g);
+    typename U::Raw gr[K], xr[K];
 #pragma unroll
-    for (int e = 0; e < N; ++e) gv[e] = gv[e] + fmaf(xv[e], b2[e], a[e]);
-    Unit<T, VEC>::store(gout + (base + pix) * ldgo + c0, gv);
-  }
+    for (int k = 0; k < K; ++k) { gr[k] = U::raw(t.at(gp, k, sg)); xr[k] = U::raw(t.at(xp, k, sx)); }
+    issued();
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float gv[N], xv[N];
+      U::unpack(gr[k], gv);
+      U::unpack(xr[k], xv);
+#pragma unroll
+      for (int e = 0; e < N; ++e) {
+        const float z = fmaf(xv[e], sc[e], sf[e]);
+        float gm = gv[e];
+        if (act == 1) gm = z > 0.f ? gm : 0.f;
+        else if (act == 2) { const float sg = 1.f / (1.f + __expf(-z)); gm *= sg * (1.f - sg); }
+        else if (HS && (act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID)) gm *= act_hs_d(z, act);
+        // the first-phase result the one-pass form would have stored is rounded to T before the statistics path is added
+        gv[e] = Elem<T>::rnd(gm * sc[e]) + fmaf(xv[e], b2[e], a[e]);
+      }
+      if (t.ok[k]) U::store(op + k * so, gv);
+    }
+  };
+  for (; pix0 + (K - 1) * stride < npix_g; pix0 += K * stride, gp += K * sg, xp += K * sx, op += K * so) trip(std::true_type{});
+  if (pix0 < npix_g) trip(std::false_type{});
 }
 
 // Second phase of the two-phase BatchNorm backward: gx = gy * act'(x*scale+shift) * scale + dS1 + 2 * x * dS2 in ONE pass
 // (the first phase is affine_act_bwd with gx == NULL: reductions only).  10 bytes per element instead of the 12 of
 // "write gx, then read it back for the statistics path".
 template <typename T, bool VEC, bool HS = false>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__ gy, int ldg, const T* __restrict__ x, int ldx,
-                                                           T* __restrict__ gx, int ldgx, const float* __restrict__ scale,
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* gy, int ldg, const T* x, int ldx,
+                                                           T* gx, int ldgx, const float* __restrict__ scale,
                                                            const float* __restrict__ shift, const double* __restrict__ dS, int ldc,
                                                            int C, long npix_g, int act, RowGeom rg) {
   constexpr int N = Unit<T, VEC>::N;
@@ -248,36 +400,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     sc[e] = scale[g * C + c0 + e]; sf[e] = shift[g * C + c0 + e];
     a[e] = (float)dS[((long)g * 2 + 0) * ldc + c0 + e]; b2[e] = (float)(2.0 * dS[((long)g * 2 + 1) * ldc + c0 + e]);
   }
-  const long base = (long)g * npix_g;
-  const long stride = (long)gridDim.x * rg.ty;
-  for (long pix0 = (long)blockIdx.x * rg.ty + ty; pix0 < npix_g; pix0 += 4 * stride) {
-    float gv[4][N], xv[4][N];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const long pix = pix0 + k * stride;
-      if (pix < npix_g) {
-        Unit<T, VEC>::load(gy + (base + pix) * ldg + c0, gv[k]);
-        Unit<T, VEC>::load(x + (base + pix) * ldx + c0, xv[k]);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const long pix = pix0 + k * stride;
-      if (pix < npix_g) {
-#pragma unroll
-        for (int e = 0; e < N; ++e) {
-          const float z = fmaf(xv[k][e], sc[e], sf[e]);
-          float gm = gv[k][e];
-          if (act == 1) gm = z > 0.f ? gm : 0.f;
-          else if (act == 2) { const float sg = 1.f / (1.f + __expf(-z)); gm *= sg * (1.f - sg); }
-          else if (HS && (act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID)) gm *= act_hs_d(z, act);
-          // the first-phase result the one-pass form would have stored is rounded to T before the statistics path is added
-          gv[k][e] = Elem<T>::rnd(gm * sc[e]) + fmaf(xv[k][e], b2[e], a[e]);
-        }
-        Unit<T, VEC>::store(gx + (base + pix) * ldgx + c0, gv[k]);
-      }
-    }
-  }
+  const long base = (long)g * npix_g, first = (long)blockIdx.x * rg.ty + ty, stride = (long)gridDim.x * rg.ty;
+  if (npix_g <= stride) bn_bwd_rows<T, VEC, HS, 1>(gy, ldg, x, ldx, gx, ldgx, sc, sf, a, b2, c0, base, npix_g, first, stride, act);
+  else bn_bwd_rows<T, VEC, HS, 4>(gy, ldg, x, ldx, gx, ldgx, sc, sf, a, b2, c0, base, npix_g, first, stride, act);
 }
 
 // ---- consumer-side finalize: the per-channel kernels between a reduction and the pass that uses its result are pure
@@ -285,11 +410,69 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
 // elementwise pass derive the coefficients of ITS channel slice from the replica sums (a few KB from L2), and let the
 // first workgroup of each slice publish them / update the parameters' side outputs.
 
+// Replica fold of one channel, the thread's share r = rl, rl + P, ... < nrep of the values p[r * rs], added in ascending r.
+// fold_issue only loads: the first kFoldWin of the share, unrolled (a uniform test ends the window, the lane's own r is
+// predicated), so that a workgroup has every replica load and every per-channel parameter load of its prologue in flight
+// before it waits once.  fold_sum adds them and walks what lies beyond the window (nrep > 16 P) the plain way.  (The loop
+// `for (r = rl; r < nrep; r += P) a += p[..]` compiled to one load + wait per iteration: 8 serial L2 round trips at
+// C = 64, 16 at C = 128 with 32 replicas.)
+constexpr int kFoldWin = 16;   // covers 32 replicas at C = 128 (2 replica lanes)
+constexpr int kSffWin = 4;     // stats_fix_fin always has 8 replica lanes: 32 replicas
+
+// `base` is the workgroup's (uniform) pointer to replica 0, `lane` the thread's own element offset c + rl * rs: the loads
+// then share one 32-bit offset register over a scalar base instead of a 64-bit address pair each.  The offset is formed
+// in 32 bits: (c + rl * rs) * sizeof(V) must stay below 4 GiB, which fold_span_ok() checks on the host before a launch.
+template <typename V>
+__device__ __forceinline__ V fold_at(const V* base, long j_rs, unsigned lane) {
+  return *reinterpret_cast<const V*>(reinterpret_cast<const char*>(base + j_rs) + lane * (unsigned)sizeof(V));
+}
+
+template <typename V, int W>
+__device__ __forceinline__ void fold_issue(const V* base, unsigned lane, long rs, int rl, int P, int nrep, V (&v)[W]) {
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    v[j] = 0;
+    if (j * P < nrep) {           // uniform
+      if (rl + j * P < nrep) v[j] = fold_at(base, (long)j * P * rs, lane);
+    }
+  }
+}
+
+template <typename V, int W>
+__device__ __forceinline__ V fold_sum(const V* base, unsigned lane, long rs, int rl, int P, int nrep, const V (&v)[W]) {
+  V a = 0;
+#pragma unroll
+  for (int j = 0; j < W; ++j)
+    if (rl + j * P < nrep) a += v[j];
+  for (int j = W; rl + j * P < nrep; ++j) a += fold_at(base, (long)j * P * rs, lane);
+  return a;
+}
+
+// the plain loop over the whole share (kernels instantiated without the window, see WIN below)
+// (both sums in ONE loop: a round trip per replica, not two)
+template <typename V, typename A>
+__device__ __forceinline__ void fold_plain(const V* base0, const V* base1, unsigned lane, long rs, int rl, int P, int nrep, A& a0, A& a1) {
+  V s0 = 0, s1 = 0;
+  for (int j = 0; rl + j * P < nrep; ++j) { s0 += fold_at(base0, (long)j * P * rs, lane); s1 += fold_at(base1, (long)j * P * rs, lane); }
+  a0 = (A)s0; a1 = (A)s1;
+}
+
+// The writer workgroup of a channel slice (blockIdx.x == 0, group 0) needs the sums of ALL groups, in order.  With up to
+// kFoldSlots groups it folds them into the one barrier pair every workgroup has (one window after the other: two f64
+// windows side by side are 128 VGPRs, which would cost the streaming body below a wave per SIMD); with more it walks them
+// one barrier pair each (`round`s).  The launch lasts as long as its slowest workgroup: with the two tower groups the
+// serial walk made the writer's chain twice everybody else's.
+// WIN: the window and the shared barrier pair.  Launches with two or more statistics groups (the DenseNet towers, where the
+// writer's chain is what the launch waits for) take it; with ONE group it measured slower at every shape of the step whose
+// grid is at the workgroup cap (+1.4 us on 7.4 for affine_act_bn, +2.5 on 7.6 for bn_bwd_apply_fin at 65536 x 64), so those
+// launches keep the plain loop and the walk.
+constexpr int kFoldSlots = 2;
+
 // y = act(BatchNorm_train(x)) (+ res) straight from the statistics S (f64 [nrep][G][2][ldc]) of x.
 // Also writes scale/shift/mean/invstd ([G][C], for the backward pass) and updates the running statistics (groups in order).
-template <typename T, bool VEC, bool HS = false>
-__global__ __launch_bounds__(256) void affine_act_bn_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy,
-                                                            const T* __restrict__ res, int ldr,
+template <typename T, bool VEC, bool HS = false, bool WIN = true>
+__global__ __launch_bounds__(256) void affine_act_bn_kernel(const T* x, int ldx, T* y, int ldy,
+                                                            const T* res, int ldr,
                                                             const double* __restrict__ S, int ldc, int nrep,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             float* __restrict__ rmean, float* __restrict__ rvar,
@@ -298,59 +481,91 @@ __global__ __launch_bounds__(256) void affine_act_bn_kernel(const T* __restrict_
                                                             int C, long npix_g, double count, float eps, float momentum, int act, RowGeom rg) {
   constexpr int N = Unit<T, VEC>::N;
   __shared__ float s_sc[64 * 8], s_sf[64 * 8];
-  __shared__ double s_red[2][256];
+  __shared__ double s_red[kFoldSlots][2][256];
   const int G = gridDim.z, g = blockIdx.z;
   const int ch0 = blockIdx.y * rg.tx * N;
   const int nch = min(rg.tx, rg.units - (int)blockIdx.y * rg.tx) * N;
   // Replica fold of the workgroup's channels in ONE round trip: the 256 threads are (channel slot cl, replica lane rl) with as
-  // many replica lanes as fit (64 channels: 4 lanes of 8 replicas each), one barrier pair per statistics group.  (The first
+  // many replica lanes as fit (64 channels: 4 lanes of 8 replicas each), one barrier pair per workgroup.  (The first
   // form walked the channels 32 at a time — four dependent load / barrier rounds for the 128-channel DenseNet bottlenecks,
   // most of this kernel's time on the small maps.)
   const int ncp = nch <= 32 ? 32 : nch <= 64 ? 64 : nch <= 128 ? 128 : 256;
   const int P = 256 / ncp;
   const int cl = threadIdx.x & (ncp - 1), rl = threadIdx.x / ncp;
   const bool writer = blockIdx.x == 0 && g == 0 && rmean;   // wave-uniform per workgroup: running statistics of the slice
+  const int per = WIN && writer && G <= kFoldSlots ? G : 1;  // groups per round
+  const int nround = writer && per == 1 ? G : 1;
+  const long rs = (long)G * 2 * ldc;
   for (int cb = 0; cb < nch; cb += ncp) {
     const int c = ch0 + cb + cl;
     const bool okc = cb + cl < nch && c < C;
-    float rm = 0.f, rv = 0.f;
-    if (writer && rl == 0 && okc) { rm = rmean[c]; rv = rvar[c]; }
-    for (int gg = 0; gg < G; ++gg) {
-      if (gg != g && !writer) continue;                      // everybody needs its own group; the writer all, in order
-      double a1 = 0., a2 = 0.;
+    const bool lead = rl == 0 && okc;
+    const unsigned lane = (unsigned)(c + rl * rs);
+    float rm = 0.f, rv = 0.f, gm = 1.f, bt = 0.f;
+    for (int rd = 0; rd < nround; ++rd) {
+      const int g0 = writer ? rd : g;                        // the writer sits in group 0: everybody's own group comes first
+      double a1[kFoldSlots], a2[kFoldSlots];
+#pragma unroll
+      for (int s = 0; s < kFoldSlots; ++s) { a1[s] = 0.; a2[s] = 0.; }
       if (okc) {
-        for (int r = rl; r < nrep; r += P) {
-          const double* Sr = S + (long)r * G * 2 * ldc;
-          a1 += Sr[((long)gg * 2 + 0) * ldc + c];
-          a2 += Sr[((long)gg * 2 + 1) * ldc + c];
+#pragma unroll
+        for (int s = 0; s < kFoldSlots; ++s) {
+          if (s < per) {
+            const double* S1 = S + ((long)(g0 + s) * 2 + 0) * ldc;
+            const double* S2 = S + ((long)(g0 + s) * 2 + 1) * ldc;
+            double v1[kFoldWin], v2[kFoldWin];
+            if constexpr (WIN) {
+              fold_issue(S1, lane, rs, rl, P, nrep, v1);
+              fold_issue(S2, lane, rs, rl, P, nrep, v2);
+            }
+            if (s == 0 && rd == 0 && rl == 0) {              // the per-channel parameters travel with the replicas
+              if (gamma) gm = gamma[c];
+              if (beta) bt = beta[c];
+              if (writer) { rm = rmean[c]; rv = rvar[c]; }
+            }
+            if constexpr (WIN) {
+              issued();
+              a1[s] = fold_sum(S1, lane, rs, rl, P, nrep, v1);
+              a2[s] = fold_sum(S2, lane, rs, rl, P, nrep, v2);
+            } else {
+              fold_plain(S1, S2, lane, rs, rl, P, nrep, a1[s], a2[s]);
+            }
+          }
         }
       }
       __syncthreads();
-      s_red[0][threadIdx.x] = a1; s_red[1][threadIdx.x] = a2;
+#pragma unroll
+      for (int s = 0; s < kFoldSlots; ++s)
+        if (s < per) { s_red[s][0][threadIdx.x] = a1[s]; s_red[s][1][threadIdx.x] = a2[s]; }
       __syncthreads();
-      if (rl == 0 && okc) {
-        double s1 = 0., s2 = 0.;
-        for (int r = 0; r < P; ++r) { s1 += s_red[0][r * ncp + cl]; s2 += s_red[1][r * ncp + cl]; }
-        const double mu = s1 / count;
-        double var = s2 / count - mu * mu;
-        if (var < 0.) var = 0.;
-        if (gg == g) {
-          const float inv = (float)(1.0 / sqrt(var + (double)eps));
-          const float sc = (gamma ? gamma[c] : 1.f) * inv;
-          const float sf = (float)((double)(beta ? beta[c] : 0.f) - mu * (double)sc);
-          s_sc[cb + cl] = sc; s_sf[cb + cl] = sf;
-          if (blockIdx.x == 0) {
-            scale_out[g * C + c] = sc; shift_out[g * C + c] = sf; mean_out[g * C + c] = (float)mu; invstd_out[g * C + c] = inv;
+      if (lead) {
+#pragma unroll
+        for (int s = 0; s < kFoldSlots; ++s) {
+          if (s >= per) continue;
+          const int gg = g0 + s;
+          double s1 = 0., s2 = 0.;
+          for (int r = 0; r < P; ++r) { s1 += s_red[s][0][r * ncp + cl]; s2 += s_red[s][1][r * ncp + cl]; }
+          const double mu = s1 / count;
+          double var = s2 / count - mu * mu;
+          if (var < 0.) var = 0.;
+          if (gg == g) {
+            const float inv = (float)(1.0 / sqrt(var + (double)eps));
+            const float sc = gm * inv;
+            const float sf = (float)((double)bt - mu * (double)sc);
+            s_sc[cb + cl] = sc; s_sf[cb + cl] = sf;
+            if (blockIdx.x == 0) {
+              scale_out[g * C + c] = sc; shift_out[g * C + c] = sf; mean_out[g * C + c] = (float)mu; invstd_out[g * C + c] = inv;
+            }
           }
-        }
-        if (writer) {
-          const double unb = count > 1. ? var * count / (count - 1.) : var;
-          rm = (1.f - momentum) * rm + momentum * (float)mu;
-          rv = (1.f - momentum) * rv + momentum * (float)unb;
+          if (writer) {
+            const double unb = count > 1. ? var * count / (count - 1.) : var;
+            rm = (1.f - momentum) * rm + momentum * (float)mu;
+            rv = (1.f - momentum) * rv + momentum * (float)unb;
+          }
         }
       }
     }
-    if (writer && rl == 0 && okc) { rmean[c] = rm; rvar[c] = rv; }
+    if (writer && lead) { rmean[c] = rm; rvar[c] = rv; }
   }
   __syncthreads();
   ROW_TXTY(rg, tx, ty);
@@ -360,28 +575,15 @@ __global__ __launch_bounds__(256) void affine_act_bn_kernel(const T* __restrict_
   float sc[N], sf[N];
 #pragma unroll
   for (int e = 0; e < N; ++e) { sc[e] = s_sc[tx * N + e]; sf[e] = s_sf[tx * N + e]; }
-  const long base = (long)g * npix_g;
-  for (long pix = (long)blockIdx.x * rg.ty + ty; pix < npix_g; pix += (long)gridDim.x * rg.ty) {
-    float f[N], r[N];
-    Unit<T, VEC>::load(x + (base + pix) * ldx + c0, f);
-    if (res) Unit<T, VEC>::load(res + (base + pix) * ldr + c0, r);
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-      float v = fmaf(f[e], sc[e], sf[e]);
-      if (act == 1) v = fmaxf(v, 0.f);
-      else if (act == 2) v = 1.f / (1.f + __expf(-v));
-      else if (HS && (act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID)) v = act_hs(v, act);
-      if (res) v += r[e];
-      f[e] = v;
-    }
-    Unit<T, VEC>::store(y + (base + pix) * ldy + c0, f);
-  }
+  const long base = (long)g * npix_g, first = (long)blockIdx.x * rg.ty + ty, stride = (long)gridDim.x * rg.ty;
+  if (res) affine_act_rows<T, VEC, HS, true>(x, ldx, y, ldy, res, ldr, sc, sf, c0, base, npix_g, first, stride, act);
+  else affine_act_rows<T, VEC, HS, false>(x, ldx, y, ldy, res, ldr, sc, sf, c0, base, npix_g, first, stride, act);
 }
 
 // gx = gy * act'(x*scale+shift) * scale + dS1 + 2*x*dS2 with dS derived in the kernel from the (dscale, dshift) replica
 // sums of the first phase; the first workgroup of a channel slice also writes dgamma / dbeta (summed over groups).
-template <typename T, bool VEC, bool HS = false>
-__global__ __launch_bounds__(256) void bn_bwd_apply_fin_kernel(const T* gy, int ldg, const T* __restrict__ x, int ldx,
+template <typename T, bool VEC, bool HS = false, bool WIN = true>
+__global__ __launch_bounds__(256) void bn_bwd_apply_fin_kernel(const T* gy, int ldg, const T* x, int ldx,
                                                                T* gx, int ldgx, const float* __restrict__ scale,
                                                                const float* __restrict__ shift, const float* __restrict__ dscale,
                                                                const float* __restrict__ dshift, int nrep,
@@ -391,97 +593,127 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fin_kernel(const T* gy, int 
                                                                double inv_count, int act, const double* __restrict__ dsum, RowGeom rg) {
   constexpr int N = Unit<T, VEC>::N;
   __shared__ float s_a[64 * 8], s_b2[64 * 8];
-  __shared__ float s_red[2][256];
+  __shared__ float s_red[kFoldSlots][2][256];
   const int G = gridDim.z, g = blockIdx.z;
   const int ch0 = blockIdx.y * rg.tx * N;
   const int nch = min(rg.tx, rg.units - (int)blockIdx.y * rg.tx) * N;
+  // the streaming pass's own coefficients are asked for first: they arrive while the fold runs
+  ROW_TXTY(rg, tx, ty);
+  const int u = blockIdx.y * rg.tx + tx;
+  const bool live = ty < rg.ty && u < rg.units;
+  const int c0 = u * N;
+  float sc[N], sf[N];
+  if (live) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) { sc[e] = scale[g * C + c0 + e]; sf[e] = shift[g * C + c0 + e]; }
+  }
   // replica fold in one round trip (see affine_act_bn_kernel): threads = (channel slot cl, replica lane rl)
   const int ncp = nch <= 32 ? 32 : nch <= 64 ? 64 : nch <= 128 ? 128 : 256;
   const int P = 256 / ncp;
   const int cl = threadIdx.x & (ncp - 1), rl = threadIdx.x / ncp;
   const bool writer = blockIdx.x == 0 && g == 0 && dgamma;     // wave-uniform per workgroup
+  const int per = WIN && writer && G <= kFoldSlots ? G : 1;    // groups per round
+  const int nround = writer && per == 1 ? G : 1;
   for (int cb = 0; cb < nch; cb += ncp) {
     const int c = ch0 + cb + cl;
     const bool okc = cb + cl < nch && c < C;
-    float dg = 0.f, db = 0.f;
-    for (int gg = 0; gg < G; ++gg) {
-      if (gg != g && !writer) continue;                         // everybody needs its own group; the writer all of them
-      float ds = 0.f, dh = 0.f;
+    const bool lead = rl == 0 && okc;
+    float dg = 0.f, db = 0.f, gm = 1.f, dg0 = 0.f, db0 = 0.f;
+    for (int rd = 0; rd < nround; ++rd) {
+      const int g0 = writer ? rd : g;
+      float ds[kFoldSlots], dh[kFoldSlots], mu[kFoldSlots], inv[kFoldSlots];
+#pragma unroll
+      for (int s = 0; s < kFoldSlots; ++s) { ds[s] = 0.f; dh[s] = 0.f; mu[s] = 0.f; inv[s] = 0.f; }
       if (okc) {
-        if (dsum) {   // f64 [nrep][G][2][C] as written by the epilogue of sdhip_conv2d_fwd_bnbwd
-          double d0 = 0., d1 = 0.;
-          for (int r = rl; r < nrep; r += P) { d0 += dsum[(((long)r * G + gg) * 2 + 0) * C + c]; d1 += dsum[(((long)r * G + gg) * 2 + 1) * C + c]; }
-          ds = (float)d0; dh = (float)d1;
-        } else {
-          for (int r = rl; r < nrep; r += P) { ds += dscale[((long)r * G + gg) * C + c]; dh += dshift[((long)r * G + gg) * C + c]; }
+#pragma unroll
+        for (int s = 0; s < kFoldSlots; ++s) {
+          if (s >= per) continue;
+          const int gg = g0 + s;
+          auto params = [&]() {                                 // the per-channel parameters travel with the replicas
+            if (rl != 0) return;
+            mu[s] = mean[gg * C + c]; inv[s] = invstd[gg * C + c];
+            if (s == 0 && rd == 0) {
+              if (gamma) gm = gamma[c];
+              if (writer && acc_par) { dg0 = dgamma[c]; db0 = dbeta[c]; }
+            }
+          };
+          if (dsum) {   // f64 [nrep][G][2][C] as written by the epilogue of sdhip_conv2d_fwd_bnbwd
+            const long rs = (long)G * 2 * C;
+            const unsigned lane = (unsigned)(c + rl * rs);
+            const double* p0 = dsum + ((long)gg * 2 + 0) * C;
+            const double* p1 = dsum + ((long)gg * 2 + 1) * C;
+            if constexpr (WIN) {
+              double v0[kFoldWin], v1[kFoldWin];
+              fold_issue(p0, lane, rs, rl, P, nrep, v0);
+              fold_issue(p1, lane, rs, rl, P, nrep, v1);
+              params();
+              issued();
+              ds[s] = (float)fold_sum(p0, lane, rs, rl, P, nrep, v0);
+              dh[s] = (float)fold_sum(p1, lane, rs, rl, P, nrep, v1);
+            } else {
+              params();
+              fold_plain(p0, p1, lane, rs, rl, P, nrep, ds[s], dh[s]);
+            }
+          } else {
+            const long rs = (long)G * C;
+            const unsigned lane = (unsigned)(c + rl * rs);
+            const float* p0 = dscale + (long)gg * C;
+            const float* p1 = dshift + (long)gg * C;
+            if constexpr (WIN) {
+              float v0[kFoldWin], v1[kFoldWin];
+              fold_issue(p0, lane, rs, rl, P, nrep, v0);
+              fold_issue(p1, lane, rs, rl, P, nrep, v1);
+              params();
+              issued();
+              ds[s] = fold_sum(p0, lane, rs, rl, P, nrep, v0);
+              dh[s] = fold_sum(p1, lane, rs, rl, P, nrep, v1);
+            } else {
+              params();
+              fold_plain(p0, p1, lane, rs, rl, P, nrep, ds[s], dh[s]);
+            }
+          }
         }
       }
       __syncthreads();
-      s_red[0][threadIdx.x] = ds; s_red[1][threadIdx.x] = dh;
+#pragma unroll
+      for (int s = 0; s < kFoldSlots; ++s)
+        if (s < per) { s_red[s][0][threadIdx.x] = ds[s]; s_red[s][1][threadIdx.x] = dh[s]; }
       __syncthreads();
-      if (rl == 0 && okc) {
-        ds = 0.f; dh = 0.f;
-        for (int r = 0; r < P; ++r) { ds += s_red[0][r * ncp + cl]; dh += s_red[1][r * ncp + cl]; }
-        const float gm = gamma ? gamma[c] : 1.f;
-        const float mu = mean[gg * C + c], inv = invstd[gg * C + c];
-        const float t = ds - mu * dh;
-        dg += inv * t; db += dh;
-        if (gg == g) {
-          const double dinv = (double)gm * t;
-          const double dvar = -0.5 * dinv * (double)inv * inv * inv;
-          const double dmu = -(double)gm * inv * dh - 2.0 * mu * dvar;
-          s_a[cb + cl] = (float)(dmu * inv_count);
-          s_b2[cb + cl] = (float)(2.0 * dvar * inv_count);
+      if (lead) {
+#pragma unroll
+        for (int s = 0; s < kFoldSlots; ++s) {
+          if (s >= per) continue;
+          const int gg = g0 + s;
+          float fs = 0.f, fh = 0.f;
+          for (int r = 0; r < P; ++r) { fs += s_red[s][0][r * ncp + cl]; fh += s_red[s][1][r * ncp + cl]; }
+          const float t = fs - mu[s] * fh;
+          dg += inv[s] * t; db += fh;
+          if (gg == g) {
+            const double dinv = (double)gm * t;
+            const double dvar = -0.5 * dinv * (double)inv[s] * inv[s] * inv[s];
+            const double dmu = -(double)gm * inv[s] * fh - 2.0 * mu[s] * dvar;
+            s_a[cb + cl] = (float)(dmu * inv_count);
+            s_b2[cb + cl] = (float)(2.0 * dvar * inv_count);
+          }
         }
       }
     }
-    if (writer && rl == 0 && okc) {      // pscale = 1 / world size when the sums are global (the gradient all-reduce adds the ranks' shares)
+    if (writer && lead) {      // pscale = 1 / world size when the sums are global (the gradient all-reduce adds the ranks' shares)
       dg *= pscale; db *= pscale;
-      dgamma[c] = acc_par ? dgamma[c] + dg : dg;
-      dbeta[c] = acc_par ? dbeta[c] + db : db;
+      dgamma[c] = acc_par ? dg0 + dg : dg;
+      dbeta[c] = acc_par ? db0 + db : db;
     }
   }
   __syncthreads();
-  ROW_TXTY(rg, tx, ty);
-  const int u = blockIdx.y * rg.tx + tx;
-  if (ty >= rg.ty || u >= rg.units) return;
-  const int c0 = u * N;
-  float sc[N], sf[N], a[N], b2[N];
+  if (!live) return;
+  float a[N], b2[N];
 #pragma unroll
-  for (int e = 0; e < N; ++e) {
-    sc[e] = scale[g * C + c0 + e]; sf[e] = shift[g * C + c0 + e];
-    a[e] = s_a[tx * N + e]; b2[e] = s_b2[tx * N + e];
-  }
-  const long base = (long)g * npix_g;
-  const long stride = (long)gridDim.x * rg.ty;
-  for (long pix0 = (long)blockIdx.x * rg.ty + ty; pix0 < npix_g; pix0 += 4 * stride) {
-    float gv[4][N], xv[4][N];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const long pix = pix0 + k * stride;
-      if (pix < npix_g) {
-        Unit<T, VEC>::load(gy + (base + pix) * ldg + c0, gv[k]);
-        Unit<T, VEC>::load(x + (base + pix) * ldx + c0, xv[k]);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const long pix = pix0 + k * stride;
-      if (pix < npix_g) {
-#pragma unroll
-        for (int e = 0; e < N; ++e) {
-          const float z = fmaf(xv[k][e], sc[e], sf[e]);
-          float gm = gv[k][e];
-          if (act == 1) gm = z > 0.f ? gm : 0.f;
-          else if (act == 2) { const float sg = 1.f / (1.f + __expf(-z)); gm *= sg * (1.f - sg); }
-          else if (HS && (act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID)) gm *= act_hs_d(z, act);
-          gv[k][e] = Elem<T>::rnd(gm * sc[e]) + fmaf(xv[k][e], b2[e], a[e]);
-        }
-        Unit<T, VEC>::store(gx + (base + pix) * ldgx + c0, gv[k]);
-      }
-    }
-  }
+  for (int e = 0; e < N; ++e) { a[e] = s_a[tx * N + e]; b2[e] = s_b2[tx * N + e]; }
+  const long base = (long)g * npix_g, first = (long)blockIdx.x * rg.ty + ty, stride = (long)gridDim.x * rg.ty;
+  if (npix_g <= stride) bn_bwd_rows<T, VEC, HS, 1>(gy, ldg, x, ldx, gx, ldgx, sc, sf, a, b2, c0, base, npix_g, first, stride, act);
+  else bn_bwd_rows<T, VEC, HS, 4>(gy, ldg, x, ldx, gx, ldgx, sc, sf, a, b2, c0, base, npix_g, first, stride, act);
 }
+
 
 // S[g][0][c] += sum x, S[g][1][c] += sum x^2  (f64 atomics)
 template <typename T, bool VEC>
@@ -631,6 +863,9 @@ Plan plan(int units, long npix_g, int G, int max_blocks = 2048) {
 
 // workgroups of the consumer-side-finalize kernels: each one re-derives its coefficients from the replica sums (KBs from L2)
 int tune_fused_blocks() { return sdhip_diag().tune_fused_blocks; }
+
+// the 32-bit lane offset of fold_at: the last replica lane (at most 8 of them) of the last channel, in bytes
+inline bool fold_span_ok(long rs, int C, size_t elem) { return (unsigned long)(7 * rs + C) * elem < (1UL << 32); }
 
 int check_rows(const char* who, long npix, int C, int G, int dtype) {
   SDHIP_CHECK_ARG(npix > 0 && C > 0 && G >= 1 && npix % G == 0, "%s: bad shape npix=%ld C=%d groups=%d", who, npix, C, G);
@@ -835,16 +1070,17 @@ extern "C" int sdhip_affine_act_bn(const void* x, int ldx, void* y, int ldy, con
   SDHIP_CHECK_ARG(x && y && stats && scale && shift && mean_out && invstd_out && ldx >= C && ldy >= C && (!res || ldr >= C),
                   "affine_act_bn: bad pointers/strides");
   SDHIP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr) && count > 0., "affine_act_bn: bad statistics arguments");
+  SDHIP_CHECK_ARG(fold_span_ok((long)G * 2 * ldc, C, sizeof(double)), "affine_act_bn: statistics replicas too far apart");
   SDHIP_CHECK_ARG(act == 0 || act == 1 || act == 2 || act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID, "affine_act_bn: activation %d", act);
   hipStream_t s = (hipStream_t)stream;
   sdhip_by_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     const bool v = sdhip_vec_ok<T>(C, {ldx, ldy, res ? ldr : 0}, {x, y, res});
     const Plan pl = plan(v ? C / Chunk<T>::N : C, npix / G, G, tune_fused_blocks());
-    sdhip_by_flag(v, [&](auto V) { sdhip_by_flag(hard_act(act), [&](auto HS) {
-      hipLaunchKernelGGL((affine_act_bn_kernel<T, V(), HS()>), pl.grid, dim3(256), 0, s, (const T*)x, ldx, (T*)y, ldy, (const T*)res, ldr, stats, ldc, nrep, gamma, beta, running_mean, running_var,
+    sdhip_by_flag(v, [&](auto V) { sdhip_by_flag(hard_act(act), [&](auto HS) { sdhip_by_flag(G >= 2, [&](auto WIN) {
+      hipLaunchKernelGGL((affine_act_bn_kernel<T, V(), HS(), WIN()>), pl.grid, dim3(256), 0, s, (const T*)x, ldx, (T*)y, ldy, (const T*)res, ldr, stats, ldc, nrep, gamma, beta, running_mean, running_var,
                          scale, shift, mean_out, invstd_out, C, npix / G, count, eps, momentum, act, pl.rg);
-    }); });
+    }); }); });
   });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
@@ -862,15 +1098,16 @@ static int bn_bwd_apply_fin_impl(const void* gy, int ldg, const void* x, int ldx
                   "bn_bwd_apply_fin: bad pointers/strides");
   SDHIP_CHECK_ARG((act == 0 || act == 1 || act == 2 || act == SDHIP_ACT_HSWISH || act == SDHIP_ACT_HSIGMOID) && count > 0. && (dgamma == nullptr) == (dbeta == nullptr),
                   "bn_bwd_apply_fin: bad arguments");
+  SDHIP_CHECK_ARG(fold_span_ok((long)G * 2 * C, C, sizeof(double)), "bn_bwd_apply_fin: replicas too far apart");
   hipStream_t s = (hipStream_t)stream;
   sdhip_by_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     const bool v = sdhip_vec_ok<T>(C, {ldg, ldx, ldgx}, {gy, x, gx});
     const Plan pl = plan(v ? C / Chunk<T>::N : C, npix / G, G, tune_fused_blocks());
-    sdhip_by_flag(v, [&](auto V) { sdhip_by_flag(hard_act(act), [&](auto HS) {
-      hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<T, V(), HS()>), pl.grid, dim3(256), 0, s, (const T*)gy, ldg, (const T*)x, ldx, (T*)gx, ldgx, scale, shift, dscale, dshift, nrep, gamma, mean, invstd,
+    sdhip_by_flag(v, [&](auto V) { sdhip_by_flag(hard_act(act), [&](auto HS) { sdhip_by_flag(G >= 2, [&](auto WIN) {
+      hipLaunchKernelGGL((bn_bwd_apply_fin_kernel<T, V(), HS(), WIN()>), pl.grid, dim3(256), 0, s, (const T*)gy, ldg, (const T*)x, ldx, (T*)gx, ldgx, scale, shift, dscale, dshift, nrep, gamma, mean, invstd,
                          dgamma, dbeta, accumulate_params, param_scale, C, npix / G, 1.0 / count, act, dsum, pl.rg);
-    }); });
+    }); }); });
   });
   SDHIP_LAUNCH_CHECK();
   return SDHIP_OK;
@@ -945,80 +1182,145 @@ extern "C" int sdhip_bn_finalize(const double* stats, int ldc, int nrep, const f
 // layer wrote, which needs exactly the top 32 of the dS just updated).  Here every workgroup re-derives the 32 coefficients
 // it needs from the replica sums (a few KB from L2) while the first ceil(Cf/32) workgroups also do the per-channel work for
 // all Cf channels (dgamma, dbeta, dS of the channels below the slice — the slice's own dS is consumed here and never again).
+// one statistics group of the per-channel part of stats_fix_fin, as its replica lane sees it
+struct SffGroup {
+  float v0[kSffWin], v1[kSffWin];     // replica windows of dscale / dshift
+  float ds, dh, mu, inv;
+  double d0, d1;                      // dS of the channel before this call (outside the slice)
+  const float *p0, *p1;
+  unsigned lane;
+  __device__ __forceinline__ void issue(const float* dscale, const float* dshift, const float* mean, const float* invstd,
+                                        const double* dS, int ldc, int gg, int c, int Cf, long rs, int rl, int nrep,
+                                        bool outside) {
+    p0 = dscale + (long)gg * Cf; p1 = dshift + (long)gg * Cf;
+    lane = (unsigned)(c + rl * rs);
+    fold_issue(p0, lane, rs, rl, 8, nrep, v0);
+    fold_issue(p1, lane, rs, rl, 8, nrep, v1);
+    mu = 0.f; inv = 0.f; d0 = 0.; d1 = 0.;
+    if (rl == 0) {
+      mu = mean[gg * Cf + c]; inv = invstd[gg * Cf + c];
+      if (outside) { d0 = dS[((long)gg * 2 + 0) * ldc + c]; d1 = dS[((long)gg * 2 + 1) * ldc + c]; }
+    }
+  }
+  __device__ __forceinline__ void sum(long rs, int rl, int nrep) {
+    ds = fold_sum(p0, lane, rs, rl, 8, nrep, v0);
+    dh = fold_sum(p1, lane, rs, rl, 8, nrep, v1);
+  }
+};
+
+// Both folds (the per-channel one of the first workgroups and the slice's) and every parameter they need are in flight before
+// the one wait, and they share one barrier pair; a second group of the per-channel fold joins that pair after a round trip
+// of its own, only groups beyond kFoldSlots cost the per-channel workgroups a further pair each.
 template <typename T>
-__global__ __launch_bounds__(256) void stats_fix_fin_kernel(const T* gin, int ldgi, const T* __restrict__ x, int ldx, T* gout, int ldgo,
+__global__ __launch_bounds__(256) void stats_fix_fin_kernel(const T* gin, int ldgi, const T* x, int ldx, T* gout, int ldgo,
                                                             long npix_g, RowGeom rg, double* __restrict__ dS, int ldc, int cs,
                                                             const float* __restrict__ dscale, const float* __restrict__ dshift, int nrep,
                                                             const float* __restrict__ gamma, const float* __restrict__ mean,
                                                             const float* __restrict__ invstd, float* __restrict__ dgamma,
                                                             float* __restrict__ dbeta, int acc_par, float pscale, int Cf, int G, double inv_count) {
   constexpr int N = Unit<T, true>::N;
-  __shared__ float red[2][8][32];
+  __shared__ float red[kFoldSlots + 1][2][8][32];       // the per-channel fold's group slots, then the slice's
   __shared__ float fa[32], fb[32];
   const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
   const int nfb = (Cf + 31) >> 5;
-  if (blockIdx.z == 0 && blockIdx.y == 0 && (int)blockIdx.x < nfb) {     // workgroup-uniform: per-channel work of block blockIdx.x
-    const int c = blockIdx.x * 32 + cl;
-    const bool okc = c < Cf;
-    float dg = 0.f, db = 0.f;
-    for (int g = 0; g < G; ++g) {
-      float ds = 0.f, dh = 0.f;
-      if (okc) {
-#pragma unroll 4
-        for (int r = rl; r < nrep; r += 8) { ds += dscale[((long)r * G + g) * Cf + c]; dh += dshift[((long)r * G + g) * Cf + c]; }
-      }
-      __syncthreads();
-      red[0][rl][cl] = ds; red[1][rl][cl] = dh;
-      __syncthreads();
-      if (rl == 0 && okc) {
-        ds = 0.f; dh = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) { ds += red[0][r][cl]; dh += red[1][r][cl]; }
-        const float gm = gamma[c];
-        const float mu = mean[g * Cf + c], inv = invstd[g * Cf + c];
-        const float t = ds - mu * dh;
-        dg += inv * t;
-        db += dh;
-        if (c < cs || c >= cs + 32) {                 // the slice's dS is formed (and consumed) by the elementwise part below
-          const double dinv = (double)gm * t;
-          const double dvar = -0.5 * dinv * (double)inv * inv * inv;
-          const double dmu = -(double)gm * inv * dh - 2.0 * mu * dvar;
-          dS[((long)g * 2 + 0) * ldc + c] += dmu * inv_count;
-          dS[((long)g * 2 + 1) * ldc + c] += dvar * inv_count;
-        }
-      }
-    }
-    if (rl == 0 && okc) {
-      dg *= pscale; db *= pscale;                    // (see bn_bwd_apply_fin_kernel)
-      dgamma[c] = acc_par ? dgamma[c] + dg : dg;
-      dbeta[c] = acc_par ? dbeta[c] + db : db;
-    }
-  }
-  // coefficients of the slice channels cs .. cs+31 for this workgroup's statistics group
   const int g = blockIdx.z;
-  {
-    const int c = cs + cl;
-    float ds = 0.f, dh = 0.f;
-#pragma unroll 4
-    for (int r = rl; r < nrep; r += 8) { ds += dscale[((long)r * G + g) * Cf + c]; dh += dshift[((long)r * G + g) * Cf + c]; }
-    __syncthreads();
-    red[0][rl][cl] = ds; red[1][rl][cl] = dh;
-    __syncthreads();
-    if (rl == 0) {
-      ds = 0.f; dh = 0.f;
+  const long rs = (long)G * Cf;
+  const bool chan = blockIdx.z == 0 && blockIdx.y == 0 && (int)blockIdx.x < nfb;   // workgroup-uniform: per-channel work of block blockIdx.x
+  const int per = G <= kFoldSlots ? G : 1, nround = G > kFoldSlots ? G : 1;
+  const int c = blockIdx.x * 32 + cl;                     // per-channel part
+  const bool okc = chan && c < Cf, lead = okc && rl == 0;
+  const bool outside = c < cs || c >= cs + 32;            // the slice's dS is formed (and consumed) by the elementwise part below
+  float dg = 0.f, db = 0.f, gmc = 0.f, dg0 = 0.f, db0 = 0.f;
+  // the group in slot `slot` of red: t, dgamma / dbeta shares, dS outside the slice
+  auto use = [&](const SffGroup& q, int slot, int gg) {
+    float fs = 0.f, fh = 0.f;
 #pragma unroll
-      for (int r = 0; r < 8; ++r) { ds += red[0][r][cl]; dh += red[1][r][cl]; }
-      const float gm = gamma[c];
-      const float mu = mean[g * Cf + c], inv = invstd[g * Cf + c];
-      const float t = ds - mu * dh;
-      const double dinv = (double)gm * t;
-      const double dvar = -0.5 * dinv * (double)inv * inv * inv;
-      const double dmu = -(double)gm * inv * dh - 2.0 * mu * dvar;
-      fa[cl] = (float)(dS[((long)g * 2 + 0) * ldc + c] + dmu * inv_count);
-      fb[cl] = (float)(2.0 * (dS[((long)g * 2 + 1) * ldc + c] + dvar * inv_count));
+    for (int r = 0; r < 8; ++r) { fs += red[slot][0][r][cl]; fh += red[slot][1][r][cl]; }
+    const float t = fs - q.mu * fh;
+    dg += q.inv * t;
+    db += fh;
+    if (outside) {
+      const double dinv = (double)gmc * t;
+      const double dvar = -0.5 * dinv * (double)q.inv * q.inv * q.inv;
+      const double dmu = -(double)gmc * q.inv * fh - 2.0 * q.mu * dvar;
+      dS[((long)gg * 2 + 0) * ldc + c] = q.d0 + dmu * inv_count;
+      dS[((long)gg * 2 + 1) * ldc + c] = q.d1 + dvar * inv_count;
     }
-    __syncthreads();
+  };
+  // issue: the slice's fold for this workgroup's statistics group, group 0 of the per-channel fold, all parameters
+  const int c2 = cs + cl;                                 // coefficients of the slice channels cs .. cs+31
+  const float* q0 = dscale + (long)g * Cf;
+  const float* q1 = dshift + (long)g * Cf;
+  const unsigned lane2 = (unsigned)(c2 + rl * rs);
+  float w0[kSffWin], w1[kSffWin];
+  fold_issue(q0, lane2, rs, rl, 8, nrep, w0);
+  fold_issue(q1, lane2, rs, rl, 8, nrep, w1);
+  float gm2 = 0.f, mu2 = 0.f, inv2 = 0.f;
+  double e0 = 0., e1 = 0.;
+  SffGroup A, B;
+  if (okc) {
+    A.issue(dscale, dshift, mean, invstd, dS, ldc, 0, c, Cf, rs, rl, nrep, outside);
+    if (rl == 0) {
+      gmc = gamma[c];
+      if (acc_par) { dg0 = dgamma[c]; db0 = dbeta[c]; }
+    }
   }
+  if (rl == 0) {   // last: the compiler converts some of these to f64 where they are loaded, which waits for them
+    gm2 = gamma[c2]; mu2 = mean[g * Cf + c2]; inv2 = invstd[g * Cf + c2];
+    e0 = dS[((long)g * 2 + 0) * ldc + c2]; e1 = dS[((long)g * 2 + 1) * ldc + c2];
+  }
+  issued();
+  red[kFoldSlots][0][rl][cl] = fold_sum(q0, lane2, rs, rl, 8, nrep, w0);
+  red[kFoldSlots][1][rl][cl] = fold_sum(q1, lane2, rs, rl, 8, nrep, w1);
+  if (chan) {
+    A.ds = 0.f; A.dh = 0.f; B.ds = 0.f; B.dh = 0.f;
+    if (okc) {
+      A.sum(rs, rl, nrep);
+      if (per == 2) {
+        B.issue(dscale, dshift, mean, invstd, dS, ldc, 1, c, Cf, rs, rl, nrep, outside);
+        issued();
+        B.sum(rs, rl, nrep);
+      }
+    }
+    red[0][0][rl][cl] = A.ds; red[0][1][rl][cl] = A.dh;
+    if (per == 2) { red[1][0][rl][cl] = B.ds; red[1][1][rl][cl] = B.dh; }
+  }
+  __syncthreads();
+  if (lead) {
+    use(A, 0, 0);
+    if (per == 2) use(B, 1, 1);
+  }
+  if (rl == 0) {
+    float fs = 0.f, fh = 0.f;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) { fs += red[kFoldSlots][0][r][cl]; fh += red[kFoldSlots][1][r][cl]; }
+    const float t = fs - mu2 * fh;
+    const double dinv = (double)gm2 * t;
+    const double dvar = -0.5 * dinv * (double)inv2 * inv2 * inv2;
+    const double dmu = -(double)gm2 * inv2 * fh - 2.0 * mu2 * dvar;
+    fa[cl] = (float)(e0 + dmu * inv_count);
+    fb[cl] = (float)(2.0 * (e1 + dvar * inv_count));
+  }
+  if (chan) {
+    for (int rd = 1; rd < nround; ++rd) {                  // groups beyond the slots, one barrier pair each
+      A.ds = 0.f; A.dh = 0.f;
+      if (okc) {
+        A.issue(dscale, dshift, mean, invstd, dS, ldc, rd, c, Cf, rs, rl, nrep, outside);
+        issued();
+        A.sum(rs, rl, nrep);
+      }
+      __syncthreads();   // previous group's partials are consumed
+      red[0][0][rl][cl] = A.ds; red[0][1][rl][cl] = A.dh;
+      __syncthreads();
+      if (lead) use(A, 0, rd);
+    }
+    if (lead) {
+      dg *= pscale; db *= pscale;                    // (see bn_bwd_apply_fin_kernel)
+      dgamma[c] = acc_par ? dg0 + dg : dg;
+      dbeta[c] = acc_par ? db0 + db : db;
+    }
+  }
+  __syncthreads();
   ROW_TXTY(rg, tx, ty);
   const int u = blockIdx.y * rg.tx + tx;
   if (ty >= rg.ty || u >= rg.units) return;
@@ -1026,15 +1328,8 @@ __global__ __launch_bounds__(256) void stats_fix_fin_kernel(const T* gin, int ld
   float a[N], b2[N];
 #pragma unroll
   for (int e = 0; e < N; ++e) { a[e] = fa[c0 + e]; b2[e] = fb[c0 + e]; }
-  const long base = (long)g * npix_g;
-  for (long pix = (long)blockIdx.x * rg.ty + ty; pix < npix_g; pix += (long)gridDim.x * rg.ty) {
-    float gv[N], xv[N];
-    Unit<T, true>::load(gin + (base + pix) * ldgi + c0, gv);
-    Unit<T, true>::load(x + (base + pix) * ldx + c0, xv);
-#pragma unroll
-    for (int e = 0; e < N; ++e) gv[e] = gv[e] + fmaf(xv[e], b2[e], a[e]);
-    Unit<T, true>::store(gout + (base + pix) * ldgo + c0, gv);
-  }
+  stats_fix_rows<T, true>(gin, ldgi, x, ldx, gout, ldgo, a, b2, c0, (long)g * npix_g, npix_g, (long)blockIdx.x * rg.ty + ty,
+                          (long)gridDim.x * rg.ty);
 }
 
 extern "C" int sdhip_stats_fix_fin(const void* gin, int ldgi, const void* x, int ldx, void* gout, int ldgo, long npix,
@@ -1045,6 +1340,7 @@ extern "C" int sdhip_stats_fix_fin(const void* gin, int ldgi, const void* x, int
   if (int rc = check_rows("stats_fix_fin", npix, 32, G, dtype)) return rc;
   SDHIP_CHECK_ARG(gin && x && gout && dS && dscale && dshift && gamma && mean && invstd && dgamma && dbeta && ldgi >= 32 && ldx >= 32 &&
                   ldgo >= 32 && cs >= 0 && cs + 32 <= Cf && ldc >= Cf && nrep >= 1 && count > 0., "stats_fix_fin: bad arguments");
+  SDHIP_CHECK_ARG(fold_span_ok((long)G * Cf, Cf, sizeof(float)), "stats_fix_fin: replicas too far apart");
   hipStream_t s = (hipStream_t)stream;
   const int nfb = sdhip_cdiv(Cf, 32);
   const int rc = sdhip_by_dtype(dtype, [&](auto tag) -> int {

@@ -117,6 +117,17 @@ template <typename T, bool VEC> struct Unit {
     if constexpr (VEC) *reinterpret_cast<u32x4*>(p) = Chunk<T>::pack(f);
     else Elem<T>::st(p, f[0]);
   }
+  // issue and use apart: raw() only loads (16 bytes, or one element); unpack() converts, once every load of a trip is on
+  // its way.  load() converts where it loads, so each guarded load of a trip waits for its own data.
+  using Raw = std::conditional_t<VEC, u32x4, T>;
+  static __device__ __forceinline__ Raw raw(const T* p) {
+    if constexpr (VEC) return *reinterpret_cast<const u32x4*>(p);
+    else return *p;
+  }
+  static __device__ __forceinline__ void unpack(const Raw& r, float* f) {
+    if constexpr (VEC) Chunk<T>::unpack(r, f);
+    else f[0] = Elem<T>::ld(&r);
+  }
 };
 
 // ---- hard activations of MobileNetV3 (models/mobilenetv3.py:44-61): act codes SDHIP_ACT_HSWISH / SDHIP_ACT_HSIGMOID ----
