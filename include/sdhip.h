@@ -478,6 +478,38 @@ int sdhip_disp_smooth(const float* left, long left_bs, long left_cs, int left_ps
                       void* workspace, long workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Operators of the Ext_small edge networks (models/dsnet_t2_ext_small.py, output type `edgeOut`): csrc/edge.hip.
+ * ------------------------------------------------------------------------- */
+/* The edge map compute_grad_mag(img, True, False) (util/utilTorchGate.py:198-204) as upstream actually computes it: convTri
+ * returns its input, the one-sided border differences are never recomputed, nothing is normalised.  Per channel, E read as 0
+ * outside the image:  Ox = 0.5 (E(y,x+1) - E(y,x-1)),  Oy = 0.5 (E(y+1,x) - E(y-1,x)),  out = sqrt(Ox^2 + Oy^2 + 1e-6).
+ * img: f32 or bf16 (in_dtype), channel c of pixel (y, x) of image b at img[b*img_bs + c*img_cs + (y*W + x)*img_ps] (NCHW,
+ *      channels-last or a channel slice of either), 1 <= C <= 4, H and W >= 2.
+ * out: f32 or bf16 (out_dtype), NHWC with pixel stride ldy >= C; channels C..ldy-1 are not written.  Arithmetic is f32.
+ * One launch; the result does not depend on the layout of img.  No backward: the image carries no gradient. */
+int sdhip_grad_mag(const void* img, long img_bs, long img_cs, long img_ps, int in_dtype, void* out, int ldy, int out_dtype,
+                   int B, int H, int W, int C, void* stream);
+/* lossEdge_fn (losses/multiLosses.py:166-182): the class-balanced binary cross-entropy of the edge head,
+ *   loss += (1/n) sum_i w_i (max(z_i, 0) - z_i t_i + log1p(exp(-|z_i|))),   grad_i = w_i (sigmoid(z_i) - t_i) / n   (WRITTEN)
+ * with w_i = N/(P+N) where t_i == 1, P/(P+N) where t_i == 0 and 0 for any other target value; P and N count the ones and
+ * zeros of all n elements (exact integers), the quotients are formed in f32 as the reference forms them.  P = 0 or N = 0:
+ * value and gradient are exactly 0.
+ * logits: f32 or bf16 (dtype), element i at logits[i*ldz] (the head's output may sit in a padded pixel); target: dense f32;
+ * grad: dense, of dtype.  Three launches (count, terms, fold) that keep integer counts and one f64 partial per workgroup in
+ * the workspace (sdhip_edge_bce_workspace_bytes(n) bytes, 8-byte aligned, no initialisation needed; < 0 for n outside
+ * [1, 2^40]): no float atomics, value and gradient are bitwise reproducible and independent of ldz and of alignment. */
+long sdhip_edge_bce_workspace_bytes(long n);
+int sdhip_edge_bce(const void* logits, long ldz, int dtype, const float* target, void* grad, double* loss, long n,
+                   void* workspace, long workspace_bytes, void* stream);
+/* y = cat(a * g, b * (1 - g)) along the channels (models/dsnet_t2_ext_small.py:361): a, b (npix, C), g (npix, 1), y ONE
+ * (npix, 2C) buffer with pixel stride ldy >= 2C.  Backward: ga = gy[:, :C] * g, gb = gy[:, C:] * (1 - g),
+ * gg[p] = sum_c (gy[p, c] a[p, c] - gy[p, C + c] b[p, c]), all WRITTEN, in one launch. */
+int sdhip_gate_pair_fwd(const void* a, int lda, const void* b, int ldb, const void* g, int ldg, void* y, int ldy, long npix,
+                        int C, int dtype, void* stream);
+int sdhip_gate_pair_bwd(const void* gy, int ldgy, const void* a, int lda, const void* b, int ldb, const void* g, int ldg,
+                        void* ga, int ldga, void* gb, int ldgb, void* gg, int ldgg, long npix, int C, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Uncertainty-weighted multitask loss (`-multaskloss 1|2`: multiTask_loss, util/utilTorchLoss.py:521-540, called at
  * models/dsnet_t2.py:1167,1296).  Per-pixel maps, reduction='none':
  *   seg:  map[p] = exp(-lv) * CE(logits[p,:], labels[p]) + lv      (F.cross_entropy(..., ignore_index, reduction='none'))

@@ -105,6 +105,14 @@ def disp_smooth_workspace_bytes(B, H, W):
     return n
 
 
+def edge_bce_workspace_bytes(n):
+    """Workspace of sdhip_edge_bce for n elements (include/sdhip.h)."""
+    nbytes = _lib.sdhip_edge_bce_workspace_bytes(n)
+    if nbytes <= 0:
+        raise SdhipError("sdhip_edge_bce_workspace_bytes: unsupported element count %d" % n)
+    return nbytes
+
+
 def dw_pool_parts(H, W, C, k, stride, dt):
     """Pool slots of sdhip_dw_conv_fwd for this input (include/sdhip.h)."""
     n = _lib.sdhip_dw_pool_parts(H, W, C, k, stride, dt)

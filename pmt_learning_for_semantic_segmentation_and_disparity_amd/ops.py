@@ -2099,6 +2099,193 @@ def disp_smooth_loss(left, disp_pred, seg_target, weight=1.0):
     return _DispSmoothFn.apply(left, disp_pred, seg_target, float(weight))
 
 
+# ============================================================================ Ext_small edge networks (csrc/edge.hip)
+def grad_mag(img, dtype=None):
+    """The edge map the reference harness feeds the `edgeOut` networks, utilTorchGate.compute_grad_mag(img, True, False)
+    (torch_implementation.py:136) as upstream computes it (include/sdhip.h has the closed form): per channel
+    sqrt(Ox^2 + Oy^2 + 1e-6) of the central differences with zero padding.  img: (B, C <= 4, H >= 2, W >= 2) f32 or bf16, NCHW,
+    channels-last or a channel slice of either (no copy is made); the result, `dtype` (default: img's), lives in NHWC memory at
+    the padded pixel stride the conv nodes read.  One launch, f32 arithmetic, no gradient: an image never requires one."""
+    if img.dim() != 4:
+        raise _lib.SdhipError("grad_mag: the image must be 4-D (B,C,H,W), got %s" % (tuple(img.shape),))
+    B, C, H, W = img.shape
+    if B < 1 or not 1 <= C <= 4 or H < 2 or W < 2:
+        raise _lib.SdhipError("grad_mag: need B >= 1, 1 <= C <= 4 and H, W >= 2, got %s" % (tuple(img.shape),))
+    _require_gpu(img)
+    dt_in = dtype_code(img)
+    dtype = img.dtype if dtype is None else dtype
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.SdhipError("grad_mag: output dtype %s (f32 and bf16 only)" % dtype)
+    if img.requires_grad:
+        raise _lib.SdhipError("grad_mag has no backward pass: the image must not require a gradient")
+    strides = _image_strides(img)
+    if strides is None:
+        img = img.contiguous()
+        strides = _image_strides(img)
+    out, ldy = alloc_nhwc(B, C, H, W, dtype, img.device)
+    call("sdhip_grad_mag", ptr(img), strides[0], strides[1], strides[2], dt_in, ptr(out), ldy, _lib.code_of(dtype), B, H, W, C, stream_ptr())
+    return out
+
+
+_edge_ws = {}
+
+
+def _check_edge_args(edge_logits, edges):
+    if edge_logits.dim() != 4 or edge_logits.shape[1] != 1 or tuple(edges.shape) != tuple(edge_logits.shape):
+        raise _lib.SdhipError("edge logits and edge target must both be (B,1,H,W), got %s and %s"
+                              % (tuple(edge_logits.shape), tuple(edges.shape)))
+    if edge_logits.numel() < 1:
+        raise _lib.SdhipError("edge loss of an empty tensor")
+    if edges.dtype != torch.float32:
+        raise _lib.SdhipError("the edge target must be f32 (got %s)" % edges.dtype)
+    if not edges.is_contiguous():
+        raise _lib.SdhipError("the edge target must be a dense (B,1,H,W) tensor")
+    dtype_code(edge_logits)
+
+
+def _edge_term(z, edges, loss):
+    """loss += lossEdge_fn(edges, z); returns the gradient w.r.t. z (dense, z's dtype): the three launches of sdhip_edge_bce."""
+    n = z.numel()
+    zv, ldz = nhwc_view(z)
+    nbytes = _lib.edge_bce_workspace_bytes(n)
+    key = (n, str(z.device))
+    ws = _edge_ws.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=z.device)
+        _edge_ws[key] = ws
+    g = torch.empty(tuple(z.shape), dtype=z.dtype, device=z.device)
+    call("sdhip_edge_bce", ptr(zv), ldz, dtype_code(zv), ptr(edges), ptr(g), ptr(loss), n, ptr(ws), ws.numel() * 8, stream_ptr())
+    return g
+
+
+class _EdgeLossFn(torch.autograd.Function):
+    """lossEdge_fn (losses/multiLosses.py:166-182) on the edge head: value and gradient in one node."""
+
+    @staticmethod
+    def forward(ctx, logits, edges):
+        loss = torch.zeros(1, dtype=torch.float64, device=logits.device)
+        ctx.save_for_backward(_edge_term(logits, edges, loss))
+        return loss.float().reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        g, = ctx.saved_tensors
+        return g * gout.to(g.dtype), None
+
+
+def edge_loss(edge_logits, edges):
+    """The reference's lossEdge_fn(edges, edge_logits): mean(w * BCEWithLogits(edge_logits, edges)) with the class-balancing
+    weight w = N/(P+N) on the pixels where edges == 1, P/(P+N) where edges == 0 and 0 on any other value, P and N the counts of
+    ones and zeros over the whole batch.  No positives or no negatives: value and gradient are exactly 0.
+      edge_logits — (B,1,H,W) f32 or bf16, dense or a 1-channel map inside a padded pixel stride (a head's output); the only
+                    input that gets a gradient (dense, in its dtype)
+      edges       — dense f32 (B,1,H,W)
+    Returns an f32 scalar; value and gradient are reproducible bit for bit."""
+    _check_edge_args(edge_logits, edges)
+    _require_gpu(edge_logits, edges)
+    return _EdgeLossFn.apply(edge_logits, edges)
+
+
+class _EdgeStepLossFn(torch.autograd.Function):
+    """total = CE(seg) + L1(disp) [+ lossEdge_fn(edges, edge logits)] — the loss of the reference's step for the `edgeOut`
+    networks (torch_implementation.py:170-171,279,304,320-325: one cross-entropy, `CFG.loss` is not consulted).  The gradients
+    w.r.t. the network outputs are produced in the same pass, as in _TrainLossFn."""
+
+    @staticmethod
+    def forward(ctx, edge_logits, disp, seg, seg_t, disp_t, edges, mask_invalid_disp, cw):
+        B, C, H, W = seg.shape
+        npix = B * H * W
+        dt = dtype_code(seg)
+        loss = torch.zeros(1, dtype=torch.float64, device=seg.device)
+        tv, ldt = nhwc_view(seg_t)
+        sv, ld = nhwc_view(seg)
+        gs = empty_nhwc(B, C, H, W, seg.dtype, seg.device)
+        if cw is None:
+            call("sdhip_ce_loss", ptr(sv), ld, ptr(tv), ldt, ptr(gs), C, ptr(loss), npix, C, 1.0, dt, stream_ptr())
+        else:
+            _seg_terms(seg, tv, ldt, gs, loss, 1.0, 0, cw)
+        dv, ldd = nhwc_view(disp)
+        if ldd != 1:      # 1-channel map inside a padded pixel stride (direct conv output): densify
+            dv = disp.contiguous()
+        gd = torch.empty_like(dv)
+        call("sdhip_l1_loss", ptr(dv), ptr(disp_t), ptr(gd), ptr(loss), npix, 1.0, int(mask_invalid_disp), dt, stream_ptr())
+        ge = _edge_term(edge_logits, edges, loss) if edges is not None else None
+        ctx.save_for_backward(ge, gd, gs)
+        return loss.float()
+
+    @staticmethod
+    def backward(ctx, g):
+        ge, gd, gs = ctx.saved_tensors
+        return ge, gd, gs, None, None, None, None, None      # d(total)/d(total) is 1 in the training step
+
+
+def edge_step_loss(edge_logits, disp, seg_logits, seg_target, disp_target, edges=None, mask_invalid_disp=False, class_weights=None):
+    """The loss of the reference step on the outputs `edge_ds, disp1, seg1, _` of an `edgeOut` network (Ext_small, Ext_smallv2):
+    cross-entropy of the ONE segmentation head + L1 of the disparity + lossEdge_fn(edges, edge_logits) as one node.
+      edges             — dense f32 (B,1,H,W) edge target, or None: the edge term is left out and the edge head gets no gradient
+      mask_invalid_disp — disparities <= 0 are invalid (train_loss)
+      class_weights     — the `-segWeight 1` table (length C) on the cross-entropy
+    Returns an f32 tensor of one element."""
+    _check_seg_args(seg_logits, seg_target, class_weights)
+    if tuple(disp.shape) != (seg_logits.shape[0], 1) + tuple(seg_logits.shape[2:]) or tuple(disp_target.shape) != tuple(disp.shape):
+        raise _lib.SdhipError("disparity and its target must be (B,1,H,W) of the segmentation's size, got %s and %s"
+                              % (tuple(disp.shape), tuple(disp_target.shape)))
+    if not disp_target.is_contiguous():
+        raise _lib.SdhipError("disparity target must be a dense (B,1,H,W) tensor")
+    if edges is not None:
+        _check_edge_args(edge_logits, edges)
+        if tuple(edges.shape) != tuple(disp.shape):
+            raise _lib.SdhipError("the edge target %s does not match the outputs %s" % (tuple(edges.shape), tuple(disp.shape)))
+    _require_gpu(edge_logits, disp, seg_logits, seg_target, disp_target, edges)
+    cw = seg_class_weights(class_weights, seg_logits.shape[1], seg_logits.device)
+    return _EdgeStepLossFn.apply(edge_logits, disp, seg_logits, seg_target, disp_target, edges, bool(mask_invalid_disp), cw)
+
+
+class _GatePairFn(torch.autograd.Function):
+    """cat(a * g, b * (1 - g), dim=1) written straight into one NHWC slab; ga, gb and gg come out of one backward launch."""
+
+    @staticmethod
+    def forward(ctx, a, b, g):
+        B, C, H, W = a.shape
+        av, lda = nhwc_view(a)
+        bv, ldb = nhwc_view(b)
+        gv, ldg = nhwc_view(g)
+        y, ldy = alloc_nhwc(B, 2 * C, H, W, a.dtype, a.device)
+        call("sdhip_gate_pair_fwd", ptr(av), lda, ptr(bv), ldb, ptr(gv), ldg, ptr(y), ldy, B * H * W, C, dtype_code(a), stream_ptr())
+        ctx.save_for_backward(av, bv, gv)
+        ctx.cfg = (lda, ldb, ldg)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        av, bv, gv = ctx.saved_tensors
+        lda, ldb, ldg = ctx.cfg
+        B, C, H, W = av.shape
+        gyv, ldgy = nhwc_view(gy)
+        ga = empty_nhwc(B, C, H, W, av.dtype, av.device)
+        gb = empty_nhwc(B, C, H, W, av.dtype, av.device)
+        gg = empty_nhwc(B, 1, H, W, av.dtype, av.device)
+        call("sdhip_gate_pair_bwd", ptr(gyv), ldgy, ptr(av), lda, ptr(bv), ldb, ptr(gv), ldg, ptr(ga), C, ptr(gb), C, ptr(gg), 1,
+             B * H * W, C, dtype_code(av), stream_ptr())
+        return ga, gb, gg
+
+
+def gate_pair(a, b, g):
+    """torch.cat((a * g, b * (1 - g)), 1) for a, b (B,C,H,W) and a one-channel gate g (B,1,H,W), all of one dtype (f32 / bf16):
+    the `s2_d*s2_at | s2_s*(1-s2_at)` line of the Ext_small networks (models/dsnet_t2_ext_small.py:361) as one launch that writes
+    both halves into one 2C-channel NHWC buffer, and one backward launch for all three gradients."""
+    if a.dim() != 4 or tuple(b.shape) != tuple(a.shape) or tuple(g.shape) != (a.shape[0], 1) + tuple(a.shape[2:]):
+        raise _lib.SdhipError("gate_pair: need a, b (B,C,H,W) and g (B,1,H,W), got %s, %s and %s"
+                              % (tuple(a.shape), tuple(b.shape), tuple(g.shape)))
+    if a.numel() < 1:
+        raise _lib.SdhipError("gate_pair of an empty tensor")
+    _require_gpu(a, b, g)
+    if not a.dtype == b.dtype == g.dtype:
+        raise _lib.SdhipError("gate_pair: a, b and g must share one dtype, got %s, %s and %s" % (a.dtype, b.dtype, g.dtype))
+    dtype_code(a)
+    return _GatePairFn.apply(a, b, g)
+
+
 # ============================================================================ dropout / global average pool
 _rng = {"seed": None, "layers": 0}
 

@@ -145,11 +145,28 @@ def model_outputs(model, dtype, left, right, seg, disp, extra=()):
     return model(x, y, *extra)
 
 
+def edge_loss(model, outs, seg, disp, edges, *, smooth_grad=0.0, use_lovasz=False, loss=None, class_weights=None,
+              mask_invalid_disp=False, **other):
+    """The loss of the reference step for an `edgeOut` network (`edge_outputs`: ext_small.Ext_small / Ext_smallv2), whose
+    outputs are `edge_ds, disp1, seg1, _` (torch_implementation.py:170-171): CE(outs[2]) + L1(outs[1]), plus
+    lossEdge_fn(edges, outs[0]) when the edge target is given (:320-323).  Upstream gives this output type one
+    ['cross_entropy'] head and never consults `-loss` (:279,286-288): Lovasz, a `loss=` list and smooth_grad are refused."""
+    if use_lovasz or loss is not None:
+        raise _lib.SdhipError("default_loss: an edge_outputs model has ONE cross-entropy head (the reference's edgeOut step does not "
+                              "consult -loss); use_lovasz / loss do not apply: pass use_lovasz=False and no loss list")
+    if smooth_grad or other.get("ignore_void") or other.get("seg3") is not None:
+        raise _lib.SdhipError("default_loss: smooth_grad / ignore_void / seg3 do not apply to an edge_outputs model")
+    return ops.edge_step_loss(outs[0], outs[1], outs[2], seg, disp, edges=edges, mask_invalid_disp=mask_invalid_disp,
+                              class_weights=class_weights)
+
+
 def default_loss(model, outs, seg, disp, *, left=None, smooth_grad=0.0, **train_loss_kwargs):
     """The loss of the reference step on the outputs of model_outputs.  Multitask: the sum of the three maps' means
     (torch_implementation.py:173-176,285-325), from the loss kernels' own sums.
     smooth_grad (non-zero): the weight of the `smooth_grad` disparity regulariser of lossDisp_fn (losses/multiLosses.py:143-146),
-    ops.disp_smooth_loss(left, outs[1], seg, smooth_grad), added to the rest; `left` is the f32 left image of the batch."""
+    ops.disp_smooth_loss(left, outs[1], seg, smooth_grad), added to the rest; `left` is the f32 left image of the batch.
+    An `edge_outputs` model (ext_small.Ext_small / Ext_smallv2) gets edge_loss above without the edge term, CE + L1: the
+    edge target is no input of a step (train.EdgeStepLoss carries it)."""
     if smooth_grad:
         if getattr(model, "multiTaskLoss", 0):
             raise _lib.SdhipError("default_loss: the multitask loss is the three maps' means; smooth_grad has no place in it")
@@ -157,6 +174,8 @@ def default_loss(model, outs, seg, disp, *, left=None, smooth_grad=0.0, **train_
             raise _lib.SdhipError("default_loss: smooth_grad needs the left image (left=...)")
     if getattr(model, "multiTaskLoss", 0):
         return multitask.step_loss(outs[4], outs[5], outs[6])
+    if getattr(model, "edge_outputs", False):
+        return edge_loss(model, outs, seg, disp, None, smooth_grad=smooth_grad, **train_loss_kwargs)
     # the `ThreeOutPuts` networks (warp.minidsnetDivide*) add the cross-entropy of their third segmentation map, outs[4]
     # (torch_implementation.py:157-158,298); Lovasz stays on outs[2], which the metrics score as well
     seg3 = outs[4] if getattr(model, "three_outputs", False) else None

@@ -103,6 +103,41 @@ class StepLoss:
                                  loss=self.seg_loss, class_weights=self.class_weights)
 
 
+class EdgeStepLoss:
+    """`TrainStep(model, loss_fn=EdgeStepLoss(model))`: the loss of the reference's `edgeOut` step (step.edge_loss) WITH its edge
+    term, CE(outs[2]) + L1(outs[1]) + lossEdge_fn(data['edges'], outs[0]), for the `edge_outputs` networks (ext_small.Ext_small,
+    Ext_smallv2).  A step takes four tensors; the edge target, dense f32 (B,1,H,W), lives in a device buffer of this object:
+    `set_edges(t)` copies the batch's target into it before the step is called.  The buffer is allocated on first use and keeps
+    its address, so a captured step reads it at every replay and sees the current target; a target of another shape or dtype
+    raises once the buffer exists.  Calling the loss before set_edges raises."""
+
+    def __init__(self, model, class_weights=None):
+        if not getattr(model, "edge_outputs", False):
+            raise _lib.SdhipError("EdgeStepLoss: the model has no edge head (edge_outputs); use StepLoss or the default loss")
+        self.model = model
+        self.class_weights = ops.seg_class_weights(class_weights, device=next(model.parameters()).device)
+        self.edges = None
+
+    def set_edges(self, t):
+        if t.dim() != 4 or t.shape[1] != 1 or t.dtype != torch.float32:
+            raise _lib.SdhipError("EdgeStepLoss.set_edges: the edge target must be f32 (B,1,H,W), got %s %s" % (t.dtype, tuple(t.shape)))
+        if self.edges is None:
+            device = next(self.model.parameters()).device
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise _lib.SdhipError("EdgeStepLoss.set_edges: the buffer cannot be allocated while a stream is capturing")
+            self.edges = torch.empty(tuple(t.shape), dtype=torch.float32, device=device)
+        elif tuple(t.shape) != tuple(self.edges.shape):
+            raise _lib.SdhipError("EdgeStepLoss.set_edges: the edge target changed shape, %s after %s: the buffer a captured step "
+                                  "reads cannot move" % (tuple(t.shape), tuple(self.edges.shape)))
+        self.edges.copy_(t, non_blocking=True)
+        return self
+
+    def __call__(self, outs, seg, disp):
+        if self.edges is None:
+            raise _lib.SdhipError("EdgeStepLoss: call set_edges(data['edges']) before the step")
+        return step.edge_loss(self.model, outs, seg, disp, self.edges, class_weights=self.class_weights)
+
+
 class TrainStep:
     def __init__(self, model, dtype=torch.bfloat16, lr=None, betas=(0.9, 0.999), eps=1e-7, use_lovasz=True,
                  use_graph=True, world_size=1, process_group=None, use_side_stream=None, loss_fn=None, metrics=None, accumulate=1,
@@ -264,7 +299,7 @@ class TrainStep:
                                      class_weights=self.class_weights)
         if self.grad_free is None and (mt or three or self.freeze_bn or (self.optimizer == "sgd" and self.weight_decay != 0)):
             self.grad_free = _unreached_parameters(self.model, loss)
-        if self.metrics is not None and (self.loss_fn is None or isinstance(self.loss_fn, StepLoss)):    # the default heads
+        if self.metrics is not None and (self.loss_fn is None or isinstance(self.loss_fn, (StepLoss, EdgeStepLoss))):    # the default heads
             self.metrics.update(outs[2].detach(), seg, outs[1].detach(), disp)
         loss.backward()
         self.ctx.join()             # weight gradients ran on the side stream
