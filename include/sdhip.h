@@ -772,6 +772,39 @@ int sdhip_warp_blend_bwd(const void* g_both, int ldgb, const void* g_warped, int
                          int gate_ch, int gate_softmax, void* g_left, int ldgl, void* g_right, int ldgr, void* g_disp, int ldgd,
                          void* g_gate, int ldgg, int B, int H, int W, int C, int dtype, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Operators of minidsnetDivideDisp / minidsnetDivideDisp2 (models/dsnet_t2_warp.py:704-972; `-net dsnet_warp_disp`,
+ * `dsnet_warp_disp_consist`).
+ *
+ * sdhip_warp_image_masked: the image the third tower pass of minidsnetDivideDisp reads (:811),
+ *   out[b,y,j,c] = [gt[b,y,j] > 0] * apply_disparity(img, -gt)[b,c,y,j]
+ * with the coordinate arithmetic and edge rules of sdhip_warp_blend_fwd (offset_sign -1): a sample at or beyond the right edge
+ * is 0, one clamped on the left copies column 0.  img: f32 or bf16 (in_dtype), read through its batch / channel / pixel
+ * strides in elements (rows follow one another pixel by pixel: NCHW, channels-last or a channel slice of either; no copy);
+ * gt: dense f32 [B][H][W]; out: NHWC of out_dtype with pixel stride ldy >= C, 1 <= C <= 4, pad lanes are not written.
+ * One launch, f32 arithmetic, forward only; the result does not depend on the image's layout. */
+int sdhip_warp_image_masked(const void* img, long img_bs, long img_cs, long img_ps, int in_dtype, const float* gt, void* out, int ldy,
+                            int out_dtype, int B, int H, int W, int C, void* stream);
+
+/* y = (1 - g) * a + g * b for NHWC maps a, b, y of C channels and a one-channel gate g (pixel strides lda, ldb, ldy >= C,
+ * ldg >= 1; pad lanes are never touched): the unwarped blend of the *_disp networks (:834).  One launch. */
+int sdhip_gate_blend_fwd(const void* a, int lda, const void* b, int ldb, const void* g, int ldg, void* y, int ldy, long npix, int C,
+                         int dtype, void* stream);
+/* ga = (1 - g) * gy, gb = g * gy, gg = sum_c gy_c * (b_c - a_c) (f32 sum); all three are written.  One launch. */
+int sdhip_gate_blend_bwd(const void* gy, int ldgy, const void* a, int lda, const void* b, int ldb, const void* g, int ldg, void* ga,
+                         int ldga, void* gb, int ldgb, void* gg, int ldgg, long npix, int C, int dtype, void* stream);
+
+/* Photometric term of the `ThreeOutPutsDispConsist` step (torch_implementation.py:314-317), MSELoss(warped, left):
+ *   loss[0] += weight * mean_{b,c,y,x} (w - l)^2,      grad = 2 * weight * (w - l) / (B*C*H*W)   (WRITTEN, dense NHWC, w's dtype)
+ * w: the warped image, NHWC of `dtype` with pixel stride ldw >= C; l: the f32 left image read through its batch / channel / pixel
+ * strides (as sdhip_warp_image_masked reads img); 1 <= C <= 4.  Every thread sums its terms in f64, every workgroup stores one f64
+ * partial in a slot of its own in the workspace (sdhip_photo_mse_workspace_bytes(npix) bytes, 8-byte aligned, no initialisation
+ * needed; < 0 for npix outside 1 .. 2^40) and a one-workgroup launch folds the slots in slot order into loss[0]: no float atomics,
+ * value and gradient repeat bit for bit and do not depend on any stride.  Two launches. */
+long sdhip_photo_mse_workspace_bytes(long npix);
+int sdhip_photo_mse(const void* w, int ldw, int dtype, const float* l, long l_bs, long l_cs, long l_ps, void* grad, double* loss,
+                    float weight, int B, int H, int W, int C, void* workspace, long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

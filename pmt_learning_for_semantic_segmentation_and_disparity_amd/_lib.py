@@ -113,6 +113,14 @@ def edge_bce_workspace_bytes(n):
     return nbytes
 
 
+def photo_mse_workspace_bytes(npix):
+    """Workspace of sdhip_photo_mse for npix pixels (include/sdhip.h)."""
+    nbytes = _lib.sdhip_photo_mse_workspace_bytes(npix)
+    if nbytes <= 0:
+        raise SdhipError("sdhip_photo_mse_workspace_bytes: unsupported pixel count %d" % npix)
+    return nbytes
+
+
 def dw_pool_parts(H, W, C, k, stride, dt):
     """Pool slots of sdhip_dw_conv_fwd for this input (include/sdhip.h)."""
     n = _lib.sdhip_dw_pool_parts(H, W, C, k, stride, dt)

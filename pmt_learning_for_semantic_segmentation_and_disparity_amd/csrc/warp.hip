@@ -249,7 +249,269 @@ inline int warp_check(const char* fn, const void* right, int ldr, const void* di
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ *_disp networks
+// (models/dsnet_t2_warp.py:704-972)  Three streaming kernels on images of C <= 4 channels and on the class scores.
+constexpr int WI_MAX_C = 4;
+
+inline dim3 stream_grid(long items) {
+  long b = (items + 255) / 256;
+  if (b > 2048) b = 2048;
+  if (b < 1) b = 1;
+  return dim3((unsigned)b);
+}
+
+// out = [gt > 0] * apply_disparity(img, -gt): one thread per pixel walks the C <= 4 channels.  The image is read through its
+// strides (planar: consecutive lanes on consecutive pixels of a plane; interleaved: on consecutive pixels of the row).
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void warp_image_masked_kernel(const TI* __restrict__ img, long bs, long cs, long ps,
+                                                                const float* __restrict__ gt, TO* __restrict__ out, int ldy, int H,
+                                                                int W, int C, long npix) {
+  for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
+    const int j = (int)(p % W);
+    const long r = p / W;
+    const float d = gt[p];
+    TO* o = out + p * ldy;
+    if (!(d > 0.f)) {                     // the mask cuts (NaN included): exact zeros
+#pragma unroll
+      for (int c = 0; c < WI_MAX_C; ++c)
+        if (c < C) Elem<TO>::st(o + c, 0.f);
+      continue;
+    }
+    const WarpCoord k = warp_coord(j, -d, W);
+    const TI* q = img + (r / H) * bs + (r % H) * (long)W * ps;
+    const TI* q0 = q + (long)k.i0 * ps;
+    const TI* q1 = q + (long)k.i1 * ps;
+#pragma unroll
+    for (int c = 0; c < WI_MAX_C; ++c)
+      if (c < C) Elem<TO>::st(o + c, k.w0 * Elem<TI>::ld(q0 + c * cs) + k.w1 * Elem<TI>::ld(q1 + c * cs));
+  }
+}
+
+// y = (1 - g) a + g b; `units` chunks of N channels per pixel, one chunk per lane
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void gate_blend_fwd_kernel(const T* __restrict__ a, int lda, const T* __restrict__ b, int ldb,
+                                                             const T* __restrict__ g, int ldg, T* __restrict__ y, int ldy, long npix,
+                                                             int C) {
+  constexpr int N = Unit<T, VEC>::N;
+  const int units = C / N;
+  const long items = npix * units;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long)gridDim.x * 256) {
+    const long pix = i / units;
+    const int c0 = (int)(i - pix * units) * N;
+    const float gv = Elem<T>::ld(g + pix * ldg), hv = 1.f - gv;
+    float av[N], bv[N];
+    Unit<T, VEC>::load(a + pix * lda + c0, av);
+    Unit<T, VEC>::load(b + pix * ldb + c0, bv);
+#pragma unroll
+    for (int e = 0; e < N; ++e) av[e] = hv * av[e] + gv * bv[e];
+    Unit<T, VEC>::store(y + pix * ldy + c0, av);
+  }
+}
+
+// a pixel's chunks are handled by G = 2^k lanes side by side (G >= min(units, 64)): lane s takes the chunks s, s + G, ...;
+// the channel sum of gg is an xor-shuffle among them
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void gate_blend_bwd_kernel(const T* __restrict__ gy, int ldgy, const T* __restrict__ a, int lda,
+                                                             const T* __restrict__ b, int ldb, const T* __restrict__ g, int ldg,
+                                                             T* __restrict__ ga, int ldga, T* __restrict__ gb, int ldgb,
+                                                             T* __restrict__ gg, int ldgg, long npix, int C, int G) {
+  constexpr int N = Unit<T, VEC>::N;
+  const int units = C / N;
+  const long slots = npix * G;
+  // the trip count is the same for every lane of a workgroup: all 64 lanes of a wave reach the shuffles
+  for (long base = (long)blockIdx.x * 256; base < slots; base += (long)gridDim.x * 256) {
+    const long i = base + threadIdx.x;
+    const long pix = i / G;
+    const int sub = (int)(i - pix * G);
+    float s = 0.f;
+    if (pix < npix) {
+      const float gv = Elem<T>::ld(g + pix * ldg), hv = 1.f - gv;
+      for (int u = sub; u < units; u += G) {
+        const int c0 = u * N;
+        float yv[N], av[N], bv[N];
+        Unit<T, VEC>::load(gy + pix * ldgy + c0, yv);
+        Unit<T, VEC>::load(a + pix * lda + c0, av);
+        Unit<T, VEC>::load(b + pix * ldb + c0, bv);
+#pragma unroll
+        for (int e = 0; e < N; ++e) {
+          s = fmaf(yv[e], bv[e] - av[e], s);
+          av[e] = hv * yv[e];
+          bv[e] = gv * yv[e];
+        }
+        Unit<T, VEC>::store(ga + pix * ldga + c0, av);
+        Unit<T, VEC>::store(gb + pix * ldgb + c0, bv);
+      }
+    }
+    for (int o = G >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (pix < npix && sub == 0) Elem<T>::st(gg + pix * ldgg, s);
+  }
+}
+
+inline int blend_group(int units) {
+  int G = 1;
+  while (G < units && G < 64) G <<= 1;
+  return G;
+}
+
+// Photometric MSE.  A workgroup handles PM_CHUNK pixels per trip, thread t the pixels base + t, base + 256 + t, ...: which
+// pixels a workgroup and a thread own depends on npix alone, never on a stride or an alignment.
+constexpr int PM_CHUNK = 1024;
+constexpr int PM_MAX_TILES = 1024;
+constexpr long PM_MAX_NPIX = 1L << 40;
+
+inline long pm_tiles(long npix) {
+  const long t = (npix + PM_CHUNK - 1) / PM_CHUNK;
+  return t > PM_MAX_TILES ? PM_MAX_TILES : t;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void photo_mse_kernel(const T* __restrict__ w, int ldw, const float* __restrict__ l, long bs, long cs,
+                                                        long ps, T* __restrict__ grad, double* __restrict__ parts, float scale, long hw,
+                                                        int C, long npix) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+  for (long base = (long)blockIdx.x * PM_CHUNK; base < npix; base += (long)gridDim.x * PM_CHUNK) {
+#pragma unroll
+    for (int k = 0; k < PM_CHUNK / 256; ++k) {
+      const long p = base + k * 256 + tid;
+      if (p >= npix) continue;
+      const long bi = p / hw;
+      const float* lp = l + bi * bs + (p - bi * hw) * ps;
+      const T* wp = w + p * ldw;
+      T* gp = grad + p * C;
+#pragma unroll
+      for (int c = 0; c < WI_MAX_C; ++c) {
+        if (c < C) {
+          const float d = Elem<T>::ld(wp + c) - lp[c * cs];
+          acc += (double)d * (double)d;
+          Elem<T>::st(gp + c, scale * d);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((tid & 63) == 0) red[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) parts[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];       // wave order: fixed
+}
+
+// One workgroup: thread i adds the slots i, i + 256, ... in that order, the 256 thread sums are added in thread order.
+__global__ __launch_bounds__(256) void photo_finish_kernel(const double* __restrict__ parts, long tiles, double scale,
+                                                           double* __restrict__ loss) {
+  __shared__ double sh[256];
+  double acc = 0.0;
+  for (long i = threadIdx.x; i < tiles; i += 256) acc += parts[i];
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+    for (int i = 0; i < 256; ++i) tot += sh[i];
+    loss[0] += scale * tot;                        // stream order makes this the only writer
+  }
+}
+
+// shared checks of an image read through (batch, channel, pixel) strides
+inline int image_check(const char* fn, const void* img, long bs, long cs, long ps, int B, int H, int W, int C) {
+  SDHIP_CHECK_ARG(img, "%s: null image pointer", fn);
+  SDHIP_CHECK_ARG(C >= 1 && C <= WI_MAX_C, "%s: C %d (1 <= C <= %d)", fn, C, WI_MAX_C);
+  SDHIP_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && (long)B * H * W <= PM_MAX_NPIX, "%s: B %d, H %d, W %d", fn, B, H, W);
+  SDHIP_CHECK_ARG(bs >= 1 && cs >= 1 && ps >= 1, "%s: image strides %ld / %ld / %ld (batch, channel, pixel) must be positive", fn, bs, cs, ps);
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int sdhip_warp_image_masked(const void* img, long img_bs, long img_cs, long img_ps, int in_dtype, const float* gt, void* out,
+                                       int ldy, int out_dtype, int B, int H, int W, int C, void* stream) {
+  if (int rc = image_check("warp_image_masked", img, img_bs, img_cs, img_ps, B, H, W, C)) return rc;
+  SDHIP_CHECK_ARG(gt && out, "warp_image_masked: null disparity / output pointer");
+  SDHIP_CHECK_ARG(W <= (1 << 24), "warp_image_masked: W %d (columns must be exact in f32: W <= 2^24)", W);
+  SDHIP_CHECK_ARG(ldy >= C, "warp_image_masked: output pixel stride %d below C = %d", ldy, C);
+  SDHIP_CHECK_DTYPE("warp_image_masked (input)", in_dtype);
+  SDHIP_CHECK_DTYPE("warp_image_masked (output)", out_dtype);
+  const long npix = (long)B * H * W;
+  sdhip_by_dtype(in_dtype, [&](auto ti) {
+    using TI = typename decltype(ti)::type;
+    sdhip_by_dtype(out_dtype, [&](auto to) {
+      using TO = typename decltype(to)::type;
+      hipLaunchKernelGGL((warp_image_masked_kernel<TI, TO>), stream_grid(npix), dim3(256), 0, (hipStream_t)stream, (const TI*)img, img_bs,
+                         img_cs, img_ps, gt, (TO*)out, ldy, H, W, C, npix);
+    });
+  });
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}
+
+extern "C" int sdhip_gate_blend_fwd(const void* a, int lda, const void* b, int ldb, const void* g, int ldg, void* y, int ldy, long npix,
+                                    int C, int dtype, void* stream) {
+  SDHIP_CHECK_ARG(a && b && g && y, "gate_blend_fwd: null pointer");
+  SDHIP_CHECK_ARG(npix >= 1 && npix <= (1L << 40) && C >= 1 && C <= (1 << 20), "gate_blend_fwd: npix %ld, C %d", npix, C);
+  SDHIP_CHECK_ARG(lda >= C && ldb >= C && ldg >= 1 && ldy >= C, "gate_blend_fwd: pixel strides %d / %d / %d / %d (a, b, g, y) for C = %d",
+                  lda, ldb, ldg, ldy, C);
+  SDHIP_CHECK_DTYPE("gate_blend_fwd", dtype);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {lda, ldb, ldy}, {a, b, y}), [&](auto V) {
+      hipLaunchKernelGGL((gate_blend_fwd_kernel<T, V()>), stream_grid(npix * (C / Unit<T, V()>::N)), dim3(256), 0, (hipStream_t)stream,
+                         (const T*)a, lda, (const T*)b, ldb, (const T*)g, ldg, (T*)y, ldy, npix, C);
+    });
+  });
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}
+
+extern "C" int sdhip_gate_blend_bwd(const void* gy, int ldgy, const void* a, int lda, const void* b, int ldb, const void* g, int ldg,
+                                    void* ga, int ldga, void* gb, int ldgb, void* gg, int ldgg, long npix, int C, int dtype,
+                                    void* stream) {
+  SDHIP_CHECK_ARG(gy && a && b && g && ga && gb && gg, "gate_blend_bwd: null pointer");
+  SDHIP_CHECK_ARG(npix >= 1 && npix <= (1L << 40) && C >= 1 && C <= (1 << 20), "gate_blend_bwd: npix %ld, C %d", npix, C);
+  SDHIP_CHECK_ARG(ldgy >= C && lda >= C && ldb >= C && ldg >= 1 && ldga >= C && ldgb >= C && ldgg >= 1,
+                  "gate_blend_bwd: pixel strides %d / %d / %d / %d / %d / %d / %d (gy, a, b, g, ga, gb, gg) for C = %d", ldgy, lda, ldb, ldg,
+                  ldga, ldgb, ldgg, C);
+  SDHIP_CHECK_DTYPE("gate_blend_bwd", dtype);
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sdhip_by_flag(sdhip_vec_ok<T>(C, {ldgy, lda, ldb, ldga, ldgb}, {gy, a, b, ga, gb}), [&](auto V) {
+      const int G = blend_group(C / Unit<T, V()>::N);
+      hipLaunchKernelGGL((gate_blend_bwd_kernel<T, V()>), stream_grid(npix * G), dim3(256), 0, (hipStream_t)stream, (const T*)gy, ldgy,
+                         (const T*)a, lda, (const T*)b, ldb, (const T*)g, ldg, (T*)ga, ldga, (T*)gb, ldgb, (T*)gg, ldgg, npix, C, G);
+    });
+  });
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}
+
+extern "C" long sdhip_photo_mse_workspace_bytes(long npix) {
+  if (npix < 1 || npix > PM_MAX_NPIX) return SDHIP_ERR_ARG;
+  return pm_tiles(npix) * (long)sizeof(double);
+}
+
+extern "C" int sdhip_photo_mse(const void* w, int ldw, int dtype, const float* l, long l_bs, long l_cs, long l_ps, void* grad,
+                               double* loss, float weight, int B, int H, int W, int C, void* workspace, long workspace_bytes,
+                               void* stream) {
+  if (int rc = image_check("photo_mse", l, l_bs, l_cs, l_ps, B, H, W, C)) return rc;
+  SDHIP_CHECK_ARG(w && grad && loss && workspace, "photo_mse: null pointer");
+  SDHIP_CHECK_ARG(ldw >= C, "photo_mse: warped pixel stride %d below C = %d", ldw, C);
+  SDHIP_CHECK_DTYPE("photo_mse", dtype);
+  const long npix = (long)B * H * W;
+  const long tiles = pm_tiles(npix);
+  SDHIP_CHECK_ARG(workspace_bytes >= tiles * (long)sizeof(double) && (((uintptr_t)workspace) & 7) == 0,
+                  "photo_mse: workspace of %ld bytes (8-byte aligned), %ld needed", workspace_bytes, tiles * (long)sizeof(double));
+  hipStream_t s = (hipStream_t)stream;
+  const double n = (double)npix * C;
+  double* parts = (double*)workspace;
+  sdhip_by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((photo_mse_kernel<T>), dim3((unsigned)tiles), dim3(256), 0, s, (const T*)w, ldw, l, l_bs, l_cs, l_ps, (T*)grad, parts,
+                       (float)(2.0 * (double)weight / n), (long)H * W, C, npix);
+  });
+  SDHIP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(photo_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)parts, tiles, (double)weight / n, loss);
+  SDHIP_LAUNCH_CHECK();
+  return SDHIP_OK;
+}
 
 extern "C" int sdhip_warp_blend_fwd(const void* seg_left, int ldl, const void* seg_right, int ldr, const void* disp, int ldd,
                                     float offset_sign, const void* gate, int ldgt, int gate_ch, int gate_softmax, void* warped,

@@ -307,6 +307,23 @@ def _space_to_depth2(x):
     return y
 
 
+class _SpaceToDepth2(torch.autograd.Function):
+    """_space_to_depth2 of an image that requires a gradient: the backward pass is the inverse strided copy into a
+    channels-last image.  (An image that requires none does not come through here.)"""
+
+    @staticmethod
+    def forward(ctx, x):
+        return _space_to_depth2(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        B, C4, H2, W2 = g.shape
+        C = C4 // 4
+        gx = ops.empty_nhwc(B, C, 2 * H2, 2 * W2, g.dtype, g.device)
+        gx.unflatten(3, (W2, 2)).unflatten(2, (H2, 2)).permute(0, 3, 5, 1, 2, 4).copy_(g.unflatten(1, (2, 2, C)))
+        return gx
+
+
 class _Stem(torch.autograd.Function):
     """conv0 (7x7 / 2) -> tap 0 (raw) and relu(norm0(.)): both outputs are used (models/densenet.py:222-225).
     A (Cout, 4C, 4, 4) weight selects the space-to-depth form (x is then the space-to-depth image)."""
@@ -360,8 +377,10 @@ class _Stem(torch.autograd.Function):
             if train:
                 call("sdhip_stats_fix", ptr(graw), Cout, ptr(c0), Cout, ptr(graw), Cout, ptr(dS), Cout, npix, Cout, groups, dt,
                      stream_ptr())
-        _, gw, _ = ops._conv_backward(spec, xv, ldx, weight, graw, Cout, None, None, False, 1, False, True)
-        return None, gw, dgamma, dbeta, None, None
+        # the image gets a gradient only where it is itself computed (warp.minidsnetDivideDisp2 feeds the tower the right image
+        # warped by the predicted disparity): the data gradient of conv0, strided for the 7x7 form; no launch otherwise
+        gx, gw, _ = ops._conv_backward(spec, xv, ldx, weight, graw, Cout, None, None, False, 1, ctx.needs_input_grad[0], True)
+        return gx, gw, dgamma, dbeta, None, None
 
 
 class _DenseLayer(nn.Module):
@@ -442,7 +461,9 @@ class DenseNet(nn.Module):
         use_s2d = (x.dtype == torch.bfloat16) if s2d is None else s2d == "1"
         if use_s2d and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0:
             # (the image may arrive zero-padded to 8 channels for the 7x7 kernels: only the weight's channels are real)
-            x, w0 = _space_to_depth2(x[:, :w0.shape[1]]), _stem_s2d_weight(w0)
+            xs = x if x.shape[1] == w0.shape[1] else x[:, :w0.shape[1]]
+            x = _SpaceToDepth2.apply(xs) if xs.requires_grad and torch.is_grad_enabled() else _space_to_depth2(xs)
+            w0 = _stem_s2d_weight(w0)
         c0, f = _Stem.apply(x, w0, self.features.norm0.weight, self.features.norm0.bias, self.features.norm0, groups)
         taps = [c0]
         f = ops.maxpool3s2(f)

@@ -114,7 +114,8 @@ class EvalStep:
                 raise _lib.SdhipError("EvalStep: with_loss needs seg and disp")
             if len(outs) < 3 and not getattr(self.model, "multiTaskLoss", 0):
                 raise _lib.SdhipError("EvalStep: with_loss needs a model with two segmentation heads and a disparity")
-            kw = dict(self.loss_kwargs, left=left) if self.loss_kwargs.get("smooth_grad") else self.loss_kwargs
+            wants_left = self.loss_kwargs.get("smooth_grad") or getattr(self.model, "photo_outputs", False)
+            kw = dict(self.loss_kwargs, left=left) if wants_left else self.loss_kwargs
             outs = outs + (step.default_loss(self.model, outs, seg, disp, **kw),)
         return outs
 

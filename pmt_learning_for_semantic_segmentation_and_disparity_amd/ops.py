@@ -1664,11 +1664,14 @@ class _WarpBlendFn(torch.autograd.Function):
         return g_left, g_right, g_disp, g_gate, None, None
 
 
-def apply_disparity(img, x_offset):
+def apply_disparity(img, x_offset, sign=1.0):
     """models/torch_dsnet.py apply_disparity(img, x_offset) with wrap_mode='edge': img (B,C,H,W) sampled at column
     j + x_offset[b,0,y,j] with linear interpolation, differentiable in both arguments.  The reference's edge rules hold:
-    a sample at or beyond the right edge is 0, one beyond the left edge copies column 0, and a clamped offset gets no gradient."""
-    return _WarpBlendFn.apply(None, img, x_offset, None, 1.0, False)
+    a sample at or beyond the right edge is 0, one beyond the left edge copies column 0, and a clamped offset gets no gradient.
+    sign=-1.0 is apply_disparity(img, -x_offset) without a pass that negates the map (the networks warp with -disp)."""
+    if sign not in (1.0, -1.0):
+        raise _lib.SdhipError("apply_disparity: sign must be 1.0 or -1.0, got %r" % (sign,))
+    return _WarpBlendFn.apply(None, img, x_offset, None, float(sign), False)
 
 
 def warp_blend(seg_left, seg_right, disp, gate, softmax_gate=False):
@@ -1678,6 +1681,155 @@ def warp_blend(seg_left, seg_right, disp, gate, softmax_gate=False):
     if gate is None:
         raise _lib.SdhipError("warp_blend needs a gate; the plain warp is apply_disparity")
     return _WarpBlendFn.apply(seg_left, seg_right, disp, gate, -1.0, softmax_gate)
+
+
+# ---------------------------------------------------------------------------- the *_disp networks (warp.minidsnetDivideDisp / Disp2)
+def _nhwc_ld(x):
+    """Pixel stride of x if its memory is NHWC with a uniform pixel stride (nhwc_view would return x itself), else None."""
+    B, C, H, W = x.shape
+    sb, sc, sh, sw = x.stride()
+    if W == 1:
+        sw = sh
+    ok = (sc == 1 or C == 1) and sw >= C and (sh == W * sw or H == 1) and (sb == H * W * sw or B == 1)
+    return sw if ok else None
+
+
+def warp_image_masked(right, gt_disp, out=None):
+    """apply_disparity(right, -gt_disp) * (gt_disp > 0): the image the third tower pass of minidsnetDivideDisp reads
+    (models/dsnet_t2_warp.py:811), one launch, no gradient (the ground truth is a constant).
+      right   — (B, 1 <= C <= 4, H, W) f32 or bf16; NCHW, channels-last or a channel slice of either, no copy is made
+      gt_disp — dense f32 (B,1,H,W)
+      out     — optional (B,C,H,W) f32 / bf16 tensor in NHWC memory (pixel stride >= C); default: right's dtype at the padded
+                pixel stride the conv nodes read.  Pad lanes are not written.
+    The edge rules of apply_disparity hold: a sample at or beyond the right edge is 0, one clamped on the left copies column 0."""
+    if right.dim() != 4 or gt_disp.dim() != 4:
+        raise _lib.SdhipError("warp_image_masked: image and disparity must be 4-D, got %s and %s" % (tuple(right.shape), tuple(gt_disp.shape)))
+    B, C, H, W = right.shape
+    if min(B, H, W) < 1 or not 1 <= C <= 4:
+        raise _lib.SdhipError("warp_image_masked: need B, H, W >= 1 and 1 <= C <= 4, got %s" % (tuple(right.shape),))
+    if tuple(gt_disp.shape) != (B, 1, H, W) or gt_disp.dtype != torch.float32 or not gt_disp.is_contiguous():
+        raise _lib.SdhipError("warp_image_masked: the disparity must be a dense f32 (B,1,H,W) = %s tensor, got %s %s"
+                              % ((B, 1, H, W), gt_disp.dtype, tuple(gt_disp.shape)))
+    dt_in = dtype_code(right)
+    if right.requires_grad or gt_disp.requires_grad:
+        raise _lib.SdhipError("warp_image_masked has no backward pass: its inputs must not require a gradient (ops.apply_disparity has one)")
+    if out is not None:
+        if tuple(out.shape) != (B, C, H, W) or out.dtype not in (torch.float32, torch.bfloat16) or _nhwc_ld(out) is None:
+            raise _lib.SdhipError("warp_image_masked: `out` must be a (B,C,H,W) = %s f32 / bf16 tensor in NHWC memory" % ((B, C, H, W),))
+    _require_gpu(right, gt_disp, out)
+    strides = _image_strides(right)
+    if strides is None:
+        right = right.contiguous()
+        strides = _image_strides(right)
+    if out is None:
+        out, ldy = alloc_nhwc(B, C, H, W, right.dtype, right.device)
+    else:
+        ldy = _nhwc_ld(out)
+    call("sdhip_warp_image_masked", ptr(right), strides[0], strides[1], strides[2], dt_in, ptr(gt_disp), ptr(out), ldy, dtype_code(out),
+         B, H, W, C, stream_ptr())
+    return out
+
+
+class _GateBlendFn(torch.autograd.Function):
+    """y = (1 - g) * a + g * b with a one-channel gate; ga, gb and gg come out of one backward launch."""
+
+    @staticmethod
+    def forward(ctx, a, b, g):
+        B, C, H, W = a.shape
+        av, lda = nhwc_view(a)
+        bv, ldb = nhwc_view(b)
+        gv, ldg = nhwc_view(g)
+        y = empty_nhwc(B, C, H, W, a.dtype, a.device)
+        call("sdhip_gate_blend_fwd", ptr(av), lda, ptr(bv), ldb, ptr(gv), ldg, ptr(y), C, B * H * W, C, dtype_code(a), stream_ptr())
+        ctx.save_for_backward(av, bv, gv)
+        ctx.cfg = (lda, ldb, ldg)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        av, bv, gv = ctx.saved_tensors
+        lda, ldb, ldg = ctx.cfg
+        B, C, H, W = av.shape
+        gyv, ldgy = nhwc_view(gy)
+        ga = empty_nhwc(B, C, H, W, av.dtype, av.device)
+        gb = empty_nhwc(B, C, H, W, av.dtype, av.device)
+        gg = empty_nhwc(B, 1, H, W, av.dtype, av.device)
+        call("sdhip_gate_blend_bwd", ptr(gyv), ldgy, ptr(av), lda, ptr(bv), ldb, ptr(gv), ldg, ptr(ga), C, ptr(gb), C, ptr(gg), 1,
+             B * H * W, C, dtype_code(av), stream_ptr())
+        return ga, gb, gg
+
+
+def gate_blend(a, b, g):
+    """(1 - g) * a + g * b for a, b (B,C,H,W) and a one-channel gate g (B,1,H,W), all of one dtype (f32 / bf16): the unwarped blend
+    `seg_branch_both` of the *_disp networks (models/dsnet_t2_warp.py:834) as one launch, and one backward launch for all three
+    gradients.  (warp_blend with a zero disparity is NOT this: the warp's right-edge rule zeroes the last column.)"""
+    if a.dim() != 4 or tuple(b.shape) != tuple(a.shape) or tuple(g.shape) != (a.shape[0], 1) + tuple(a.shape[2:]):
+        raise _lib.SdhipError("gate_blend: need a, b (B,C,H,W) and g (B,1,H,W), got %s, %s and %s"
+                              % (tuple(a.shape), tuple(b.shape), tuple(g.shape)))
+    if a.numel() < 1:
+        raise _lib.SdhipError("gate_blend of an empty tensor")
+    if not a.dtype == b.dtype == g.dtype:
+        raise _lib.SdhipError("gate_blend: a, b and g must share one dtype, got %s, %s and %s" % (a.dtype, b.dtype, g.dtype))
+    dtype_code(a)
+    _require_gpu(a, b, g)
+    return _GateBlendFn.apply(a, b, g)
+
+
+_photo_ws = {}
+
+
+class _PhotoLossFn(torch.autograd.Function):
+    """weight * MSELoss(warped, left): value and gradient in one node (two launches), as _SegLossFn."""
+
+    @staticmethod
+    def forward(ctx, warped, left, weight):
+        B, C, H, W = warped.shape
+        wv, ldw = nhwc_view(warped)
+        strides = _image_strides(left)
+        if strides is None:
+            left = left.contiguous()
+            strides = _image_strides(left)
+        npix = B * H * W
+        nbytes = _lib.photo_mse_workspace_bytes(npix)
+        key = (npix, str(warped.device))
+        ws = _photo_ws.get(key)
+        if ws is None or ws.numel() * 8 < nbytes:
+            ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=warped.device)
+            _photo_ws[key] = ws
+        loss = torch.zeros(1, dtype=torch.float64, device=warped.device)
+        g = empty_nhwc(B, C, H, W, warped.dtype, warped.device)
+        call("sdhip_photo_mse", ptr(wv), ldw, dtype_code(wv), ptr(left), strides[0], strides[1], strides[2], ptr(g), ptr(loss), weight,
+             B, H, W, C, ptr(ws), ws.numel() * 8, stream_ptr())
+        ctx.save_for_backward(g)
+        return loss.float().reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        g, = ctx.saved_tensors
+        return g * gout.to(g.dtype), None, None
+
+
+def photo_loss(warped, left, weight=1.0):
+    """weight * torch.nn.MSELoss()(warped, left): the photometric term of the reference's `ThreeOutPutsDispConsist` step
+    (torch_implementation.py:314-317), the mean over batch, channels and pixels of the squared difference.
+      warped — (B, 1 <= C <= 4, H, W) f32 or bf16 (the warped right image, a network output); the only input that gets a
+               gradient, 2 * weight * (warped - left) / (B*C*H*W) in its dtype
+      left   — f32 image of the same shape; NCHW, channels-last or a channel slice of either, no copy is made
+    Returns an f32 scalar; value and gradient are reproducible bit for bit and do not depend on the operands' strides."""
+    if warped.dim() != 4 or left.dim() != 4:
+        raise _lib.SdhipError("photo_loss: warped and left must be 4-D (B,C,H,W), got %s and %s" % (tuple(warped.shape), tuple(left.shape)))
+    if tuple(warped.shape) != tuple(left.shape):
+        raise _lib.SdhipError("photo_loss: warped %s and left %s differ in shape (MSELoss of a 3-channel warp needs the 3-channel "
+                              "image)" % (tuple(warped.shape), tuple(left.shape)))
+    if warped.numel() < 1 or not 1 <= warped.shape[1] <= 4:
+        raise _lib.SdhipError("photo_loss: need B, H, W >= 1 and 1 <= C <= 4, got %s" % (tuple(warped.shape),))
+    if left.dtype != torch.float32:
+        raise _lib.SdhipError("photo_loss: the left image must be f32, the input a step is fed (got %s)" % left.dtype)
+    dtype_code(warped)
+    _require_gpu(warped, left)
+    if warped.device != left.device:
+        raise _lib.SdhipError("photo_loss: warped and left live on different devices")
+    return _PhotoLossFn.apply(warped, left, float(weight))
 
 
 # ============================================================================ losses of the timed step

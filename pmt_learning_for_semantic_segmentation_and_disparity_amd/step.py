@@ -142,6 +142,12 @@ def model_outputs(model, dtype, left, right, seg, disp, extra=()):
     x, y = left.to(dtype), right.to(dtype)
     if getattr(model, "multiTaskLoss", 0) and seg is not None and disp is not None:
         return model(x, y, None, disp, seg.argmax(1))
+    if getattr(model, "disp_input", False):
+        # `ThreeOutPutsDisp` (warp.minidsnetDivideDisp; torch_implementation.py:133-134): the network reads the f32 disparity target
+        if disp is None:
+            raise _lib.SdhipError("model_outputs: a disp_input model (%s) is called as model(left, right, disp) and needs the "
+                                  "disparity target, in training and in evaluation" % type(model).__name__)
+        return model(x, y, disp.float(), *extra)
     return model(x, y, *extra)
 
 
@@ -160,13 +166,33 @@ def edge_loss(model, outs, seg, disp, edges, *, smooth_grad=0.0, use_lovasz=Fals
                               class_weights=class_weights)
 
 
+def photo_step_loss(model, outs, seg, left, *, use_lovasz=True, loss=None, class_weights=None, ignore_void=False, **other):
+    """The loss of the reference step for a `ThreeOutPutsDispConsist` network (`photo_outputs`: warp.minidsnetDivideDisp2;
+    torch_implementation.py:157-158,279-317): CE(outs[0]) + [-loss list](outs[2]) + CE(outs[4]) + MSE(outs[5], left).  The
+    disparity has NO target term: upstream multiplies its L1 by 0 (dropped here) and trains the head through the warped image."""
+    if left is None:
+        raise _lib.SdhipError("default_loss: a photo_outputs model (%s) compares its warped right image with the left image: "
+                              "pass left=..." % type(model).__name__)
+    if left.dim() != 4 or left.shape[1] != 3:
+        raise _lib.SdhipError("default_loss: the photometric term needs the 3-channel left image, got %s (upstream's MSELoss "
+                              "fails on a 4-channel include_edges input too)" % (tuple(left.shape),))
+    if other.get("seg3") is not None:
+        raise _lib.SdhipError("default_loss: seg3 is outs[4] of a photo_outputs model, not an argument")
+    plan = loss if loss is not None else (("cross_entropy", "lovasz_loss") if use_lovasz else ("cross_entropy",))
+    total = ops.seg_loss(outs[0], seg, ("cross_entropy",), class_weights)
+    total = total + ops.seg_loss(outs[2], seg, plan, class_weights, ignore_void)
+    total = total + ops.seg_loss(outs[4], seg, ("cross_entropy",), class_weights)
+    return total + ops.photo_loss(outs[5], left)
+
+
 def default_loss(model, outs, seg, disp, *, left=None, smooth_grad=0.0, **train_loss_kwargs):
     """The loss of the reference step on the outputs of model_outputs.  Multitask: the sum of the three maps' means
     (torch_implementation.py:173-176,285-325), from the loss kernels' own sums.
     smooth_grad (non-zero): the weight of the `smooth_grad` disparity regulariser of lossDisp_fn (losses/multiLosses.py:143-146),
     ops.disp_smooth_loss(left, outs[1], seg, smooth_grad), added to the rest; `left` is the f32 left image of the batch.
     An `edge_outputs` model (ext_small.Ext_small / Ext_smallv2) gets edge_loss above without the edge term, CE + L1: the
-    edge target is no input of a step (train.EdgeStepLoss carries it)."""
+    edge target is no input of a step (train.EdgeStepLoss carries it).
+    A `photo_outputs` model (warp.minidsnetDivideDisp2) gets photo_step_loss above: it needs `left`, 3 channels."""
     if smooth_grad:
         if getattr(model, "multiTaskLoss", 0):
             raise _lib.SdhipError("default_loss: the multitask loss is the three maps' means; smooth_grad has no place in it")
@@ -176,6 +202,9 @@ def default_loss(model, outs, seg, disp, *, left=None, smooth_grad=0.0, **train_
         return multitask.step_loss(outs[4], outs[5], outs[6])
     if getattr(model, "edge_outputs", False):
         return edge_loss(model, outs, seg, disp, None, smooth_grad=smooth_grad, **train_loss_kwargs)
+    if getattr(model, "photo_outputs", False):
+        loss = photo_step_loss(model, outs, seg, left, **train_loss_kwargs)
+        return loss + ops.disp_smooth_loss(left, outs[1], seg, smooth_grad) if smooth_grad else loss
     # the `ThreeOutPuts` networks (warp.minidsnetDivide*) add the cross-entropy of their third segmentation map, outs[4]
     # (torch_implementation.py:157-158,298); Lovasz stays on outs[2], which the metrics score as well
     seg3 = outs[4] if getattr(model, "three_outputs", False) else None

@@ -295,8 +295,10 @@ class TrainStep:
         elif self.loss_fn is not None:
             loss = self.loss_fn(outs, seg, disp)
         else:
+            # a photo_outputs model (warp.minidsnetDivideDisp2) compares its warped right image with the f32 left image
+            images = dict(left=left) if getattr(self.model, "photo_outputs", False) else {}
             loss = step.default_loss(self.model, outs, seg, disp, use_lovasz=self.use_lovasz, loss=self.seg_loss,
-                                     class_weights=self.class_weights)
+                                     class_weights=self.class_weights, **images)
         if self.grad_free is None and (mt or three or self.freeze_bn or (self.optimizer == "sgd" and self.weight_decay != 0)):
             self.grad_free = _unreached_parameters(self.model, loss)
         if self.metrics is not None and (self.loss_fn is None or isinstance(self.loss_fn, (StepLoss, EdgeStepLoss))):    # the default heads

@@ -3,6 +3,10 @@ util/utilLoadNetwork.py, output type `ThreeOutPuts`): the segmentation decoder r
 scores are warped into the left view with the predicted disparity (ops.warp_blend, models/torch_dsnet.py apply_disparity)
 and blended with the left scores by a learnt gate, so the disparity head receives gradient from the segmentation loss.
 
+The `*_disp` variants (`-net dsnet_warp_disp` / `dsnet_warp_disp_consist`, output types `ThreeOutPutsDisp` /
+`ThreeOutPutsDispConsist`; _WarpDispNet below) run the tower a third time on the right image moved into the left view and
+blend the two segmentation maps without a warp.
+
 Same class names, constructor signatures, output tuples and state_dict keys as the reference.  The file's pyramid is NOT
 nn.piramidNet2: it has a fourth level on the 1/16 tap and returns nine tensors (piramidNet2Warp below).
 """
@@ -132,6 +136,13 @@ class _WarpNet(nn.Module):
         x, x1_1 = ops.split_batch(x, B)[0], ops.split_batch(x1_1, B)[0]
         seg_l, seg_r = ops.split_batch(seg, B)
         pa, pb = ops.split_batch(t[7], B)
+        y, disp = self._disparity(x, xl2, pa, pb, size)
+        s2_d = ops.concat([x1_1, ops.interpolate(y, size=x1_1.shape[2:])])
+        return seg_l, seg_r, disp, s2_d
+
+    def _disparity(self, x, xl2, pa, pb, size):
+        """The disparity branch: correlation of the 1/8 pyramids, Conv2DownUp3/4, the x8 head.  Returns (y, disp): the
+        64-channel 1/8 map the gate heads read as well, and the full-resolution disparity."""
         y = self.correlation_sampler(pa, pb)
         if self.patch_type == '1dcorr':
             y = self.corrConv2d[0].run(torch.squeeze(y, 1), act=1)
@@ -144,9 +155,7 @@ class _WarpNet(nn.Module):
         d0 = ops.upcat_conv1x1(y, xl2, self.conv1d_2[0].c2d.weight, act=1)
         if d0 is None:
             d0 = self.conv1d_2[0].run(ops.concat([ops.interpolate(y, scale_factor=8), xl2]), act=1)
-        disp = ops.interpolate(self.dispoutConv(self.Conv2DownUp5(d0)), size=size, mode='bilinear')
-        s2_d = ops.concat([x1_1, ops.interpolate(y, size=x1_1.shape[2:])])
-        return seg_l, seg_r, disp, s2_d
+        return y, ops.interpolate(self.dispoutConv(self.Conv2DownUp5(d0)), size=size, mode='bilinear')
 
 
 class minidsnetDivide(_WarpNet):
@@ -187,3 +196,67 @@ class minidsnetDivideSoftmax(_WarpNet):
         at_d = ops.interpolate(at_d, size=seg_l.shape[2:], mode='nearest')
         both, warped, prob = ops.warp_blend(seg_l, seg_r, disp, at_d, softmax_gate=True)
         return seg_l, disp, both, disp, warped, prob
+
+
+class _WarpDispNet(_WarpNet):
+    """What minidsnetDivideDisp and minidsnetDivideDisp2 share (models/dsnet_t2_warp.py:704-972: one constructor, one forward up
+    to the image of the third tower pass).  minidsnetDivide's members in its order, then Conv2DownUp7 over 128 channels (both
+    decoder maps and the disparity features) and the sigmoid gate.  The tower runs THREE times in sequence - left, right (only
+    its 1/8 pyramid is used), the right image moved into the left view - and SmallsegNet twice, on the first and the third
+    pass: the third depends on the disparity, so nothing is batched and every BatchNorm of the tower moves its running
+    statistics three times per training step, in upstream's order.  The two segmentation maps are blended WITHOUT a warp
+    (upstream's warp line is commented out): ops.gate_blend.  DenseNet only."""
+
+    def __init__(self, CFG, labels=8, pretrained=False, patch_type='', include_edges=False, backbone='densenet'):
+        super().__init__()
+        if backbone != 'densenet':
+            raise NotImplementedError("backbone %r: %s is on the native path with 'densenet' only" % (backbone, type(self).__name__))
+        self._build(CFG, labels, pretrained, patch_type, include_edges, 'densenet', 'densenet', 576, 256)
+        self.Conv2DownUp7 = Conv2DownUp(128, 64, 3)
+        self.conv1d_at_d = nn.Sequential(conv2dSame(64, 1, 1, padding='same'), nn.Sigmoid())
+
+    def _run(self, input_a, input_b, third_image):
+        """third_image(right, disp_out) -> the (B,3,H,W) input of the third tower pass.
+        Returns (both, disp_out, seg_left, seg_right, gate, third image)."""
+        B = input_a.shape[0]
+        size = input_a.shape[2:]
+        both, img_a = _stereo_buffer(input_a, input_b, self.include_edges)
+        if self.include_edges:      # conv2d_ba0 sees the right image's edge map too (the tower's weights have no 4th column)
+            both[B:, 3] = input_b[:, 3]
+        ta = self.resnet_features(both[:B])
+        tb = self.resnet_features(both[B:])
+        xl2 = self.conv2d_ba1[0].fused(img_a, act=1)
+        self.conv2d_ba0[0].fused(both, act=1, groups=2)       # computed on both images and unused, exactly as upstream
+        x, x1_1, seg_l = self.segNet(ta[8], size, ta[6])
+        y, disp = self._disparity(x, xl2, ta[7], tb[7], size)
+        third = third_image(both[B:, :3], disp)
+        tc = self.resnet_features(third)
+        _, x2_1, seg_r = self.segNet(tc[8], size, tc[6])
+        s2_d = ops.concat([x1_1, x2_1, ops.interpolate(y, size=x1_1.shape[2:])])
+        at_d = self.conv1d_at_d[0].run(self.Conv2DownUp7(s2_d), act=2)
+        at_d = ops.interpolate(at_d, size=seg_l.shape[2:], mode='nearest')
+        return ops.gate_blend(seg_l, seg_r, at_d), disp, seg_l, seg_r, at_d, third
+
+
+class minidsnetDivideDisp(_WarpDispNet):
+    """models/dsnet_t2_warp.py:704-836 (`-net dsnet_warp_disp`, output type `ThreeOutPutsDisp`).  The third tower pass reads the
+    right image warped by the GROUND-TRUTH disparity and cut where that is not positive (ops.warp_image_masked): a constant,
+    no gradient flows through it.  forward(left, right, disp) -> (both, disp_out, seg_left, disp_out, seg_right, gate)."""
+    disp_input = True          # step.model_outputs: called as model(left, right, disp) with the f32 disparity target
+
+    def forward(self, input_a, input_b, disp):
+        both, disp_out, seg_l, seg_r, at_d, _ = self._run(input_a, input_b, lambda right, _d: ops.warp_image_masked(right, disp))
+        return both, disp_out, seg_l, disp_out, seg_r, at_d
+
+
+class minidsnetDivideDisp2(_WarpDispNet):
+    """models/dsnet_t2_warp.py:839-972 (`-net dsnet_warp_disp_consist`, output type `ThreeOutPutsDispConsist`).  The third tower
+    pass reads warped_right = apply_disparity(right, -disp_out), the right image warped by the PREDICTED disparity: the
+    gradient of the segmentation losses flows back through the whole tower (densenet._Stem's data gradient) into the
+    disparity head, and the step compares warped_right with the left image (ops.photo_loss) instead of disp_out with a
+    disparity target.  forward(left, right) -> (both, disp_out, seg_left, disp_out, seg_right, warped_right)."""
+    photo_outputs = True       # step.default_loss: three segmentation terms + MSE(outs[5], left), no L1
+
+    def forward(self, input_a, input_b):
+        both, disp_out, seg_l, seg_r, _, warped = self._run(input_a, input_b, lambda right, d: ops.apply_disparity(right, d, sign=-1.0))
+        return both, disp_out, seg_l, disp_out, seg_r, warped
