@@ -14,11 +14,11 @@
 //                          halo of 1.  The Gaussian runs separably in LDS (rows, then columns), the two weight planes follow, and
 //                          every thread then writes the gradient of four pixels and adds their value terms in f64.  The
 //                          workgroup STORES its f64 partial into a slot of its own (no float atomics);
-//   2. disp_smooth_finish_kernel  one workgroup folds the slots in slot order and does loss += s * sum.
+//   2. slot_fold_kernel    (loss_common.h) one workgroup folds the slots in slot order and does loss += s * sum.
 // Value and gradient are bitwise reproducible.  Everything outside the image reads as: luma 0, no label, disparity 0.
 #include <math.h>
 
-#include "sdhip_common.h"
+#include "loss_common.h"
 
 namespace {
 
@@ -143,27 +143,13 @@ __global__ __launch_bounds__(256) void disp_smooth_kernel(const float* __restric
       acc += (double)(wv * fabsf(dv) + wh * fabsf(dh));
     }
   }
+  // block_tail (sdhip_common.h) written out: as a call, the compiler schedules the stencil section above differently
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
   if ((tid & 63) == 0) red[tid >> 6] = acc;
   __syncthreads();
   if (tid == 0)                                   // wave order: fixed
     slots[((long)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// One workgroup: thread i adds the slots i, i + 256, ... in that order, the 256 thread sums are added in thread order.
-__global__ __launch_bounds__(256) void disp_smooth_finish_kernel(const double* __restrict__ slots, long n, double scale,
-                                                                 double* __restrict__ loss) {
-  __shared__ double sh[256];
-  double acc = 0.0;
-  for (long i = threadIdx.x; i < n; i += 256) acc += slots[i];
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tot = 0.0;
-    for (int i = 0; i < 256; ++i) tot += sh[i];
-    loss[0] += scale * tot;                        // stream order makes this the only writer
-  }
 }
 
 // matlab_style_gauss2D((7, 7), 2) = outer(g, g) with g = e / sum(e), e_k = exp(-k^2 / 8): float64, then rounded to f32
@@ -189,12 +175,10 @@ extern "C" int sdhip_disp_smooth(const float* left, long left_bs, long left_cs, 
   SDHIP_CHECK_ARG(ds_shape_ok(B, H, W), "disp_smooth: B %d, H %d, W %d (all positive, B <= 65535, H <= %d)", B, H, W, 65535 * DS_TH);
   SDHIP_CHECK_ARG(C >= 1 && C <= DS_MAX_C, "disp_smooth: C %d (1 <= C <= %d)", C, DS_MAX_C);
   SDHIP_CHECK_ARG(ldt >= C, "disp_smooth: target pixel stride %d below C = %d", ldt, C);
-  SDHIP_CHECK_ARG(left_ps >= 1 && left_cs >= 1 && left_bs >= 1, "disp_smooth: image strides %ld / %ld / %d (batch, channel, pixel) must be positive",
-                  left_bs, left_cs, left_ps);
+  SDHIP_CHECK_IMAGE_STRIDES("disp_smooth", left_bs, left_cs, left_ps);
   SDHIP_CHECK_DTYPE("disp_smooth", dtype);
   const long need = ds_slots(B, H, W) * (long)sizeof(double);
-  SDHIP_CHECK_ARG(workspace_bytes >= need && (((uintptr_t)workspace) & 7) == 0,
-                  "disp_smooth: workspace of %ld bytes (8-byte aligned), %ld needed", workspace_bytes, need);
+  SDHIP_CHECK_WORKSPACE("disp_smooth", workspace, workspace_bytes, need);
   hipStream_t s = (hipStream_t)stream;
   const double scale = (double)weight * 0.7 / (128.0 * (double)B * (double)H * (double)W);
   const dim3 grid((unsigned)ds_tiles_x(W), (unsigned)ds_tiles_y(H), (unsigned)B);
@@ -213,7 +197,5 @@ extern "C" int sdhip_disp_smooth(const float* left, long left_bs, long left_cs, 
     else launch(std::integral_constant<int, 1>{});
   });
   SDHIP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(disp_smooth_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)workspace, ds_slots(B, H, W), scale, loss);
-  SDHIP_LAUNCH_CHECK();
-  return SDHIP_OK;
+  return sdhip_slot_fold(__func__, (const double*)workspace, ds_slots(B, H, W), scale, loss, s);
 }

@@ -14,7 +14,7 @@
 //      edge_bce_kernel     every workgroup folds the slots (integers: the order does not matter), forms both weights in f32 as the
 //                          reference does, then computes max(z,0) - z t + log1p(exp(-|z|)) and the gradient w (sigmoid(z) - t) / n
 //                          of its elements and stores its f64 partial of sum(w * bce) in a slot of its own;
-//      edge_finish_kernel  one workgroup folds the partials in slot order: loss += sum / n.
+//      slot_fold_kernel    (loss_common.h) one workgroup folds the partials in slot order: loss += sum / n.
 //    No float atomics: value and gradient are bitwise reproducible.  Which elements a workgroup and a thread own depends on n
 //    alone, never on alignment or strides, so the bits do not depend on how the logits are laid out either.
 //
@@ -23,7 +23,7 @@
 //    pass forms ga = gy_a g, gb = gy_b (1 - g) and gg = sum_c (gy_a a - gy_b b), the sum by shuffles among the pixel's lanes.
 #include <math.h>
 
-#include "sdhip_common.h"
+#include "loss_common.h"
 
 namespace {
 
@@ -93,13 +93,6 @@ __global__ __launch_bounds__(256) void grad_mag_kernel(const TI* __restrict__ im
         if (c < C) Elem<TO>::st(o + c, v[c]);
     }
   }
-}
-
-inline dim3 edge_grid(long items) {
-  long b = (items + 255) / 256;
-  if (b > 2048) b = 2048;
-  if (b < 1) b = 1;
-  return dim3((unsigned)b);
 }
 
 // ------------------------------------------------------------------------------------------------ balanced BCE
@@ -198,25 +191,8 @@ __global__ __launch_bounds__(256) void edge_bce_kernel(const T* __restrict__ z, 
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = acc;
-  __syncthreads();
-  if (tid == 0) parts[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];       // wave order: fixed
-}
-
-// One workgroup: thread i adds the slots i, i + 256, ... in that order, the 256 thread sums are added in thread order.
-__global__ __launch_bounds__(256) void edge_finish_kernel(const double* __restrict__ parts, long tiles, double scale, double* __restrict__ loss) {
-  __shared__ double sh[256];
-  double acc = 0.0;
-  for (long i = threadIdx.x; i < tiles; i += 256) acc += parts[i];
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tot = 0.0;
-    for (int i = 0; i < 256; ++i) tot += sh[i];
-    loss[0] += scale * tot;                        // stream order makes this the only writer
-  }
+  const double tot = block_tail(acc, red);
+  if (tid == 0) parts[blockIdx.x] = tot;
 }
 
 // ------------------------------------------------------------------------------------------------ gated pair
@@ -281,12 +257,6 @@ __global__ __launch_bounds__(256) void gate_pair_bwd_kernel(const T* __restrict_
   }
 }
 
-inline int gate_group(int units) {
-  int G = 1;
-  while (G < units && G < 64) G <<= 1;
-  return G;
-}
-
 }  // namespace
 
 extern "C" int sdhip_grad_mag(const void* img, long img_bs, long img_cs, long img_ps, int in_dtype, void* out, int ldy, int out_dtype,
@@ -294,8 +264,7 @@ extern "C" int sdhip_grad_mag(const void* img, long img_bs, long img_cs, long im
   SDHIP_CHECK_ARG(img && out, "grad_mag: null pointer");
   SDHIP_CHECK_ARG(C >= 1 && C <= GM_MAX_C, "grad_mag: C %d (1 <= C <= %d)", C, GM_MAX_C);
   SDHIP_CHECK_ARG(B >= 1 && H >= 2 && W >= 2 && (long)B * H * W <= (1L << 40), "grad_mag: B %d, H %d, W %d (B >= 1, H and W >= 2)", B, H, W);
-  SDHIP_CHECK_ARG(img_bs >= 1 && img_cs >= 1 && img_ps >= 1, "grad_mag: image strides %ld / %ld / %ld (batch, channel, pixel) must be positive",
-                  img_bs, img_cs, img_ps);
+  SDHIP_CHECK_IMAGE_STRIDES("grad_mag", img_bs, img_cs, img_ps);
   SDHIP_CHECK_ARG(ldy >= C, "grad_mag: output pixel stride %d below C = %d", ldy, C);
   SDHIP_CHECK_DTYPE("grad_mag (input)", in_dtype);
   SDHIP_CHECK_DTYPE("grad_mag (output)", out_dtype);
@@ -310,7 +279,7 @@ extern "C" int sdhip_grad_mag(const void* img, long img_bs, long img_cs, long im
       using TO = typename decltype(to)::type;
       sdhip_by_flag(vin, [&](auto VI) {
         sdhip_by_flag(vout, [&](auto VO) {
-          hipLaunchKernelGGL((grad_mag_kernel<TI, TO, VI(), VO()>), edge_grid(npix), dim3(256), 0, (hipStream_t)stream, (const TI*)img, img_bs,
+          hipLaunchKernelGGL((grad_mag_kernel<TI, TO, VI(), VO()>), stream_grid(npix), dim3(256), 0, (hipStream_t)stream, (const TI*)img, img_bs,
                              img_cs, img_ps, (TO*)out, ldy, H, W, C, npix);
         });
       });
@@ -332,8 +301,7 @@ extern "C" int sdhip_edge_bce(const void* logits, long ldz, int dtype, const flo
   SDHIP_CHECK_ARG(ldz >= 1, "edge_bce: logit stride %ld must be positive", ldz);
   SDHIP_CHECK_DTYPE("edge_bce", dtype);
   const long need = eb_bytes(n);
-  SDHIP_CHECK_ARG(workspace_bytes >= need && (((uintptr_t)workspace) & 7) == 0,
-                  "edge_bce: workspace of %ld bytes (8-byte aligned), %ld needed", workspace_bytes, need);
+  SDHIP_CHECK_WORKSPACE("edge_bce", workspace, workspace_bytes, need);
   hipStream_t s = (hipStream_t)stream;
   const long tiles = eb_tiles(n);
   unsigned long long* counts = (unsigned long long*)workspace;
@@ -350,9 +318,7 @@ extern "C" int sdhip_edge_bce(const void* logits, long ldz, int dtype, const flo
                        (const unsigned long long*)counts, parts, n, (float)(1.0 / (double)n));
   });
   SDHIP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(edge_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)parts, tiles, 1.0 / (double)n, loss);
-  SDHIP_LAUNCH_CHECK();
-  return SDHIP_OK;
+  return sdhip_slot_fold(__func__, parts, tiles, 1.0 / (double)n, loss, s);
 }
 
 extern "C" int sdhip_gate_pair_fwd(const void* a, int lda, const void* b, int ldb, const void* g, int ldg, void* y, int ldy, long npix,
@@ -365,7 +331,7 @@ extern "C" int sdhip_gate_pair_fwd(const void* a, int lda, const void* b, int ld
   sdhip_by_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     sdhip_by_flag(sdhip_vec_ok<T>(C, {lda, ldb, ldy}, {a, b, y}), [&](auto V) {
-      hipLaunchKernelGGL((gate_pair_fwd_kernel<T, V()>), edge_grid(npix * (C / Unit<T, V()>::N)), dim3(256), 0, (hipStream_t)stream, (const T*)a,
+      hipLaunchKernelGGL((gate_pair_fwd_kernel<T, V()>), stream_grid(npix * (C / Unit<T, V()>::N)), dim3(256), 0, (hipStream_t)stream, (const T*)a,
                          lda, (const T*)b, ldb, (const T*)g, ldg, (T*)y, ldy, npix, C);
     });
   });
@@ -384,8 +350,8 @@ extern "C" int sdhip_gate_pair_bwd(const void* gy, int ldgy, const void* a, int 
   sdhip_by_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     sdhip_by_flag(sdhip_vec_ok<T>(C, {ldgy, lda, ldb, ldga, ldgb}, {gy, a, b, ga, gb}), [&](auto V) {
-      const int G = gate_group(C / Unit<T, V()>::N);
-      hipLaunchKernelGGL((gate_pair_bwd_kernel<T, V()>), edge_grid(npix * G), dim3(256), 0, (hipStream_t)stream, (const T*)gy, ldgy, (const T*)a,
+      const int G = lane_group(C / Unit<T, V()>::N);
+      hipLaunchKernelGGL((gate_pair_bwd_kernel<T, V()>), stream_grid(npix * G), dim3(256), 0, (hipStream_t)stream, (const T*)gy, ldgy, (const T*)a,
                          lda, (const T*)b, ldb, (const T*)g, ldg, (T*)ga, ldga, (T*)gb, ldgb, (T*)gg, ldgg, npix, C, G);
     });
   });

@@ -18,17 +18,6 @@ namespace {
 constexpr int kMaxL = 32;           // up to 32 classes: the L*L histogram lives in LDS
 constexpr int kNC = SDHIP_METRIC_COUNTS, kNS = SDHIP_METRIC_SUMS;
 
-__device__ __forceinline__ long wave_sum_l(long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // One workgroup walks 256-pixel tiles.  With more than a few channels per pixel a lane-per-pixel read touches one cache
 // line per lane and instruction (the texture-address unit, not HBM, then sets the pace: 1.5 TB/s measured at L=19), so
 // STAGE copies the tile's logits and targets lane-linearly (fully coalesced) into LDS first and the per-pixel scan
@@ -134,9 +123,9 @@ __global__ __launch_bounds__(256) void step_metrics_kernel(
   const int wave = threadIdx.x >> 6;
   if (small && lane < L * L && hreg) atomicAdd(&hist[lane], hreg);
 #pragma unroll
-  for (int i = 0; i < kNC; ++i) { const long v = wave_sum_l(c[i]); if (lane == 0) wc[wave][i] = v; }
+  for (int i = 0; i < kNC; ++i) { const long v = wave_sum(c[i]); if (lane == 0) wc[wave][i] = v; }
 #pragma unroll
-  for (int i = 0; i < kNS; ++i) { const double v = wave_sum_d(s[i]); if (lane == 0) wsum[wave][i] = v; }
+  for (int i = 0; i < kNS; ++i) { const double v = wave_sum(s[i]); if (lane == 0) wsum[wave][i] = v; }
   __syncthreads();   // also orders the histogram updates above before the flush below
   // memory-side atomics on one cache line serialise: the workgroups spread over `nrep` replicas (one 256-byte line
   // each for the f64 sums, rep_stride counters each), summed by the caller

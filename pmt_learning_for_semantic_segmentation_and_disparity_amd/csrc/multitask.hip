@@ -15,15 +15,6 @@
 
 namespace {
 
-__device__ __forceinline__ float mt_block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = 0.f;
-  if (threadIdx.x == 0) for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
-  return r;
-}
-
 // a label counts when it names one of the C classes and is not ignore_index; anything else (ignore_index itself, or an
 // out-of-range label, which the reference rejects with an error) contributes CE 0
 __device__ __forceinline__ bool mt_counted(long l, int C, int ignore) { return l != (long)ignore && l >= 0 && l < (long)C; }
@@ -68,7 +59,7 @@ __global__ __launch_bounds__(256) void mt_seg_fwd_kernel(const T* __restrict__ y
     lse_out[p] = lse;
     part += m;
   }
-  const float tot = mt_block_sum(part, sh);
+  const float tot = block_sum(part, sh);
   if (threadIdx.x == 0) atomicAdd(sum, (double)tot * (double)wsum);
 }
 
@@ -102,7 +93,7 @@ __global__ __launch_bounds__(256) void mt_seg_fwd_rows_kernel(const T* __restric
     }
     __syncthreads();
   }
-  const float tot = mt_block_sum(part, sh);
+  const float tot = block_sum(part, sh);
   if (tid == 0) atomicAdd(sum, (double)tot * (double)wsum);
 }
 
@@ -129,7 +120,7 @@ __global__ __launch_bounds__(256) void mt_seg_bwd_kernel(const T* __restrict__ y
     if (gy) mt_row_grad(row, gy + p * ldg, C, l, counted, lse, gp * e);
   }
   if (dlv) {
-    const float tot = mt_block_sum(part, sh);
+    const float tot = block_sum(part, sh);
     if (threadIdx.x == 0) atomicAdd(dlv, tot);
   }
 }
@@ -179,7 +170,7 @@ __global__ __launch_bounds__(256) void mt_seg_bwd_rows_kernel(const T* __restric
     __syncthreads();
   }
   if (dlv) {
-    const float tot = mt_block_sum(part, sh);
+    const float tot = block_sum(part, sh);
     if (tid == 0) atomicAdd(dlv, tot);
   }
 }
@@ -197,7 +188,7 @@ __global__ __launch_bounds__(256) void mt_l1_fwd_kernel(const T* __restrict__ a,
     map[i] = m;
     part += m;
   }
-  const float tot = mt_block_sum(part, sh);
+  const float tot = block_sum(part, sh);
   if (threadIdx.x == 0) atomicAdd(sum, (double)tot * (double)wsum);
 }
 
@@ -218,7 +209,7 @@ __global__ __launch_bounds__(256) void mt_l1_bwd_kernel(const T* __restrict__ a,
     if (ga) Elem<T>::st(ga + i * ldg, d > 0.f ? gp * e : (d < 0.f ? -gp * e : 0.f));
   }
   if (dlv) {
-    const float tot = mt_block_sum(part, sh);
+    const float tot = block_sum(part, sh);
     if (threadIdx.x == 0) atomicAdd(dlv, tot);
   }
 }

@@ -84,16 +84,6 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
   }
 }
 
-// block reduce of one float, result valid in thread 0
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = 0.f;
-  if (threadIdx.x == 0) for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
-  return r;
-}
-
 // loss += weight/npix * sum_p sum_c -t[p,c] * log_softmax(y[p,:])_c ;  gy[p,c] = weight/npix * (softmax_c * sum_c t - t_c)
 template <typename T>
 __global__ __launch_bounds__(256) void ce_kernel(const T* __restrict__ y, int ldy, const float* __restrict__ t, int ldt,

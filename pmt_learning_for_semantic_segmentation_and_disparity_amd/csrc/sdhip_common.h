@@ -95,7 +95,8 @@ template <> struct Chunk<bf16_t> {
 };
 
 // ---- wave64 reductions (DPP-free, shuffle based) --------------------------
-__device__ __forceinline__ float wave_sum(float v) {
+// one loop for every summand type __shfl_xor takes (in use: float, and metrics.hip's long and double)
+template <typename T> __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
@@ -104,6 +105,28 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// ---- reductions of a workgroup (one wave per 64 threads; `sh` / `red` hold one value per wave) ------------------------
+// block reduce of one float, result valid in thread 0
+__device__ __forceinline__ float block_sum(float v, float* sh) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float r = 0.f;
+  if (threadIdx.x == 0) for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
+  return r;
+}
+// Ordered tail of a 256-thread workgroup, the first half of the "slot fold" (loss_common.h has the second): every wave sums
+// its 64 lanes, the four wave sums are added in wave order, always in this association, so the f64 partial a workgroup
+// stores in its slot has the same bits on every run.  For thread 0 (any thread may read it); one barrier.
+template <typename T> __device__ __forceinline__ T block_tail(T v, T* red) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);     // wave_sum written out: nested, the callers are scheduled differently
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 // one "unit" of a row-wise elementwise kernel: a 16-byte chunk (VEC) or a single element

@@ -21,7 +21,7 @@
 // pixel stride or an unaligned row is stored element by element.  The order of the LDS adds is not fixed, so g_right is
 // reproducible to f32
 // rounding, not bit for bit.
-#include "sdhip_common.h"
+#include "loss_common.h"
 
 namespace {
 
@@ -253,13 +253,6 @@ inline int warp_check(const char* fn, const void* right, int ldr, const void* di
 // (models/dsnet_t2_warp.py:704-972)  Three streaming kernels on images of C <= 4 channels and on the class scores.
 constexpr int WI_MAX_C = 4;
 
-inline dim3 stream_grid(long items) {
-  long b = (items + 255) / 256;
-  if (b > 2048) b = 2048;
-  if (b < 1) b = 1;
-  return dim3((unsigned)b);
-}
-
 // out = [gt > 0] * apply_disparity(img, -gt): one thread per pixel walks the C <= 4 channels.  The image is read through its
 // strides (planar: consecutive lanes on consecutive pixels of a plane; interleaved: on consecutive pixels of the row).
 template <typename TI, typename TO>
@@ -347,12 +340,6 @@ __global__ __launch_bounds__(256) void gate_blend_bwd_kernel(const T* __restrict
   }
 }
 
-inline int blend_group(int units) {
-  int G = 1;
-  while (G < units && G < 64) G <<= 1;
-  return G;
-}
-
 // Photometric MSE.  A workgroup handles PM_CHUNK pixels per trip, thread t the pixels base + t, base + 256 + t, ...: which
 // pixels a workgroup and a thread own depends on npix alone, never on a stride or an alignment.
 constexpr int PM_CHUNK = 1024;
@@ -390,26 +377,8 @@ __global__ __launch_bounds__(256) void photo_mse_kernel(const T* __restrict__ w,
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = acc;
-  __syncthreads();
-  if (tid == 0) parts[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];       // wave order: fixed
-}
-
-// One workgroup: thread i adds the slots i, i + 256, ... in that order, the 256 thread sums are added in thread order.
-__global__ __launch_bounds__(256) void photo_finish_kernel(const double* __restrict__ parts, long tiles, double scale,
-                                                           double* __restrict__ loss) {
-  __shared__ double sh[256];
-  double acc = 0.0;
-  for (long i = threadIdx.x; i < tiles; i += 256) acc += parts[i];
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tot = 0.0;
-    for (int i = 0; i < 256; ++i) tot += sh[i];
-    loss[0] += scale * tot;                        // stream order makes this the only writer
-  }
+  const double tot = block_tail(acc, red);
+  if (tid == 0) parts[blockIdx.x] = tot;
 }
 
 // shared checks of an image read through (batch, channel, pixel) strides
@@ -417,7 +386,7 @@ inline int image_check(const char* fn, const void* img, long bs, long cs, long p
   SDHIP_CHECK_ARG(img, "%s: null image pointer", fn);
   SDHIP_CHECK_ARG(C >= 1 && C <= WI_MAX_C, "%s: C %d (1 <= C <= %d)", fn, C, WI_MAX_C);
   SDHIP_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && (long)B * H * W <= PM_MAX_NPIX, "%s: B %d, H %d, W %d", fn, B, H, W);
-  SDHIP_CHECK_ARG(bs >= 1 && cs >= 1 && ps >= 1, "%s: image strides %ld / %ld / %ld (batch, channel, pixel) must be positive", fn, bs, cs, ps);
+  SDHIP_CHECK_IMAGE_STRIDES(fn, bs, cs, ps);
   return 0;
 }
 
@@ -474,7 +443,7 @@ extern "C" int sdhip_gate_blend_bwd(const void* gy, int ldgy, const void* a, int
   sdhip_by_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     sdhip_by_flag(sdhip_vec_ok<T>(C, {ldgy, lda, ldb, ldga, ldgb}, {gy, a, b, ga, gb}), [&](auto V) {
-      const int G = blend_group(C / Unit<T, V()>::N);
+      const int G = lane_group(C / Unit<T, V()>::N);
       hipLaunchKernelGGL((gate_blend_bwd_kernel<T, V()>), stream_grid(npix * G), dim3(256), 0, (hipStream_t)stream, (const T*)gy, ldgy,
                          (const T*)a, lda, (const T*)b, ldb, (const T*)g, ldg, (T*)ga, ldga, (T*)gb, ldgb, (T*)gg, ldgg, npix, C, G);
     });
@@ -497,8 +466,7 @@ extern "C" int sdhip_photo_mse(const void* w, int ldw, int dtype, const float* l
   SDHIP_CHECK_DTYPE("photo_mse", dtype);
   const long npix = (long)B * H * W;
   const long tiles = pm_tiles(npix);
-  SDHIP_CHECK_ARG(workspace_bytes >= tiles * (long)sizeof(double) && (((uintptr_t)workspace) & 7) == 0,
-                  "photo_mse: workspace of %ld bytes (8-byte aligned), %ld needed", workspace_bytes, tiles * (long)sizeof(double));
+  SDHIP_CHECK_WORKSPACE("photo_mse", workspace, workspace_bytes, tiles * (long)sizeof(double));
   hipStream_t s = (hipStream_t)stream;
   const double n = (double)npix * C;
   double* parts = (double*)workspace;
@@ -508,9 +476,7 @@ extern "C" int sdhip_photo_mse(const void* w, int ldw, int dtype, const float* l
                        (float)(2.0 * (double)weight / n), (long)H * W, C, npix);
   });
   SDHIP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(photo_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)parts, tiles, (double)weight / n, loss);
-  SDHIP_LAUNCH_CHECK();
-  return SDHIP_OK;
+  return sdhip_slot_fold(__func__, parts, tiles, (double)weight / n, loss, s);
 }
 
 extern "C" int sdhip_warp_blend_fwd(const void* seg_left, int ldl, const void* seg_right, int ldr, const void* disp, int ldd,

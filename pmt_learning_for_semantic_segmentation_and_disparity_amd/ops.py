@@ -1717,10 +1717,7 @@ def warp_image_masked(right, gt_disp, out=None):
         if tuple(out.shape) != (B, C, H, W) or out.dtype not in (torch.float32, torch.bfloat16) or _nhwc_ld(out) is None:
             raise _lib.SdhipError("warp_image_masked: `out` must be a (B,C,H,W) = %s f32 / bf16 tensor in NHWC memory" % ((B, C, H, W),))
     _require_gpu(right, gt_disp, out)
-    strides = _image_strides(right)
-    if strides is None:
-        right = right.contiguous()
-        strides = _image_strides(right)
+    right, strides = _strided_image(right)
     if out is None:
         out, ldy = alloc_nhwc(B, C, H, W, right.dtype, right.device)
     else:
@@ -1730,83 +1727,111 @@ def warp_image_masked(right, gt_disp, out=None):
     return out
 
 
-class _GateBlendFn(torch.autograd.Function):
-    """y = (1 - g) * a + g * b with a one-channel gate; ga, gb and gg come out of one backward launch."""
+class _GateFn(torch.autograd.Function):
+    """A one-channel gate g on two C-channel maps, `pair` choosing between the two operators (csrc/edge.hip, csrc/warp.hip):
+      pair:  cat(a * g, b * (1 - g), dim=1) written straight into one 2C-channel NHWC slab at the padded pixel stride
+      blend: (1 - g) * a + g * b, C channels
+    ga, gb and gg come out of one backward launch."""
 
     @staticmethod
-    def forward(ctx, a, b, g):
+    def forward(ctx, a, b, g, pair):
         B, C, H, W = a.shape
         av, lda = nhwc_view(a)
         bv, ldb = nhwc_view(b)
         gv, ldg = nhwc_view(g)
-        y = empty_nhwc(B, C, H, W, a.dtype, a.device)
-        call("sdhip_gate_blend_fwd", ptr(av), lda, ptr(bv), ldb, ptr(gv), ldg, ptr(y), C, B * H * W, C, dtype_code(a), stream_ptr())
+        y, ldy = alloc_nhwc(B, 2 * C, H, W, a.dtype, a.device) if pair else (empty_nhwc(B, C, H, W, a.dtype, a.device), C)
+        call("sdhip_gate_pair_fwd" if pair else "sdhip_gate_blend_fwd", ptr(av), lda, ptr(bv), ldb, ptr(gv), ldg, ptr(y), ldy,
+             B * H * W, C, dtype_code(a), stream_ptr())
         ctx.save_for_backward(av, bv, gv)
-        ctx.cfg = (lda, ldb, ldg)
+        ctx.cfg = (lda, ldb, ldg, pair)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         av, bv, gv = ctx.saved_tensors
-        lda, ldb, ldg = ctx.cfg
+        lda, ldb, ldg, pair = ctx.cfg
         B, C, H, W = av.shape
         gyv, ldgy = nhwc_view(gy)
         ga = empty_nhwc(B, C, H, W, av.dtype, av.device)
         gb = empty_nhwc(B, C, H, W, av.dtype, av.device)
         gg = empty_nhwc(B, 1, H, W, av.dtype, av.device)
-        call("sdhip_gate_blend_bwd", ptr(gyv), ldgy, ptr(av), lda, ptr(bv), ldb, ptr(gv), ldg, ptr(ga), C, ptr(gb), C, ptr(gg), 1,
-             B * H * W, C, dtype_code(av), stream_ptr())
-        return ga, gb, gg
+        call("sdhip_gate_pair_bwd" if pair else "sdhip_gate_blend_bwd", ptr(gyv), ldgy, ptr(av), lda, ptr(bv), ldb, ptr(gv), ldg,
+             ptr(ga), C, ptr(gb), C, ptr(gg), 1, B * H * W, C, dtype_code(av), stream_ptr())
+        return ga, gb, gg, None
+
+
+def _check_gate_args(who, a, b, g):
+    if a.dim() != 4 or tuple(b.shape) != tuple(a.shape) or tuple(g.shape) != (a.shape[0], 1) + tuple(a.shape[2:]):
+        raise _lib.SdhipError("%s: need a, b (B,C,H,W) and g (B,1,H,W), got %s, %s and %s"
+                              % (who, tuple(a.shape), tuple(b.shape), tuple(g.shape)))
+    if a.numel() < 1:
+        raise _lib.SdhipError("%s of an empty tensor" % who)
+    if not a.dtype == b.dtype == g.dtype:
+        raise _lib.SdhipError("%s: a, b and g must share one dtype, got %s, %s and %s" % (who, a.dtype, b.dtype, g.dtype))
+    dtype_code(a)
+    _require_gpu(a, b, g)
 
 
 def gate_blend(a, b, g):
     """(1 - g) * a + g * b for a, b (B,C,H,W) and a one-channel gate g (B,1,H,W), all of one dtype (f32 / bf16): the unwarped blend
     `seg_branch_both` of the *_disp networks (models/dsnet_t2_warp.py:834) as one launch, and one backward launch for all three
     gradients.  (warp_blend with a zero disparity is NOT this: the warp's right-edge rule zeroes the last column.)"""
-    if a.dim() != 4 or tuple(b.shape) != tuple(a.shape) or tuple(g.shape) != (a.shape[0], 1) + tuple(a.shape[2:]):
-        raise _lib.SdhipError("gate_blend: need a, b (B,C,H,W) and g (B,1,H,W), got %s, %s and %s"
-                              % (tuple(a.shape), tuple(b.shape), tuple(g.shape)))
-    if a.numel() < 1:
-        raise _lib.SdhipError("gate_blend of an empty tensor")
-    if not a.dtype == b.dtype == g.dtype:
-        raise _lib.SdhipError("gate_blend: a, b and g must share one dtype, got %s, %s and %s" % (a.dtype, b.dtype, g.dtype))
-    dtype_code(a)
-    _require_gpu(a, b, g)
-    return _GateBlendFn.apply(a, b, g)
+    _check_gate_args("gate_blend", a, b, g)
+    return _GateFn.apply(a, b, g, False)
 
 
-_photo_ws = {}
+# ---------------------------------------------------------------------------- plumbing of the scalar loss terms
+_loss_ws = {}
 
 
-class _PhotoLossFn(torch.autograd.Function):
-    """weight * MSELoss(warped, left): value and gradient in one node (two launches), as _SegLossFn."""
+def _loss_workspace(term, key, nbytes, device):
+    """The scratch buffer the kernels of loss term `term` fold their slots in (csrc/loss_common.h), for the problem `key` on
+    `device`: uint8, at least nbytes, a whole number of 8-byte slots.  Cached, so a captured step finds it allocated; the
+    term is part of the key, so two terms of one step never share a buffer."""
+    key = (term,) + tuple(key) + (str(device),)
+    ws = _loss_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty((nbytes + 7) // 8 * 8, dtype=torch.uint8, device=device)
+        _loss_ws[key] = ws
+    return ws
+
+
+class _ValueGradFn(torch.autograd.Function):
+    """A scalar loss term whose kernels produce value and gradient in one pass: photo_loss, seg_loss, disp_smooth_loss,
+    edge_loss.  `launch(x, loss, *args)` adds the term onto the f64 `loss` and returns its gradient w.r.t. x, the one input
+    that gets one."""
 
     @staticmethod
-    def forward(ctx, warped, left, weight):
-        B, C, H, W = warped.shape
-        wv, ldw = nhwc_view(warped)
-        strides = _image_strides(left)
-        if strides is None:
-            left = left.contiguous()
-            strides = _image_strides(left)
-        npix = B * H * W
-        nbytes = _lib.photo_mse_workspace_bytes(npix)
-        key = (npix, str(warped.device))
-        ws = _photo_ws.get(key)
-        if ws is None or ws.numel() * 8 < nbytes:
-            ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=warped.device)
-            _photo_ws[key] = ws
-        loss = torch.zeros(1, dtype=torch.float64, device=warped.device)
-        g = empty_nhwc(B, C, H, W, warped.dtype, warped.device)
-        call("sdhip_photo_mse", ptr(wv), ldw, dtype_code(wv), ptr(left), strides[0], strides[1], strides[2], ptr(g), ptr(loss), weight,
-             B, H, W, C, ptr(ws), ws.numel() * 8, stream_ptr())
-        ctx.save_for_backward(g)
+    def forward(ctx, x, launch, *args):
+        loss = torch.zeros(1, dtype=torch.float64, device=x.device)
+        ctx.save_for_backward(launch(x, loss, *args))
+        ctx.nargs = 2 + len(args)
         return loss.float().reshape(())
 
     @staticmethod
     def backward(ctx, gout):
         g, = ctx.saved_tensors
-        return g * gout.to(g.dtype), None, None
+        return (g * gout.to(g.dtype),) + (None,) * (ctx.nargs - 1)
+
+
+def _dense_disp(disp):
+    """A (B,1,H,W) map as the loss kernels read it, pixel after pixel: disp itself, or a dense copy of a 1-channel map that
+    sits inside a padded pixel stride (a direct conv output)."""
+    dv, ldd = nhwc_view(disp)
+    return dv if ldd == 1 else disp.contiguous()
+
+
+def _photo_term(warped, loss, left, weight):
+    """loss += weight * MSELoss(warped, left); returns the gradient w.r.t. warped: the two launches of sdhip_photo_mse."""
+    B, C, H, W = warped.shape
+    wv, ldw = nhwc_view(warped)
+    left, strides = _strided_image(left)
+    npix = B * H * W
+    ws = _loss_workspace("photo", (npix,), _lib.photo_mse_workspace_bytes(npix), warped.device)
+    g = empty_nhwc(B, C, H, W, warped.dtype, warped.device)
+    call("sdhip_photo_mse", ptr(wv), ldw, dtype_code(wv), ptr(left), strides[0], strides[1], strides[2], ptr(g), ptr(loss), weight,
+         B, H, W, C, ptr(ws), ws.numel(), stream_ptr())
+    return g
 
 
 def photo_loss(warped, left, weight=1.0):
@@ -1829,13 +1854,10 @@ def photo_loss(warped, left, weight=1.0):
     _require_gpu(warped, left)
     if warped.device != left.device:
         raise _lib.SdhipError("photo_loss: warped and left live on different devices")
-    return _PhotoLossFn.apply(warped, left, float(weight))
+    return _ValueGradFn.apply(warped, _photo_term, left, float(weight))
 
 
 # ============================================================================ losses of the timed step
-_lovasz_ws = {}
-_seg_ws = {}
-
 # entries of the reference's `-loss` list (losses/multiLosses.py:8-128) built here / defined upstream but not built
 SEG_LOSS_TERMS = ("cross_entropy", "lovasz_loss", "tversky_loss2", "dice_loss", "diceEntropy")
 SEG_LOSS_NOT_BUILT = ("tversky_loss", "area_ce", "area_hinge", "binary_ce", "categoricalNlll", "ohm_loss", "dual_edge_reg")
@@ -1889,12 +1911,7 @@ def _seg_terms(s, tv, ldt, grad, loss, ce_weight, terms, cw):
     (tv, ldt): nhwc_view of the one-hot target."""
     B, C, H, W = s.shape
     sv, ld = nhwc_view(s)
-    nbytes = _lib.seg_terms_workspace_bytes(B, H * W, C)
-    key = (B, H * W, C, str(s.device))
-    ws = _seg_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
-        _seg_ws[key] = ws
+    ws = _loss_workspace("seg", (B, H * W, C), _lib.seg_terms_workspace_bytes(B, H * W, C), s.device)
     dt, st = dtype_code(s), stream_ptr()
     call("sdhip_seg_sums", ptr(sv), ld, ptr(tv), ldt, B, H * W, C, ptr(ws), ws.numel(), dt, st)
     call("sdhip_seg_finish", ptr(ws), ws.numel(), ptr(cw), ptr(loss), B, H * W, C, ce_weight, terms, st)
@@ -1906,12 +1923,7 @@ def _lovasz_term(s, tv, ldt, grad, loss, weight, ignore_void):
     B, C, H, W = s.shape
     npix = B * H * W
     sv, ld = nhwc_view(s)
-    nbytes = _lib.lovasz_workspace_bytes(npix, C)
-    key = (npix, C, str(s.device))
-    ws = _lovasz_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
-        _lovasz_ws[key] = ws
+    ws = _loss_workspace("lovasz", (npix, C), _lib.lovasz_workspace_bytes(npix, C), s.device)
     call("sdhip_lovasz_softmax", ptr(sv), ld, ptr(tv), ldt, ptr(grad), C, ptr(loss), npix, C, weight, ptr(ws),
          ws.numel(), int(ignore_void), dtype_code(s), stream_ptr())
 
@@ -1931,26 +1943,16 @@ def _check_seg_args(logits, seg_t, class_weights):
             raise _lib.SdhipError("class_weights has %d entries for %d classes" % (n, C))
 
 
-class _SegLossFn(torch.autograd.Function):
-    """lossSeg_fn(loss, ...)[2] on one segmentation head (losses/multiLosses.py:8-128): value and gradient in one node."""
-
-    @staticmethod
-    def forward(ctx, logits, seg_t, plan, cw, ignore_void):
-        ce_weight, lovasz_weight, terms = plan
-        B, C, H, W = logits.shape
-        loss = torch.zeros(1, dtype=torch.float64, device=logits.device)
-        g = empty_nhwc(B, C, H, W, logits.dtype, logits.device)
-        tv, ldt = nhwc_view(seg_t)
-        _seg_terms(logits, tv, ldt, g, loss, ce_weight, terms, cw)
-        if lovasz_weight:
-            _lovasz_term(logits, tv, ldt, g, loss, lovasz_weight, ignore_void)
-        ctx.save_for_backward(g)
-        return loss.float().reshape(())
-
-    @staticmethod
-    def backward(ctx, gout):
-        g, = ctx.saved_tensors
-        return g * gout.to(g.dtype), None, None, None, None
+def _seg_loss_term(logits, loss, seg_t, plan, cw, ignore_void):
+    """loss += lossSeg_fn(loss list, ...)[2] on one segmentation head (losses/multiLosses.py:8-128); returns the gradient."""
+    ce_weight, lovasz_weight, terms = plan
+    B, C, H, W = logits.shape
+    g = empty_nhwc(B, C, H, W, logits.dtype, logits.device)
+    tv, ldt = nhwc_view(seg_t)
+    _seg_terms(logits, tv, ldt, g, loss, ce_weight, terms, cw)
+    if lovasz_weight:
+        _lovasz_term(logits, tv, ldt, g, loss, lovasz_weight, ignore_void)
+    return g
 
 
 def seg_loss(logits, seg_target, loss=("cross_entropy",), class_weights=None, ignore_void=False):
@@ -1966,7 +1968,7 @@ def seg_loss(logits, seg_target, loss=("cross_entropy",), class_weights=None, ig
     _check_seg_args(logits, seg_target, class_weights)
     _require_gpu(logits, seg_target)
     cw = seg_class_weights(class_weights, logits.shape[1], logits.device)
-    return _SegLossFn.apply(logits, seg_target, plan, cw, bool(ignore_void))
+    return _ValueGradFn.apply(logits, _seg_loss_term, seg_target, plan, cw, bool(ignore_void))
 
 
 class _TrainLossFn(torch.autograd.Function):
@@ -1997,9 +1999,7 @@ class _TrainLossFn(torch.autograd.Function):
             else:                                   # seg1 / seg3: ['cross_entropy'] with the class weights (:279,297)
                 _seg_terms(s, tv, ldt, g, loss, 1.0, 0, cw)
             grads.append(g)
-        dv, ldd = nhwc_view(disp)
-        if ldd != 1:      # 1-channel map inside a padded pixel stride (direct conv output): densify
-            dv = disp.contiguous()
+        dv = _dense_disp(disp)
         if not disp_t.is_contiguous():
             raise _lib.SdhipError("disparity target must be a dense (B,1,H,W) tensor")
         gd = torch.empty_like(dv)
@@ -2169,9 +2169,6 @@ def train_loss(seg1, disp, seg2, seg_target, disp_target, use_lovasz=True, mask_
     return _TrainLossFn.apply(seg1, disp, seg2, seg_target, disp_target, use_lovasz, mask_invalid_disp, ignore_void, seg3, plan, cw)
 
 
-_disp_smooth_ws = {}
-
-
 def _image_strides(left):
     """(batch, channel, pixel) strides of a (B,>=3,H,W) image whose rows follow one another pixel by pixel (NCHW, channels-last
     or a channel slice of either), or None."""
@@ -2184,38 +2181,28 @@ def _image_strides(left):
     return sb, sc, sw
 
 
-class _DispSmoothFn(torch.autograd.Function):
-    """smoothing_gradients (util/utilTorchLoss.py:41-101) on one disparity map: value and gradient in one stencil pass."""
+def _strided_image(img):
+    """(img, its (batch, channel, pixel) strides); a layout _image_strides does not serve is copied to NCHW first."""
+    strides = _image_strides(img)
+    if strides is None:
+        img = img.contiguous()
+        strides = _image_strides(img)
+    return img, strides
 
-    @staticmethod
-    def forward(ctx, left, disp, seg_t, weight):
-        B, _, H, W = disp.shape
-        C = seg_t.shape[1]
-        strides = _image_strides(left)
-        if strides is None:
-            left = left.contiguous()
-            strides = _image_strides(left)
-        tv, ldt = nhwc_view(seg_t)
-        dv, ldd = nhwc_view(disp)
-        if ldd != 1:      # 1-channel map inside a padded pixel stride (direct conv output): densify
-            dv = disp.contiguous()
-        nbytes = _lib.disp_smooth_workspace_bytes(B, H, W)
-        key = (B, H, W, str(disp.device))
-        ws = _disp_smooth_ws.get(key)
-        if ws is None or ws.numel() * 8 < nbytes:
-            ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=disp.device)
-            _disp_smooth_ws[key] = ws
-        loss = torch.zeros(1, dtype=torch.float64, device=disp.device)
-        g = torch.empty((B, 1, H, W), dtype=dv.dtype, device=dv.device)
-        call("sdhip_disp_smooth", ptr(left), strides[0], strides[1], strides[2], ptr(tv), ldt, ptr(dv), dtype_code(dv), ptr(g),
-             ptr(loss), B, H, W, C, weight, ptr(ws), ws.numel() * 8, stream_ptr())
-        ctx.save_for_backward(g)
-        return loss.float().reshape(())
 
-    @staticmethod
-    def backward(ctx, gout):
-        g, = ctx.saved_tensors
-        return None, g * gout.to(g.dtype), None, None
+def _disp_smooth_term(disp, loss, left, seg_t, weight):
+    """loss += weight * smoothing_gradients (util/utilTorchLoss.py:41-101) on one disparity map; returns the gradient w.r.t.
+    disp: value and gradient in one stencil pass."""
+    B, _, H, W = disp.shape
+    C = seg_t.shape[1]
+    left, strides = _strided_image(left)
+    tv, ldt = nhwc_view(seg_t)
+    dv = _dense_disp(disp)
+    ws = _loss_workspace("disp_smooth", (B, H, W), _lib.disp_smooth_workspace_bytes(B, H, W), disp.device)
+    g = torch.empty((B, 1, H, W), dtype=dv.dtype, device=dv.device)
+    call("sdhip_disp_smooth", ptr(left), strides[0], strides[1], strides[2], ptr(tv), ldt, ptr(dv), dtype_code(dv), ptr(g),
+         ptr(loss), B, H, W, C, weight, ptr(ws), ws.numel(), stream_ptr())
+    return g
 
 
 def disp_smooth_loss(left, disp_pred, seg_target, weight=1.0):
@@ -2248,7 +2235,7 @@ def disp_smooth_loss(left, disp_pred, seg_target, weight=1.0):
     if seg_target.dtype != torch.float32:
         raise _lib.SdhipError("disp_smooth_loss: the one-hot segmentation target must be f32 (got %s)" % seg_target.dtype)
     dtype_code(disp_pred)
-    return _DispSmoothFn.apply(left, disp_pred, seg_target, float(weight))
+    return _ValueGradFn.apply(disp_pred, _disp_smooth_term, left, seg_target, float(weight))
 
 
 # ============================================================================ Ext_small edge networks (csrc/edge.hip)
@@ -2270,16 +2257,10 @@ def grad_mag(img, dtype=None):
         raise _lib.SdhipError("grad_mag: output dtype %s (f32 and bf16 only)" % dtype)
     if img.requires_grad:
         raise _lib.SdhipError("grad_mag has no backward pass: the image must not require a gradient")
-    strides = _image_strides(img)
-    if strides is None:
-        img = img.contiguous()
-        strides = _image_strides(img)
+    img, strides = _strided_image(img)
     out, ldy = alloc_nhwc(B, C, H, W, dtype, img.device)
     call("sdhip_grad_mag", ptr(img), strides[0], strides[1], strides[2], dt_in, ptr(out), ldy, _lib.code_of(dtype), B, H, W, C, stream_ptr())
     return out
-
-
-_edge_ws = {}
 
 
 def _check_edge_args(edge_logits, edges):
@@ -2295,34 +2276,15 @@ def _check_edge_args(edge_logits, edges):
     dtype_code(edge_logits)
 
 
-def _edge_term(z, edges, loss):
-    """loss += lossEdge_fn(edges, z); returns the gradient w.r.t. z (dense, z's dtype): the three launches of sdhip_edge_bce."""
+def _edge_term(z, loss, edges):
+    """loss += lossEdge_fn(edges, z) (losses/multiLosses.py:166-182); returns the gradient w.r.t. z (dense, z's dtype): the
+    three launches of sdhip_edge_bce."""
     n = z.numel()
     zv, ldz = nhwc_view(z)
-    nbytes = _lib.edge_bce_workspace_bytes(n)
-    key = (n, str(z.device))
-    ws = _edge_ws.get(key)
-    if ws is None or ws.numel() * 8 < nbytes:
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=z.device)
-        _edge_ws[key] = ws
+    ws = _loss_workspace("edge", (n,), _lib.edge_bce_workspace_bytes(n), z.device)
     g = torch.empty(tuple(z.shape), dtype=z.dtype, device=z.device)
-    call("sdhip_edge_bce", ptr(zv), ldz, dtype_code(zv), ptr(edges), ptr(g), ptr(loss), n, ptr(ws), ws.numel() * 8, stream_ptr())
+    call("sdhip_edge_bce", ptr(zv), ldz, dtype_code(zv), ptr(edges), ptr(g), ptr(loss), n, ptr(ws), ws.numel(), stream_ptr())
     return g
-
-
-class _EdgeLossFn(torch.autograd.Function):
-    """lossEdge_fn (losses/multiLosses.py:166-182) on the edge head: value and gradient in one node."""
-
-    @staticmethod
-    def forward(ctx, logits, edges):
-        loss = torch.zeros(1, dtype=torch.float64, device=logits.device)
-        ctx.save_for_backward(_edge_term(logits, edges, loss))
-        return loss.float().reshape(())
-
-    @staticmethod
-    def backward(ctx, gout):
-        g, = ctx.saved_tensors
-        return g * gout.to(g.dtype), None
 
 
 def edge_loss(edge_logits, edges):
@@ -2335,7 +2297,7 @@ def edge_loss(edge_logits, edges):
     Returns an f32 scalar; value and gradient are reproducible bit for bit."""
     _check_edge_args(edge_logits, edges)
     _require_gpu(edge_logits, edges)
-    return _EdgeLossFn.apply(edge_logits, edges)
+    return _ValueGradFn.apply(edge_logits, _edge_term, edges)
 
 
 class _EdgeStepLossFn(torch.autograd.Function):
@@ -2356,12 +2318,10 @@ class _EdgeStepLossFn(torch.autograd.Function):
             call("sdhip_ce_loss", ptr(sv), ld, ptr(tv), ldt, ptr(gs), C, ptr(loss), npix, C, 1.0, dt, stream_ptr())
         else:
             _seg_terms(seg, tv, ldt, gs, loss, 1.0, 0, cw)
-        dv, ldd = nhwc_view(disp)
-        if ldd != 1:      # 1-channel map inside a padded pixel stride (direct conv output): densify
-            dv = disp.contiguous()
+        dv = _dense_disp(disp)
         gd = torch.empty_like(dv)
         call("sdhip_l1_loss", ptr(dv), ptr(disp_t), ptr(gd), ptr(loss), npix, 1.0, int(mask_invalid_disp), dt, stream_ptr())
-        ge = _edge_term(edge_logits, edges, loss) if edges is not None else None
+        ge = _edge_term(edge_logits, loss, edges) if edges is not None else None
         ctx.save_for_backward(ge, gd, gs)
         return loss.float()
 
@@ -2393,49 +2353,12 @@ def edge_step_loss(edge_logits, disp, seg_logits, seg_target, disp_target, edges
     return _EdgeStepLossFn.apply(edge_logits, disp, seg_logits, seg_target, disp_target, edges, bool(mask_invalid_disp), cw)
 
 
-class _GatePairFn(torch.autograd.Function):
-    """cat(a * g, b * (1 - g), dim=1) written straight into one NHWC slab; ga, gb and gg come out of one backward launch."""
-
-    @staticmethod
-    def forward(ctx, a, b, g):
-        B, C, H, W = a.shape
-        av, lda = nhwc_view(a)
-        bv, ldb = nhwc_view(b)
-        gv, ldg = nhwc_view(g)
-        y, ldy = alloc_nhwc(B, 2 * C, H, W, a.dtype, a.device)
-        call("sdhip_gate_pair_fwd", ptr(av), lda, ptr(bv), ldb, ptr(gv), ldg, ptr(y), ldy, B * H * W, C, dtype_code(a), stream_ptr())
-        ctx.save_for_backward(av, bv, gv)
-        ctx.cfg = (lda, ldb, ldg)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        av, bv, gv = ctx.saved_tensors
-        lda, ldb, ldg = ctx.cfg
-        B, C, H, W = av.shape
-        gyv, ldgy = nhwc_view(gy)
-        ga = empty_nhwc(B, C, H, W, av.dtype, av.device)
-        gb = empty_nhwc(B, C, H, W, av.dtype, av.device)
-        gg = empty_nhwc(B, 1, H, W, av.dtype, av.device)
-        call("sdhip_gate_pair_bwd", ptr(gyv), ldgy, ptr(av), lda, ptr(bv), ldb, ptr(gv), ldg, ptr(ga), C, ptr(gb), C, ptr(gg), 1,
-             B * H * W, C, dtype_code(av), stream_ptr())
-        return ga, gb, gg
-
-
 def gate_pair(a, b, g):
     """torch.cat((a * g, b * (1 - g)), 1) for a, b (B,C,H,W) and a one-channel gate g (B,1,H,W), all of one dtype (f32 / bf16):
     the `s2_d*s2_at | s2_s*(1-s2_at)` line of the Ext_small networks (models/dsnet_t2_ext_small.py:361) as one launch that writes
     both halves into one 2C-channel NHWC buffer, and one backward launch for all three gradients."""
-    if a.dim() != 4 or tuple(b.shape) != tuple(a.shape) or tuple(g.shape) != (a.shape[0], 1) + tuple(a.shape[2:]):
-        raise _lib.SdhipError("gate_pair: need a, b (B,C,H,W) and g (B,1,H,W), got %s, %s and %s"
-                              % (tuple(a.shape), tuple(b.shape), tuple(g.shape)))
-    if a.numel() < 1:
-        raise _lib.SdhipError("gate_pair of an empty tensor")
-    _require_gpu(a, b, g)
-    if not a.dtype == b.dtype == g.dtype:
-        raise _lib.SdhipError("gate_pair: a, b and g must share one dtype, got %s, %s and %s" % (a.dtype, b.dtype, g.dtype))
-    dtype_code(a)
-    return _GatePairFn.apply(a, b, g)
+    _check_gate_args("gate_pair", a, b, g)
+    return _GateFn.apply(a, b, g, True)
 
 
 # ============================================================================ dropout / global average pool

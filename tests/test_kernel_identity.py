@@ -26,14 +26,16 @@ def _block(text, first, nxt):
 
 @pytest.fixture(scope="module")
 def variants(tmp_path_factory):
-    """hanet.hip as it is, with one constant of one kernel changed, and with two kernels' launches trading places; each in
-    a tree of its own (<tree>/pkg/csrc next to <tree>/include), compiled once."""
+    """hanet.hip as it is, with one constant of one kernel changed, with two kernels' launches trading places, and with one
+    kernel under another name; each in a tree of its own (<tree>/pkg/csrc next to <tree>/include), compiled once."""
     src = open(os.path.join(CSRC, "hanet.hip")).read()
     assert src.count(SEED_MUL) == 1
     # the compiler emits template kernels in the order the host code first names them: trade the two entry points
     a, b = _block(src, 'extern "C" int sdhip_mul_rows_fwd(', 'extern "C" int sdhip_mul_rows_bwd(')
     c = src.index('extern "C" int sdhip_dropout_channels(')
-    texts = {"same": src, "const": src.replace(SEED_MUL, "0x9E3779B97F4A7C17ULL"), "swap": src[:a] + src[b:c] + src[a:b] + src[c:]}
+    texts = {"same": src, "const": src.replace(SEED_MUL, "0x9E3779B97F4A7C17ULL"), "swap": src[:a] + src[b:c] + src[a:b] + src[c:],
+             "rename": src.replace("zero_rows_kernel", "clear_rows_kernel")}
+    assert src.count("zero_rows_kernel") == 2                         # the kernel and its one launch
     base = tmp_path_factory.mktemp("kernel_identity")
     dirs = {}
     for name, text in texts.items():
@@ -44,7 +46,7 @@ def variants(tmp_path_factory):
         shutil.copy(os.path.join(CSRC, "sdhip_common.h"), d / "sdhip_common.h")
         (d / "hanet.hip").write_text(text)
         dirs[name] = str(d)
-    with ThreadPoolExecutor(max_workers=3) as ex:
+    with ThreadPoolExecutor(max_workers=4) as ex:
         asm = dict(zip(dirs, ex.map(lambda d: ki.assemble(os.path.join(d, "hanet.hip"), os.path.join(d, "hanet.s")), dirs.values())))
     return dirs, asm
 
@@ -73,3 +75,19 @@ def test_kernels_that_trade_places_are_still_identical(variants):
     assert asm["same"] != asm["swap"]
     n, same, bad = ki.compare_asm(asm["same"], asm["swap"])
     assert n == same >= 10 and not bad, bad
+
+
+def test_a_renamed_kernel_is_missing_without_rename_and_identical_with_it(variants, capsys):
+    dirs, asm = variants
+    n, same, bad = ki.compare_asm(asm["same"], asm["rename"])
+    assert n - same == 2 and len(bad) == 4, bad                       # f32 and bf16, each only in A and only in B
+    assert sum("zero_rows_kernel" in b and "only in A" in b for b in bad) == 2, bad
+    assert sum("clear_rows_kernel" in b and "only in B" in b for b in bad) == 2, bad
+    assert ki.main([dirs["same"], dirs["rename"]]) == 1
+    assert "only in A" in capsys.readouterr().out
+    # the new name is one letter longer: the count in front of it in the mangled symbol follows
+    n, same, bad = ki.compare_asm(ki.rename(asm["same"], [("zero_rows_kernel", "clear_rows_kernel")]), asm["rename"])
+    assert n == same >= 10 and not bad, bad
+    assert ki.main([dirs["same"], dirs["rename"], "--rename", "zero_rows_kernel=clear_rows_kernel"]) == 0
+    m = re.search(r"hanet\.hip\s+kernels\s+(\d+), identical\s+(\d+)", capsys.readouterr().out)
+    assert m and int(m.group(1)) == int(m.group(2)) >= 10

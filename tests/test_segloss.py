@@ -312,11 +312,47 @@ def test_poisoned_workspace():
         z, t, w, void = _inputs(case)
         for names in (("cross_entropy", "tversky_loss2"), ("diceEntropy",)):
             a = _run(z, t, names, w, void)
-            assert ops._seg_ws
-            for ws in ops._seg_ws.values():
+            assert any(k[0] == "seg" for k in ops._loss_ws)
+            for ws in ops._loss_ws.values():
                 ws.fill_(0xFF)                       # all-ones words: NaN as f32 and as f64
             b = _run(z, t, names, w, void)
             assert torch.isfinite(b[0]).all() and torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), (case, names)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_poisoned_slot_fold_workspaces(dtype):
+    """photo_loss, edge_loss and disp_smooth_loss share one slot fold (csrc/loss_common.h): every slot is written before the
+    fold reads it.  Shapes of more than one slot: 1500 pixels = 2 tiles of 1024, 4500 elements = 2 tiles of 4096, and a
+    17 x 65 map = 2 x 2 stencil tiles of 16 x 64 (DS_TH x DS_TW)."""
+    from pmt_learning_for_semantic_segmentation_and_disparity_amd import ops
+    gen = torch.Generator().manual_seed(11)
+    r = lambda *s: torch.rand(*s, generator=gen)
+    left = r(1, 3, 5, 300).cuda()
+    edges = (r(1, 1, 9, 500) < 0.3).float().cuda()
+    img = r(1, 3, 17, 65).cuda()
+    onehot = torch.zeros(1, 2, 17, 65)
+    onehot[:, 0, :, :40] = 1
+    onehot[:, 1, :, 40:] = 1
+    onehot = onehot.cuda()
+    terms = {"photo": (r(1, 3, 5, 300), lambda x: ops.photo_loss(x, left)),
+             "edge": (r(1, 1, 9, 500) - 0.5, lambda x: ops.edge_loss(x, edges)),
+             "disp_smooth": (8.0 * r(1, 1, 17, 65), lambda x: ops.disp_smooth_loss(img, x, onehot))}
+
+    def run(x0, fn):
+        x = x0.cuda().to(dtype).requires_grad_(True)
+        loss = fn(x)
+        loss.backward()
+        return loss.detach().clone(), x.grad.clone()
+
+    first = {k: run(*v) for k, v in terms.items()}
+    assert set(terms) <= {k[0] for k in ops._loss_ws}
+    for ws in ops._loss_ws.values():
+        ws.fill_(0xFF)                               # all-ones words: NaN as f64, huge as u64
+    for k, v in terms.items():
+        loss, grad = run(*v)
+        assert torch.isfinite(loss).all() and torch.isfinite(grad).all() and float(loss) > 0, k
+        assert torch.equal(loss, first[k][0]) and torch.equal(grad, first[k][1]), k
 
 
 @pytest.mark.gpu

@@ -1,9 +1,11 @@
 """Is the gfx950 device code of two csrc directories the same, kernel by kernel?  (no GPU needed)
-  python tools/kernel_identity.py CSRC_A CSRC_B [file.hip ...]
+  python tools/kernel_identity.py CSRC_A CSRC_B [--rename OLD=NEW ...] [file.hip ...]
 Every .hip of both directories is compiled to device assembly with the flags of build.py.  The compiler emits template
 instantiations in the order the host code first names them, so the files are not compared as a whole: per file, the set
 of symbols, each function's instructions, each kernel's descriptor block and each kernel's metadata entry (registers,
 LDS, scratch, kernarg layout) must match.  Each directory keeps its place in a tree (it finds ../../include/sdhip.h).
+A kernel that B calls by another name is compared all the same with --rename OLD=NEW (repeatable): OLD, a substring of
+A's mangled symbols, is written as NEW in A's assembly before the comparison.
 Prints `<file>: kernels N, identical N` per file; exits 1 and names the symbols on any difference."""
 import importlib.util
 import os
@@ -27,6 +29,14 @@ def assemble(src, out):
         raise RuntimeError("hipcc failed on %s\n%s" % (src, r.stderr))
     with open(out) as f:
         return f.read()
+
+
+def rename(text, pairs):
+    """The assembly with every OLD of `pairs` [(OLD, NEW), ...] written as NEW.  A mangled symbol counts the letters of each
+    identifier in front of it (`16slot_fold_kernel`): where OLD is a whole identifier that count follows the name."""
+    for old, new in pairs:
+        text = text.replace("%d%s" % (len(old), old), "%d%s" % (len(new), new)).replace(old, new)
+    return text
 
 
 def _code(line):
@@ -76,7 +86,7 @@ def compare_asm(a, b):
     return len(ma), sum(1 for s in ma if s not in bad), ["%s: %s" % (s, w) for s, w in sorted(bad.items())]
 
 
-def compare_dirs(dir_a, dir_b, only=()):
+def compare_dirs(dir_a, dir_b, only=(), renames=()):
     """-> {file: (kernels, identical, [complaints])} over the .hip files of both directories"""
     names = [set(f for f in os.listdir(d) if f.endswith(".hip")) for d in (dir_a, dir_b)]
     res = {f: (0, 0, ["file only in %s" % ("A" if f in names[0] else "B")]) for f in names[0] ^ names[1] if not only or f in only}
@@ -86,14 +96,21 @@ def compare_dirs(dir_a, dir_b, only=()):
         with ThreadPoolExecutor(max_workers=6) as ex:
             asm = list(ex.map(lambda j: assemble(*j), jobs))
     for i, f in enumerate(both):
-        res[f] = compare_asm(asm[2 * i], asm[2 * i + 1])
+        res[f] = compare_asm(rename(asm[2 * i], renames), asm[2 * i + 1])
     return res
 
 
 def main(argv):
+    argv, renames = list(argv), []
+    while "--rename" in argv:
+        i = argv.index("--rename")
+        if i + 1 >= len(argv) or not all(argv[i + 1].partition("=")[::2]):
+            sys.exit("--rename takes OLD=NEW")
+        renames.append(tuple(argv[i + 1].split("=", 1)))
+        del argv[i:i + 2]
     if len(argv) < 2:
         sys.exit(__doc__)
-    res = compare_dirs(argv[0], argv[1], argv[2:])
+    res = compare_dirs(argv[0], argv[1], argv[2:], renames)
     ok = True
     for f in sorted(res):
         n, same, bad = res[f]
