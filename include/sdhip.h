@@ -378,6 +378,23 @@ int sdhip_resize_fwd(const void* x, int ldx, void* y, int ldy, int B, int H, int
 /* tmp: caller-provided f32 workspace of B*Ho*W*C elements. */
 int sdhip_resize_bwd(const void* gy, int ldg, void* gx, int ldgx, float* tmp, int B, int H, int W, int C,
                      int Ho, int Wo, int mode, float scale_h, float scale_w, int dtype, void* stream);
+/* The pooled pyramids (models/dsnet_t2.py:2037-2081): y = cat([x] + [bilinear(map_j -> (H, W)) for j < n], channels),
+ * align_corners=False, written by ONE launch that owns whole rows of the slab y (B, H, W, C + n*Cb; pixel stride ldy).
+ * maps: HOST array of n <= 8 branch maps (B, h, w, Cb; pixel stride ld) of any size; the table travels in the kernel
+ * arguments.  Every value has the bits sdhip_resize_fwd (mode 1) into the slice and a copy of x would give.
+ * SDHIP_ERR_UNSUPPORTED (nothing launched): a pointer, stride or channel count that is not a whole number of 16-byte units. */
+typedef struct SdhipPyrMap {
+  void* p;
+  int h, w, ld, reserved;
+} SdhipPyrMap;
+int sdhip_pyramid_upcat_fwd(const void* x, int ldx, const SdhipPyrMap* maps, int n, void* y, int ldy,
+                            int B, int H, int W, int C, int Cb, int dtype, void* stream);
+/* The gradients of all n maps from the slab gradient gy (read in place at channel C + j*Cb, pixel stride ldg) in two
+ * launches: the separable gather of sdhip_resize_bwd (W axis into tmp, then H), its window, weights and lanes-per-item
+ * rule per branch.  gmaps[j].p receives the gradient of map j (every element written).  tmp: f32 workspace of
+ * B*H*Cb*sum(w_j) elements.  The x-part of the gradient is the view gy[:, :C] and is not touched. */
+int sdhip_pyramid_upcat_bwd(const void* gy, int ldg, const SdhipPyrMap* gmaps, int n, float* tmp,
+                            int B, int H, int W, int C, int Cb, int dtype, void* stream);
 /* y[p,c] = a[p,c] * m[p] and its gradients (ga = g*m, gm[p] = sum_c g*a). */
 int sdhip_mul_bcast_fwd(const void* a, int lda, const void* m, int ldm, void* y, int ldy, long npix, int C,
                         int dtype, void* stream);

@@ -85,6 +85,20 @@ class WgradItem(ctypes.Structure):
                                             "pad_l", "D", "Do", "kd", "sd", "pad_d", "in_relu", "groups")]
 
 
+class PyrMap(ctypes.Structure):
+    """SdhipPyrMap of include/sdhip.h: one branch map of a pyramid (tests/test_pyramid.py holds it against the typedef)."""
+    _fields_ = [("p", ctypes.c_void_p)] + [(n, ctypes.c_int) for n in ("h", "w", "ld", "reserved")]
+
+
+def pyr_maps(entries):
+    """HOST table of the sdhip_pyramid_* entry points: entries = [(tensor, h, w, ld), ...].
+    -> (the argument, the array that must outlive the call)."""
+    t = (PyrMap * len(entries))()
+    for e, (m, h, w, ld) in zip(t, entries):
+        e.p, e.h, e.w, e.ld = m.data_ptr(), h, w, ld
+    return ctypes.cast(t, ctypes.c_void_p), t
+
+
 def lovasz_workspace_bytes(npix, C):
     return _lib.sdhip_lovasz_workspace_bytes(npix, C)
 
@@ -186,6 +200,7 @@ TUNE_BN_SLOT_MAX_MB = int(_diag_switch("SDHIP_TUNE_BN_SLOT_MAX_MB") or 40)
 DIAG_NO_BNPRO = bool(_diag_switch("SDHIP_DIAG_NO_BNPRO"))
 DIAG_NO_BNBWD_EPILOGUE = bool(_diag_switch("SDHIP_DIAG_NO_BNBWD_EPILOGUE"))
 DIAG_STEM_S2D = _diag_switch("SDHIP_STEM_S2D")
+DIAG_NO_PYRAMID_FUSE = bool(_diag_switch("SDHIP_DIAG_NO_PYRAMID_FUSE"))   # pyramids composed from single-tensor nodes, the unread b0 slab written (A/B)
 
 
 def abi_version():

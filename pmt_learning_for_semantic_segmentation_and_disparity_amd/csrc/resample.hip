@@ -7,20 +7,9 @@
 //   F.interpolate nearest / bilinear            models/dsnet_t2.py:927-936,1204-1275,2037-2081; models/aspp.py:88
 //   s2_d * at_s (1-channel attention broadcast) models/dsnet_t2.py:1258
 // Index arithmetic follows ATen's CPU kernels so that results agree with the reference to rounding.
-#include "sdhip_common.h"
+#include "resample_common.h"
 
 namespace {
-
-struct Img { int B, H, W, C, ld; };
-
-// flat work item -> (pixel, channel unit)
-template <int N>
-__device__ __forceinline__ bool item(long i, long npix, int units, long& pix, int& c0) {
-  if (i >= npix * units) return false;
-  pix = i / units;
-  c0 = (int)(i - pix * units) * N;
-  return true;
-}
 
 // ---------------------------------------------------------------- max pool 3x3 / stride 2 / pad 1
 template <typename T, bool VEC>
@@ -144,24 +133,6 @@ __global__ __launch_bounds__(256) void avgpool_bwd(const T* __restrict__ gy, Img
 }
 
 // ---------------------------------------------------------------- resize (ATen area_pixel_* index maths, f32)
-struct Axis { int in, out; float scale; int mode; };  // mode 0 nearest, 1 bilinear (align_corners=False), 2 bilinear (True)
-
-__device__ __forceinline__ int nearest_src(const Axis& a, int d) {
-  const int s = (int)floorf((float)d * a.scale);
-  return s < a.in - 1 ? s : a.in - 1;
-}
-__device__ __forceinline__ void linear_src(const Axis& a, int d, int& i0, int& i1, float& l1) {
-  float s;
-  if (a.mode == 2) s = (float)d * a.scale;
-  else { s = ((float)d + 0.5f) * a.scale - 0.5f; if (s < 0.f) s = 0.f; }
-  i0 = (int)s;
-  if (i0 > a.in - 1) i0 = a.in - 1;
-  i1 = i0 + (i0 < a.in - 1 ? 1 : 0);
-  l1 = s - (float)i0;
-  if (l1 < 0.f) l1 = 0.f;
-  if (l1 > 1.f) l1 = 1.f;
-}
-
 template <typename T, bool VEC>
 __global__ __launch_bounds__(256) void resize_fwd(const T* __restrict__ x, Img in, T* __restrict__ y, Img out, Axis ah, Axis aw) {
   constexpr int N = Unit<T, VEC>::N;
@@ -217,25 +188,10 @@ __global__ __launch_bounds__(256) void resize_bwd_axis(const T* __restrict__ gy,
     float acc[N];
 #pragma unroll
     for (int e = 0; e < N; ++e) acc[e] = 0.f;
-    // destination candidates: source coordinate within [i-1, i+1) (+-2 destinations of slack).  align_corners=False samples
-    // at (d + 0.5) * scale - 0.5, so its window is shifted by 0.5 * inv - 0.5 destinations: without the shift an upsampling by
-    // more than ~4x missed the destinations between (i+1) * inv and (i+1.5) * inv (x32: 7 % of the gradient dropped)
-    const float inv = a.scale > 0.f ? 1.f / a.scale : 0.f;
-    const float shift = a.mode == 1 ? 0.5f * inv - 0.5f : 0.f;
-    int lo = (int)floorf(((float)i - 1.f) * inv + shift) - 2, hi = (int)ceilf(((float)i + 1.f) * inv + shift) + 2;
-    if (a.scale <= 0.f) { lo = 0; hi = a.out - 1; }
-    if (lo < 0) lo = 0;
-    if (hi > a.out - 1) hi = a.out - 1;
+    int lo, hi;
+    bwd_window(a, i, lo, hi);       // destination candidates of source index i
     for (int d = lo + sub; d <= hi; d += split) {
-      float wgt = 0.f;
-      if (a.mode == 0) {
-        wgt = nearest_src(a, d) == i ? 1.f : 0.f;
-      } else {
-        int i0, i1; float l1;
-        linear_src(a, d, i0, i1, l1);
-        if (i0 == i) wgt += 1.f - l1;
-        if (i1 == i) wgt += l1;
-      }
+      const float wgt = bwd_weight(a, d, i);
       if (wgt != 0.f) {
         float g[N];
         Unit<T, VEC>::load(gy + ((o * a.out + d) * inner + r) * ldg + c0, g);
@@ -294,20 +250,6 @@ __global__ __launch_bounds__(256) void mul_bcast_bwd(const T* __restrict__ g, in
     }
     Elem<T>::st(gm + pix * ldgm, s);
   }
-}
-
-inline dim3 grid_for(long items) {
-  long b = (items + 255) / 256;
-  if (b > 4096) b = 4096;
-  if (b < 1) b = 1;
-  return dim3((unsigned)b);
-}
-
-Axis make_axis(int in, int out, int mode, float scale_override) {
-  Axis a; a.in = in; a.out = out; a.mode = mode;
-  if (mode == 2) a.scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  else a.scale = scale_override > 0.f ? scale_override : (float)in / (float)out;
-  return a;
 }
 
 }  // namespace
@@ -414,11 +356,7 @@ extern "C" int sdhip_resize_bwd(const void* gy, int ldg, void* gx, int ldgx, flo
   const long np1 = (long)B * Ho * W;
   // pass 2: along H.  layout [outer = B][axis = H][inner = W][C]; input tmp (f32), output gx (T)
   const long np2 = (long)B * H * W;
-  auto lanes = [](const Axis& a) {      // candidates per item ~ 2 / scale + 5 (see the kernel's [lo, hi] window)
-    const float span = a.scale > 0.f ? 2.f / a.scale + 5.f : (float)a.out;
-    return span >= 32.f ? 16 : span >= 12.f ? 4 : 1;
-  };
-  const int sw = lanes(aw), sh = lanes(ah);
+  const int sw = bwd_lanes(aw), sh = bwd_lanes(ah);
   sdhip_by_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     constexpr bool f32 = std::is_same<T, float>::value;

@@ -214,9 +214,10 @@ def _pool_branch(p, cin):
     return nn.Sequential(nn.AvgPool2d(p, p), convbn(cin, 32, 3, 1, 'same', 1), nn.ReLU(inplace=True))
 
 
-def _pyramid_branches(branches, x, groups):
+def _pyramid_branches(branches, x, groups, upsample=True):
     """[bilinear_up(relu(bn(conv3x3(avgpool_p(x))))) for each branch] (models/dsnet_t2.py:2037-2081).
-    The pools share work: pool_2p = 2x2 pool of pool_p (identical windows, mean of equal-size means)."""
+    The pools share work: pool_2p = 2x2 pool of pool_p (identical windows, mean of equal-size means).
+    upsample=False: the maps before the upsampling (_pyramid writes them into its slab itself)."""
     order = sorted(range(len(branches)), key=lambda j: branches[j][0].kernel_size)
     outs, pooled, prev_p = [None] * len(branches), x, 1
     for j in order:
@@ -227,13 +228,23 @@ def _pyramid_branches(branches, x, groups):
         pooled = ops.avgpool(pooled, p // prev_p)
         prev_p = p
         y = branches[j][1].fused(pooled, act=1, groups=groups)
-        outs[j] = ops.interpolate(y, size=x.shape[2:], mode='bilinear')
+        outs[j] = ops.interpolate(y, size=x.shape[2:], mode='bilinear') if upsample else y
     return outs
 
 
-def _pyramid(branches, x, groups):
-    """cat([x] + the branches of _pyramid_branches)."""
-    return ops.concat([x] + _pyramid_branches(branches, x, groups))
+def _pyramid(branches, x, groups, need_slab=True):
+    """cat([x] + the branches of _pyramid_branches), the slab written by one launch (ops.pyramid_upcat) and the gradients of
+    all branch maps by two.  need_slab=False: the pools, convolutions and BatchNorms run (their running statistics are part
+    of the checkpoint) and None is returned in place of a slab nobody reads."""
+    if ops._lib.DIAG_NO_PYRAMID_FUSE:
+        return ops.concat([x] + _pyramid_branches(branches, x, groups))
+    maps = _pyramid_branches(branches, x, groups, upsample=False)
+    if not need_slab:
+        return None
+    y = ops.pyramid_upcat(x, maps)
+    if y is None:
+        y = ops.concat([x] + [ops.interpolate(m, size=x.shape[2:], mode='bilinear') for m in maps])
+    return y
 
 
 class piramidNet2(nn.Module):
@@ -259,9 +270,11 @@ class piramidNet2(nn.Module):
         for j in range(3):
             setattr(self, 'branch2_%d' % j, _pool_branch(pv[j + 2], cin[2]))
 
-    def forward(self, x, groups=1):
+    def forward(self, x, groups=1, need_b0=True):
+        """need_b0=False (a caller that never reads the 1/2 pyramid): its pools, convolutions and BatchNorms run as
+        always — the running statistics move in train mode — but the 224-channel slab is not written; None stands in."""
         o = self.resnet_features(x, groups)
-        b0 = _pyramid([getattr(self, 'branch0_%d' % j) for j in range(5)], o[0], groups)
+        b0 = _pyramid([getattr(self, 'branch0_%d' % j) for j in range(5)], o[0], groups, need_slab=need_b0)
         b1 = _pyramid([getattr(self, 'branch1_%d' % j) for j in range(4)], o[1], groups)
         b2 = _pyramid([getattr(self, 'branch2_%d' % j) for j in range(3)], o[2], groups)
         return o[0], o[1], o[2], o[3], o[4], b2, b1, b0
@@ -392,10 +405,12 @@ class minidsnetExt(nn.Module):
     def forward(self, input_a, input_b, pos=None, disp_gt=None, seg_gt=None):
         B, _, H, W = input_a.shape
         both, img_a = _stereo_buffer(input_a, input_b, self.include_edges)
-        t = self.resnet_features(both, groups=2)          # taps of both towers, batch = [left | right]
+        # taps of both towers, batch = [left | right]; the 1/2 pyramid t[7] is read nowhere below (nor upstream: a_pyramidB_0)
+        t = self.resnet_features(both, groups=2, need_b0=False)
         if self.multiTaskLoss == 2:
             return self._forward_mt_heads(t, B, H, W, disp_gt, seg_gt)
-        halves = [ops.split_batch(u, B) for u in t]   # left / right tower outputs (one gradient buffer per tap in the backward)
+        # left / right tower outputs (one gradient buffer per tap in the backward)
+        halves = [ops.split_batch(u, B) if u is not None else (None, None) for u in t]
         a = [h[0] for h in halves]
         b = [h[1] for h in halves]
         xl3 = self.conv2d_ba3[0].fused(img_a, act=1)      # computed (and unused) exactly as in the reference

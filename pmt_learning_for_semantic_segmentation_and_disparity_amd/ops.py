@@ -1536,6 +1536,59 @@ def concat(xs):
     return _ConcatFn.apply(*xs)
 
 
+# ============================================================================ pooled pyramids (csrc/pyramid.hip)
+class _Unfused(Exception):
+    """An entry point of csrc/pyramid.hip declined its arguments in a forward pass (nothing was launched by it): the caller
+    composes the single-tensor nodes instead."""
+
+
+class _PyramidUpcatFn(torch.autograd.Function):
+    """cat([x] + [bilinear(m -> x's size) for m in maps], 1) as ONE launch that writes whole rows of the slab, and the
+    gradients of all maps in two; the x-part of the gradient stays a view of the slab's gradient, as in _ConcatFn."""
+
+    @staticmethod
+    def forward(ctx, x, *maps):
+        _require_gpu(x, *maps)
+        B, C, H, W = x.shape
+        n, Cb = len(maps), maps[0].shape[1]
+        if any(m.shape[0] != B or m.shape[1] != Cb or m.dtype != x.dtype for m in maps):
+            raise _lib.SdhipError("pyramid_upcat: the branch maps must share x's batch and dtype and one channel count")
+        xv, ldx = nhwc_view(x)
+        mv = [nhwc_view(m) for m in maps]
+        out, ldo = alloc_nhwc(B, C + n * Cb, H, W, x.dtype, x.device)
+        arg, keep = _lib.pyr_maps([(v, v.shape[2], v.shape[3], ld) for v, ld in mv])
+        if not try_call("sdhip_pyramid_upcat_fwd", ptr(xv), ldx, arg, n, ptr(out), ldo, B, H, W, C, Cb, dtype_code(x), stream_ptr()):
+            raise _Unfused()
+        ctx.cfg = (B, C, H, W, Cb, [(m.shape[2], m.shape[3]) for m in maps])
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        B, C, H, W, Cb, sizes = ctx.cfg
+        n = len(sizes)
+        need_x, need_m = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:])
+        g, ldg = nhwc_view(gy)
+        gms = [None] * n
+        if need_m:
+            gms = [empty_nhwc(B, Cb, h, w, g.dtype, g.device) for h, w in sizes]
+            tmp = torch.empty(B * H * Cb * sum(w for _, w in sizes), dtype=torch.float32, device=g.device)
+            arg, keep = _lib.pyr_maps([(t, h, w, Cb) for t, (h, w) in zip(gms, sizes)])
+            if not try_call("sdhip_pyramid_upcat_bwd", ptr(g), ldg, arg, n, ptr(tmp), B, H, W, C, Cb, dtype_code(g), stream_ptr()):
+                for j, (h, w) in enumerate(sizes):
+                    call("sdhip_resize_bwd", ptr(g[:, C + j * Cb:C + (j + 1) * Cb]), ldg, ptr(gms[j]), Cb, ptr(tmp), B, h, w, Cb, H, W,
+                         1, 0.0, 0.0, dtype_code(g), stream_ptr())
+        return (g[:, :C] if need_x else None,) + tuple(gms)
+
+
+def pyramid_upcat(x, maps):
+    """cat([x] + [bilinear upsample of each map to x's size], 1); None where the fused kernel does not apply (the caller
+    then composes interpolate + concat)."""
+    try:
+        return _PyramidUpcatFn.apply(x, *maps)
+    except _Unfused:
+        return None
+
+
 class _RepeatBatchFn(torch.autograd.Function):
     """x -> [x | x] along the batch (one tower's map fed to both halves of a batched pass): two copies into one NHWC
     buffer; the backward adds the two halves of the incoming gradient."""
