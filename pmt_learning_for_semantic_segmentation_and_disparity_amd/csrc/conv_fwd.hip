@@ -17,6 +17,7 @@
 #include "conv_common.h"
 #include "conv_fast.h"
 #include "conv_point.h"
+#include "conv_grow.h"
 #include "conv_band.h"
 #include "conv_gemm.h"
 #include "conv_thin.h"
@@ -663,6 +664,35 @@ int path_point(const ConvCall& c, const ConvPlan& d) {
   return launch_point(f, g.B, c.stream);
 }
 
+// ---- 3x3 split-K kernel (conv_grow.h): bf16 3x3 / stride 1 / pad 1 with an input prologue (given together with a
+//      statistics epilogue, or the consumer-side BatchNorm finalize) from 64 .. 256 channels into exactly 32: the conv2 of
+//      the DenseNet dense layers.  The map and grid limits are what was measured (tools/gpu_conv3x3_small.py, 16 images):
+//      see kGrowMaxMap / kGrowMaxWG and DESIGN.md §4.  A given prologue WITHOUT a statistics epilogue is an inference call
+//      and keeps the halo-tile kernel, for the reason written above path_point ----
+int path_grow(const ConvCall& c, const ConvPlan& d) {
+  const ConvGeom& g = c.g;
+  const SdhipDiag& dg = sdhip_diag();
+  if (!(c.dtype == SDHIP_BF16 && !c.bx && !c.addend && c.omul == 1 && (c.ps || (c.in_scale && c.stats)) && !c.bias && c.act == 0 && !c.accumulate &&
+        g.kh == 3 && g.kw == 3 && c.flat() && g.stride == 1 && g.dil == 1 && g.pad_t == 1 && g.pad_l == 1 && g.Ho == g.H && g.Wo == g.W &&
+        c.Cin % 32 == 0 && c.Cin >= 64 && c.Cin <= 256 && c.Cout == kGrowBN && (long)g.H * g.W <= kGrowMaxMap &&
+        (long)g.B * sdhip_cdiv(g.H, kGrowTH) * sdhip_cdiv(g.W, kGrowTW) <= kGrowMaxWG &&
+        d.vec_in && d.vec_out && (long)g.H * g.W * c.ldx < (1L << 31) && !dg.conv_generic && !dg.conv_no_grow))
+    return kNotTaken;
+  const ProStats* ps = c.ps;
+  GrowArgs f{};
+  f.x = c.x; f.wp = c.wp; f.y = c.y; f.in_scale = c.in_scale; f.in_shift = c.in_shift; f.stats = c.stats;
+  f.H = g.H; f.W = g.W; f.Cin = c.Cin; f.ldx = c.ldx; f.ldy = c.ldy; f.tiles_w = sdhip_cdiv(g.W, kGrowTW);
+  f.in_relu = c.in_relu; f.bpg = g.B / c.groups;
+  f.stats_ld = d.stats_ld; f.nrep = d.nrep; f.rep_stride = d.rep_stride;
+  if (ps) {
+    f.pin_stats = ps->stats; f.pin_ld = ps->ld; f.pin_nrep = ps->nrep; f.pin_groups = c.groups; f.pin_gamma = ps->gamma; f.pin_beta = ps->beta;
+    f.pin_scale = ps->scale; f.pin_shift = ps->shift; f.pin_mean = ps->mean; f.pin_invstd = ps->invstd; f.pin_rmean = ps->rmean; f.pin_rvar = ps->rvar;
+    f.pin_eps = ps->eps; f.pin_momentum = ps->momentum; f.pin_count = ps->count;
+    f.pend_stats = ps->pend; f.pin_fold = ps->fold; f.pend_ld = ps->pend_ld; f.pend_nrep = ps->pend_nrep; f.pend_c0 = ps->pend_c0; f.pend_n = ps->pend ? ps->pend_n : 0;
+  }
+  return launch_grow(f, g.B, c.stream);
+}
+
 // ---- fast path (conv_fast.h): 16-byte-aligned pixels on both sides, halo-tile mode.  It takes every variant (phase
 //      output, BatchNorm-backward epilogue, consumer-side BatchNorm finalize) ----
 int path_fast(const ConvCall& c, const ConvPlan& d) {
@@ -781,6 +811,7 @@ int conv2d_fwd_impl(const ConvCall& c) {
     if ((rc = path(c, d)) != kNotTaken) return rc;
   if (c.addend && !c.bx) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_add: only the persistent 5x5 kernel adds a second tensor in its epilogue (bf16, <= 64 channels, >= 192 tiles of 16x32)");
   if ((rc = path_point(c, d)) != kNotTaken) return rc;
+  if ((rc = path_grow(c, d)) != kNotTaken) return rc;
   if ((rc = path_fast(c, d)) != kNotTaken) return rc;
   if (c.omul != 1) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_phase: interleaved output needs the aligned fast path (ldx %% 8, ldy %% 4)");
   if (c.ps) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_bnpro: needs the aligned fast path (ldx %% 8, ldy %% 4, halo tile within LDS)");

@@ -38,6 +38,7 @@ static void diag_fill() {
   g_diag.conv_no_band = env_set("SDHIP_CONV_NO_BAND");
   g_diag.conv_no_band3 = env_set("SDHIP_CONV_NO_BAND3");
   g_diag.conv_no_point = env_set("SDHIP_CONV_NO_POINT");
+  g_diag.conv_no_grow = env_set("SDHIP_CONV_NO_GROW");
   g_diag.wgrad_generic = env_set("SDHIP_WGRAD_GENERIC");
   g_diag.wgrad_no_pack = env_set("SDHIP_WGRAD_NO_PACK");
   g_diag.wgrad_force_pack = env_set("SDHIP_WGRAD_FORCE_PACK");

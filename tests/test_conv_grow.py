@@ -1,0 +1,176 @@
+"""The 3x3 split-K convolution of csrc/conv_grow.h (bf16 3x3 / stride 1 / pad 1 with an input prologue, 64 .. 256 channels
+into 32, on small maps: conv2 of the DenseNet dense layers), through sdhip_conv2d_fwd (given in_scale / in_shift) and
+sdhip_conv2d_fwd_bnpro (the consumer-side BatchNorm finalize), against the float64 references and bounds of
+tests/test_conv_kernels.py.
+
+Without a GPU: grow_taken() mirrors path_grow of csrc/conv_fwd.hip term by term; it names every case below, rejects each
+single violation of the predicate and every case of the tables of test_conv_kernels.py (whose tile assumptions therefore hold).
+With a GPU: x and y are channel slices of NaN-filled slabs, so a NaN in y is a padding lane, a dead channel or a pixel past
+the image that reached an MFMA; the draw keeps |shift| >= 0.25 with both signs of scale and shift, so a padding pixel that
+was normalised instead of zeroed is far outside the bound.  Shapes are the smallest at which the kernel takes another
+route: fewer / uneven / most (tap, k-step) units per wave and a k-step tail inside a 64-channel weight row (Cin 64, 128,
+160, 256), two tiles that both touch the border (8x16), interior halo rows shared between tiles (16x32), one ragged tile
+with dead pixel rows (3x5, 5x13), a halo that is all padding (1x1), a one-column ragged tile (4x17), the group taken from
+the image index (B 4 / two groups, B 2 / one).
+
+The statistics bound is test_conv_kernels.stats_bound with a (4, 16) tile: the kernel sums 64 stored values in f32 (16 by
+DPP, the four tile rows through LDS) before its f64 atomic.
+"""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import convops_ref as CR  # noqa: E402
+import rowops_ref as R  # noqa: E402
+import test_conv_kernels as K  # noqa: E402
+from rowops_ref import U32, check  # noqa: E402
+from test_conv_kernels import (BF16, BNPRO_COMBOS, EPS32, F32, MOM32, P, StatBuf, Table, Vol, bits, check_stats, code, dev, draw, draw_bnpro,  # noqa: E402
+                               fwd_ref, gpu_fwd, isbf, mk, pro_err, run, st)
+
+NO_GROW = {"SDHIP_CONV_NO_GROW": "1"}
+SLICE = (64, 160)       # y as channels [64, 96) of a 160-channel slab, as a dense layer writes its growth channels
+GROW_MAX_MAP, GROW_MAX_WG = 2048, 512     # kGrowMaxMap, kGrowMaxWG of csrc/conv_grow.h
+
+
+def gr(name, **kw):
+    base = dict(kh=3, kw=3, B=4, H=8, W=16, Cin=128, Cout=32, pro="relu", groups=2, lx="slab8", ly=SLICE, stats=(2, 1))
+    base.update(kw)
+    return mk(name, **base)
+
+
+CASES = [gr("cin%d" % ci, Cin=ci) for ci in (64, 128, 160, 256)]
+CASES += [gr("map16x32", H=16, W=32, B=2, groups=1, stats=(3, 0)), gr("map3x5", H=3, W=5, Cin=160), gr("map5x13", H=5, W=13, Cin=64),
+          gr("map1x1", H=1, W=1), gr("map4x17", H=4, W=17, Cin=256), gr("G1_B2", groups=1, B=2, stats=(1, 0)),
+          gr("dense", ly="dense", Cin=160), gr("lin", pro="lin", Cin=160), gr("lin_map5x13", pro="lin", H=5, W=13, ly="dense")]
+BYNAME = {c.name: c for c in CASES}
+
+
+def _lay(lay, C):
+    return R.layout(lay, C) if isinstance(lay, str) else lay
+
+
+def grow_taken(c, dtype, env=None):
+    """Mirror of path_grow (csrc/conv_fwd.hip)."""
+    env = dict(c.env, **(env or {}))
+    Cin = K.cin_of(c, dtype)
+    (kx, ldx), (ky, ldy) = _lay(c.lx, Cin), _lay(c.ly, c.Cout)
+    return bool(isbf(dtype) and c.pro is not None and c.stats is not None and not c.bias and c.act == 0 and not c.acc and
+                c.kh == 3 and c.kw == 3 and c.kd == 1 and c.D == 1 and c.Do == 1 and c.stride == 1 and c.dil == 1 and
+                c.pad_t == 1 and c.pad_l == 1 and c.Ho == c.H and c.Wo == c.W and
+                Cin % 32 == 0 and 64 <= Cin <= 256 and c.Cout == 32 and c.H * c.W <= GROW_MAX_MAP and
+                c.B * K.cdiv(c.H, 4) * K.cdiv(c.W, 16) <= GROW_MAX_WG and
+                ldx % 8 == 0 and (kx * 2) % 16 == 0 and ldy % 4 == 0 and (ky * 2) % 8 == 0 and c.H * c.W * ldx < 2 ** 31 and
+                "SDHIP_CONV_NO_GROW" not in env and "SDHIP_CONV_GENERIC" not in env)
+
+
+def test_grow_predicate():
+    for c in CASES:
+        assert grow_taken(c, BF16), c.name
+        assert not grow_taken(c, F32), c.name
+        assert not grow_taken(c, BF16, NO_GROW) and not grow_taken(c, BF16, K.GENERIC_ENV), c.name
+    for tag, kw in (("k1", dict(kh=1, kw=1)), ("k5", dict(kh=5, kw=5)), ("stride2", dict(stride=2)), ("dil2", dict(dil=2)),
+                    ("cin48", dict(Cin=48)), ("cin288", dict(Cin=288)), ("cout24", dict(Cout=24)), ("cout64", dict(Cout=64)),
+                    ("nopro", dict(pro=None)), ("nostats", dict(stats=None)), ("bias", dict(bias=1)), ("act", dict(act=1)), ("acc", dict(acc=1)),
+                    ("lx_ldodd", dict(lx="ldodd")), ("ly_ldodd", dict(ly="ldodd")), ("lx_misal", dict(lx="misal")), ("ly_misal", dict(ly="misal")),
+                    ("map48x48", dict(H=48, W=48, B=2, groups=1)), ("grid", dict(B=2 * GROW_MAX_WG, H=1, W=1))):
+        assert not grow_taken(gr(tag, **kw), BF16), tag
+    pad0 = gr("pad0")
+    pad0.update(pad_t=0, pad_l=0)
+    assert not grow_taken(pad0, BF16)
+    # the headline step's blocks (16 images): what was measured faster is taken
+    for tag, H, W in (("block4", 8, 16), ("block3", 16, 32), ("block2", 32, 64)):      # block 2: 512 workgroups, the limit
+        assert grow_taken(gr(tag, B=16, H=H, W=W), BF16), tag
+    assert not grow_taken(gr("block1", B=16, H=64, W=128), BF16) and not grow_taken(gr("block2_B32", B=32, H=32, W=64), BF16)
+    for dtype in (F32, BF16):
+        for c in K.FWD:
+            assert not grow_taken(c, dtype), c.name
+        for Cin in (32, 96, 160):        # the shapes of test_conv_kernels.test_conv2d_fwd_bnpro
+            for kh in (1, 3):
+                assert not grow_taken(mk("bnpro", kh=kh, kw=kh, Cin=Cin, Cout=24, pro="relu", lx="slab8", ly="slab8", stats=(3, 1)), dtype)
+
+
+# =========================================================================== GPU: sdhip_conv2d_fwd with in_scale / in_shift
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", [c.name for c in CASES])
+def test_conv_grow_fwd(name):
+    """New kernel and the kernel it replaces (SDHIP_CONV_NO_GROW) against the same reference and against each other: y within
+    the bound with no element excluded, the slab around y untouched, the statistics the sums of the stored y; a second launch
+    of the new kernel gives the same y bits."""
+    c = BYNAME[name]
+    d = draw(c, BF16)
+    assert np.abs(d.sh).min() >= 0.25 and (d.sc < 0).any() and (d.sc > 0).any() and (d.sh < 0).any() and (d.sh > 0).any()
+    ref, bound = fwd_ref(c, BF16, d)
+    got, ybits = {}, {}
+    for tag, env in (("grow", {}), ("fast", NO_GROW), ("grow again", {})):
+        y, sb = gpu_fwd(c, BF16, d, env)
+        label = "grow %s %s" % (name, tag)
+        got[tag] = y.np()
+        check(label, got[tag], ref, bound)
+        assert y.pads_intact(), label
+        if sb:
+            check_stats(label + " stats", sb, got[tag], c.groups, (4, 16))
+        ybits[tag] = bits(y.v)
+    assert torch.equal(ybits["grow"], ybits["grow again"]), "grow %s: y differs between two launches" % name
+    check("grow %s new against old" % name, got["grow"], got["fast"], bound)
+
+
+# =========================================================================== GPU: sdhip_conv2d_fwd_bnpro
+@pytest.mark.gpu
+@pytest.mark.parametrize("Cin", [64, 128, 256])
+def test_conv_grow_bnpro(Cin):
+    """The assertions of test_conv_kernels.test_conv2d_fwd_bnpro on the shapes that take the new kernel (3x3, Cout 32)."""
+    from test_bn_kernels import b_finalize
+    dtype, kh, pad = BF16, 3, 1
+    for (G, nrep, pend_nrep, running, out_stats) in BNPRO_COMBOS:
+        d = draw_bnpro(kh, Cin, G, nrep, pend_nrep, running, dtype, Cout=32)
+        assert grow_taken(mk("bnpro", kh=3, kw=3, B=d.B, H=d.H, W=d.W, Cin=Cin, Cout=32, pro="relu", groups=G, lx="slab8", ly="slab8",
+                             stats=(3, 1)), dtype)      # (the finalize form needs no statistics epilogue: the mirror speaks of the given-prologue form)
+        c0 = Cin - 32
+        r = CR.bnpro(d.x, d.w, d.in_stats, d.count, d.gamma, d.beta, d.rm0, d.rv0, EPS32, MOM32, G, d.pend, c0, pad, pad)
+        S = r["in_stats"].sum(0)[:, :, :Cin] if pend_nrep else R.replica_sum(d.in_stats)
+        bf_ = b_finalize(S, d.count, d.gamma, d.beta, d.rm0, d.rv0)
+        x = Vol((d.B, 1, d.H, d.W, Cin), dtype, "slab8", d.x)
+        y = Vol((d.B, 1, d.H, d.W, d.Cout), dtype, "slab8")
+        wp = dev(CR.pack_conv(d.w, isbf(dtype)), dtype)
+        ld_in = Cin + 3
+        ins = torch.full((nrep, G, 2, ld_in), -7.25, dtype=torch.float64, device="cuda")
+        ins[..., :Cin] = torch.from_numpy(d.in_stats).cuda()
+        ins0 = ins.clone()
+        pend = None
+        if pend_nrep:
+            pend = torch.full((pend_nrep, G, 2, 37), float('nan'), dtype=torch.float64, device="cuda")
+            pend[..., :32] = torch.from_numpy(d.pend).cuda()
+        gam, bet = Table(d.gamma), Table(d.beta)
+        rm, rv = (Table(d.rm0), Table(d.rv0)) if running else (None, None)
+        outs = [torch.full((G * Cin + 16,), float('nan'), dtype=torch.float32, device="cuda") for _ in range(4)]
+        sb = StatBuf(3, G, d.Cout, 1) if out_stats else None
+        run("sdhip_conv2d_fwd_bnpro", x.p, P(wp), y.p, sb.p if sb else None, sb.ld if sb else 0, 3 if sb else 1,
+            P(ins), ld_in, nrep, P(pend), 37, max(pend_nrep, 1), c0, 32 if pend_nrep else 0, gam.p, bet.p,
+            rm.p if rm else None, rv.p if rv else None, P(outs[0], 32), P(outs[1], 32), P(outs[2], 32), P(outs[3], 32),
+            ctypes.c_double(d.count), ctypes.c_float(EPS32), ctypes.c_float(MOM32),
+            d.B, d.H, d.W, Cin, x.ld, d.H, d.W, d.Cout, y.ld, kh, kh, pad, pad, G, code(dtype))
+        label = "grow bnpro Cin%d G%d nrep%d pend%d" % (Cin, G, nrep, pend_nrep)
+        for key, o in zip(("scale", "shift", "mean", "invstd"), outs):
+            check(label + " " + key, o[8:8 + G * Cin].double().cpu().numpy().reshape(G, Cin), r[key], bf_[key])
+            assert bool(torch.isnan(o[:8]).all() and torch.isnan(o[8 + G * Cin:]).all())
+        if running:
+            check(label + " rmean", rm.t[8:8 + Cin].double().cpu().numpy(), r["rmean"], bf_["rmean"])
+            check(label + " rvar", rv.t[8:8 + Cin].double().cpu().numpy(), r["rvar"], bf_["rvar"])
+        want = ins0.clone()
+        if pend_nrep:
+            folded = ins[0, :, :, c0:Cin].cpu().numpy()
+            check(label + " fold", folded, d.pend.sum(0), 2.0 ** -50 * np.abs(d.pend).sum(0) + 1e-300)
+            want[0, :, :, c0:Cin] = ins[0, :, :, c0:Cin]
+        assert torch.equal(bits(ins), bits(want)), label + ": in_stats outside the folded channels"
+        A = CR.corr(np.abs(CR.prologue(d.x, r["scale"], r["shift"], 1, G)), np.abs(d.w), pad_t=pad, pad_l=pad)
+        e = (Cin * kh * kh + 1) * U32 * A + CR.corr(pro_err(d.x, r["scale"], r["shift"], G, dtype, bf_["scale"], bf_["shift"]), np.abs(d.w), pad_t=pad, pad_l=pad)
+        got = y.np()
+        check(label + " y", got, r["y"], e + st(r["y"], dtype, e) + 1e-300)
+        assert y.pads_intact(), label
+        if sb:
+            check_stats(label + " out_stats", sb, got, G, (4, 16))
