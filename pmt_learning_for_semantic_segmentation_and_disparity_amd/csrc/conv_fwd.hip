@@ -18,6 +18,7 @@
 #include "conv_fast.h"
 #include "conv_point.h"
 #include "conv_grow.h"
+#include "conv_mid.h"
 #include "conv_band.h"
 #include "conv_gemm.h"
 #include "conv_thin.h"
@@ -693,6 +694,32 @@ int path_grow(const ConvCall& c, const ConvPlan& d) {
   return launch_grow(f, g.B, c.stream);
 }
 
+// ---- whole-weight-set kernel (conv_mid.h): bf16 3x3 / stride 1 / pad 1, 64 -> 64, no prologue, bias, activation or
+//      accumulation: the decoder blocks on the 1/4-resolution maps, forward (plain or with the statistics epilogue) and data
+//      gradient (the BatchNorm-backward epilogue of sdhip_conv2d_fwd_bnbwd mode 0, with or without its addend).  Same y bits
+//      as the halo-tile kernel.  The map and grid limits are what was measured faster (tools/gpu_conv3x3_mid.py, 8 images):
+//      see kMidMinMap / kMidMaxMap / kMidMaxWG and DESIGN.md section 4; SDHIP_TUNE_MID_* replace them (tests) ----
+int path_mid(const ConvCall& c, const ConvPlan& d) {
+  const ConvGeom& g = c.g;
+  const SdhipDiag& dg = sdhip_diag();
+  const long min_map = dg.tune_mid_min_map > 0 ? dg.tune_mid_min_map : kMidMinMap, max_map = dg.tune_mid_max_map > 0 ? dg.tune_mid_max_map : kMidMaxMap;
+  const long max_wg = dg.tune_mid_max_wg > 0 ? dg.tune_mid_max_wg : kMidMaxWG;
+  if (!(c.dtype == SDHIP_BF16 && g.kh == 3 && g.kw == 3 && c.flat() && g.stride == 1 && g.dil == 1 && g.pad_t == 1 && g.pad_l == 1 &&
+        g.Ho == g.H && g.Wo == g.W && c.Cin == kMidBN && c.Cout == kMidBN && !c.in_scale && !c.ps && !c.bias && c.act == 0 && !c.accumulate &&
+        c.omul == 1 && (c.bx ? c.bx_mode == 0 : !c.addend) && (long)g.H * g.W >= min_map && (long)g.H * g.W <= max_map &&
+        (long)g.B * sdhip_cdiv(g.H, kMidTH) * sdhip_cdiv(g.W, kMidTW) <= max_wg &&
+        d.vec_in && d.vec_out && (long)g.H * g.W * c.ldx < (1L << 31) && !dg.conv_generic && !dg.conv_no_mid))
+    return kNotTaken;
+  MidArgs f{};
+  f.x = c.x; f.wp = c.wp; f.y = c.y; f.stats = c.stats;
+  f.H = g.H; f.W = g.W; f.ldx = c.ldx; f.ldy = c.ldy; f.tiles_w = sdhip_cdiv(g.W, kMidTW);
+  f.bpg = g.B / c.groups;
+  f.stats_ld = d.stats_ld; f.nrep = d.nrep; f.rep_stride = d.rep_stride;
+  f.bx = c.bx; f.bsc = c.bsc; f.bsh = c.bsh; f.ldbx = c.ldbx;
+  f.res = c.bx ? c.addend : nullptr; f.ldres = c.ldadd;
+  return launch_mid(f, g.B, c.stream);
+}
+
 // ---- fast path (conv_fast.h): 16-byte-aligned pixels on both sides, halo-tile mode.  It takes every variant (phase
 //      output, BatchNorm-backward epilogue, consumer-side BatchNorm finalize) ----
 int path_fast(const ConvCall& c, const ConvPlan& d) {
@@ -812,6 +839,7 @@ int conv2d_fwd_impl(const ConvCall& c) {
   if (c.addend && !c.bx) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_add: only the persistent 5x5 kernel adds a second tensor in its epilogue (bf16, <= 64 channels, >= 192 tiles of 16x32)");
   if ((rc = path_point(c, d)) != kNotTaken) return rc;
   if ((rc = path_grow(c, d)) != kNotTaken) return rc;
+  if ((rc = path_mid(c, d)) != kNotTaken) return rc;
   if ((rc = path_fast(c, d)) != kNotTaken) return rc;
   if (c.omul != 1) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_phase: interleaved output needs the aligned fast path (ldx %% 8, ldy %% 4)");
   if (c.ps) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_bnpro: needs the aligned fast path (ldx %% 8, ldy %% 4, halo tile within LDS)");

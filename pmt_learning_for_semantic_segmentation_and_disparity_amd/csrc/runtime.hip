@@ -39,6 +39,7 @@ static void diag_fill() {
   g_diag.conv_no_band3 = env_set("SDHIP_CONV_NO_BAND3");
   g_diag.conv_no_point = env_set("SDHIP_CONV_NO_POINT");
   g_diag.conv_no_grow = env_set("SDHIP_CONV_NO_GROW");
+  g_diag.conv_no_mid = env_set("SDHIP_CONV_NO_MID");
   g_diag.wgrad_generic = env_set("SDHIP_WGRAD_GENERIC");
   g_diag.wgrad_no_pack = env_set("SDHIP_WGRAD_NO_PACK");
   g_diag.wgrad_force_pack = env_set("SDHIP_WGRAD_FORCE_PACK");
@@ -55,6 +56,9 @@ static void diag_fill() {
   g_diag.tune_fused_blocks = env_int("SDHIP_TUNE_FUSED_BLOCKS", 768);
   g_diag.tune_gemm_dbg = env_int("SDHIP_TUNE_GEMM_DBG", 0);
   g_diag.tune_band_dbg = env_int("SDHIP_TUNE_BAND_DBG", 0);
+  g_diag.tune_mid_min_map = env_int("SDHIP_TUNE_MID_MIN_MAP", 0);
+  g_diag.tune_mid_max_map = env_int("SDHIP_TUNE_MID_MAX_MAP", 0);
+  g_diag.tune_mid_max_wg = env_int("SDHIP_TUNE_MID_MAX_WG", 0);
   g_diag.tune_atomic_tbs = getenv("SDHIP_TUNE_ATOMIC_TBS") ? atof(getenv("SDHIP_TUNE_ATOMIC_TBS")) : 1.3;
   g_diag.tune_wg1_tile = getenv("SDHIP_TUNE_WG1_TILE") ? atof(getenv("SDHIP_TUNE_WG1_TILE")) : 1.0;
   g_diag_init = true;
