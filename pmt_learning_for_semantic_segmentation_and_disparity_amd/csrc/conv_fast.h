@@ -107,6 +107,19 @@ template <> struct LdsRow<1> {
 // global load at all inside its stage loop (hipcc would wait for it — and with it for the DMA — in the MFMA loop).
 // BX: the BatchNorm-backward-sums epilogue (FastArgs::bx) — an instantiation of its own, because its extra live values
 // push the 8x32x64 form from 244 to 264 VGPRs, i.e. from two workgroups per CU to one, for EVERY launch of that form.
+// The BX epilogue works in batches of kBxTiles output-channel tiles (16 channels each): a batch is scale / shift of those
+// tiles plus u (and the addend) of every pixel tile of the wave — 8 + 4 * NT_PIX (8 * NT_PIX with an addend) registers per
+// channel tile.  kBxSets = 2 keeps two register sets: batch i + 1 is in flight while batch i is consumed.
+//   4 x 16 (one pixel tile):   one batch of all tiles; BN 128 two batches of four, one after the other — all eight at once
+//                              (96 operand registers) take the form from three workgroups per CU to two, which measured slower
+//   8 x 32 (four pixel tiles): two sets of one tile (BN 128: of two)
+// kBxFront forms issue batch 0 in front of the stage loop and hold it across the loop; the others issue it behind the last
+// MFMA.  Chosen per form from tools/gpu_conv_bx.py's table and the register budget: the narrow 4 x 16
+// forms, which run the smallest maps, gain from the early issue and stay under 128 registers with it.
+template <int TH, int BN, int KS> constexpr int kBxTiles = TH == 4 ? (BN == 128 ? 4 : BN / 16) : (BN == 128 ? 2 : 1);
+template <int TH, int BN, int KS> constexpr int kBxSets = TH == 4 ? 1 : 2;
+template <int TH, int BN, int KS> constexpr bool kBxFront = (TH == 4 && BN <= 32);
+
 template <typename T, int TH, int TW, int BN, int KS, bool DMA, bool BX = false>
 __global__ __launch_bounds__(256) void conv_fast_kernel(const FastArgs p) {
   constexpr int V = Chunk<T>::N;          // elements per 16 bytes
@@ -409,6 +422,66 @@ __global__ __launch_bounds__(256) void conv_fast_kernel(const FastArgs p) {
     }
   };
 
+  // ---- BX: the operands of the BatchNorm-backward epilogue (scale / shift, u, the addend), as BATCHES of plain loads ----
+  // The loads of a batch (kBxTiles above) are straight-line — no per-lane condition stands in front of one, so hipcc issues
+  // them back to back and waits once: a pixel past the image loads the nearest pixel inside it, a channel group at or past
+  // Cout a group below it (Cout % 4 == 0); such lanes get gm = 0 and a predicated store.  scale / shift are loaded once per
+  // channel tile.
+  // Addresses: a pixel tile is one image row per wave, so the row's base is a scalar and a lane adds a 32-bit byte offset
+  // (column, channel group); the tiles entirely below Cout share one offset (the loads differ in their immediate), every
+  // other tile takes the offset of the first such tile, clamped.  No 64-bit address per load: at BN 128 those cost 64 registers.
+  // (The offsets are 32-bit: one image row of u / of the addend is taken to stay below 2^31 elements, as the host checks for x's whole image.)
+  constexpr bool BXF = BX && kBxFront<TH, BN, KS>;
+  constexpr int MB = BX ? kBxTiles<TH, BN, KS> : NT_CO, NCH = NT_CO / MB;   // tiles per batch, batches
+  constexpr int NBS = (BX && NCH > 1) ? kBxSets<TH, BN, KS> : 1;
+  static_assert(NT_CO % MB == 0 && (NBS == 1 || NBS == 2), "whole batches; one or two register sets");
+  // wide forms: a lane's two sums of a channel tile go to LDS as soon as they are final, instead of 8 * NT_CO registers of
+  // them; the narrow forms keep them in registers and need no barrier in front of the epilogue
+  constexpr bool BXS = BX && BN >= 64;
+  u32x2 eu[NBS][MB][NT_PIX], er[NBS][MB][NT_PIX];
+  f32x4 esc[NBS][MB], esh[NBS][MB];
+  // (everything the batches need is computed inside the lambda: the other instantiations must not change by a single instruction)
+  auto bx_issue = [&](int bi, int set) {   // batch bi: channel tiles bi * MB .. + MB - 1
+    const int m0 = bi * MB;
+    const int bx_wave = __builtin_amdgcn_readfirstlane(wave);
+    const long bx_img = (long)blockIdx.z * p.Ho * p.Wo;   // omul == 1
+    const bool bx_add = p.res != nullptr;                 // uniform; mode 1 always has its addend
+    const int bx_tf = min(NT_CO, (p.Cout - n0) >> 4);     // uniform: output-channel tiles entirely below Cout
+    const int bx_cl = n0 + 4 * lg, bx_ct = min(bx_cl + bx_tf * 16, p.Cout - 4);
+    auto bx_off = [&](int mi, unsigned full, unsigned tail, int bytes) -> unsigned { return mi < bx_tf ? full + mi * 16 * bytes : tail; };
+    const char* const scb = reinterpret_cast<const char*>(p.bsc + (long)grp * p.Cout);
+    const char* const shb = reinterpret_cast<const char*>(p.bsh + (long)grp * p.Cout);
+#pragma unroll
+    for (int k = 0; k < MB; ++k) {
+      const unsigned o = bx_off(m0 + k, bx_cl * 4u, bx_ct * 4u, 4);
+      esc[set][k] = *reinterpret_cast<const f32x4*>(scb + o);
+      esh[set][k] = *reinterpret_cast<const f32x4*>(shb + o);
+    }
+#pragma unroll
+    for (int ni = 0; ni < NT_PIX; ++ni) {
+      const int pt = bx_wave * NT_PIX + ni;
+      const long rowc = bx_img + (long)min(oh0 + pt / TWT, p.Ho - 1) * p.Wo;    // scalar
+      const int owc = min(ow0 + (pt % TWT) * 16 + l15, p.Wo - 1);
+      const char* const ur = reinterpret_cast<const char*>((const T*)p.bx + rowc * p.ldbx);
+      const unsigned uf = (unsigned)(owc * p.ldbx + bx_cl) * 2u, ut = (unsigned)(owc * p.ldbx + bx_ct) * 2u;
+#pragma unroll
+      for (int k = 0; k < MB; ++k) eu[set][k][ni] = *reinterpret_cast<const u32x2*>(ur + bx_off(m0 + k, uf, ut, 2));
+    }
+    if (bx_add) {
+#pragma unroll
+      for (int ni = 0; ni < NT_PIX; ++ni) {
+        const int pt = bx_wave * NT_PIX + ni;
+        const long rowc = bx_img + (long)min(oh0 + pt / TWT, p.Ho - 1) * p.Wo;
+        const int owc = min(ow0 + (pt % TWT) * 16 + l15, p.Wo - 1);
+        const char* const rr = reinterpret_cast<const char*>((const T*)p.res + rowc * p.ldres);
+        const unsigned rf = (unsigned)(owc * p.ldres + bx_cl) * 2u, rt = (unsigned)(owc * p.ldres + bx_ct) * 2u;
+#pragma unroll
+        for (int k = 0; k < MB; ++k) er[set][k][ni] = *reinterpret_cast<const u32x2*>(rr + bx_off(m0 + k, rf, rt, 2));
+      }
+    }
+  };
+  if constexpr (BXF) bx_issue(0, 0);
+
   // the first weights (LDS-DMA) and, for small tiles, the raw halo loads go out BEFORE the consumer-side finalize below: they
   // do not depend on it and cover its round trips to the statistics
   w_issue(0, 0, wl0);
@@ -509,6 +582,7 @@ __global__ __launch_bounds__(256) void conv_fast_kernel(const FastArgs p) {
   // ---- epilogue: bias / activation / accumulate / store / BN statistics ----
   // Everything wave-uniform (bias? activation? interior tile?) is decided once, outside the per-tile code, so the
   // common case — interior tile, plain store — is straight-line: 4 VALU + one 8/16-byte store per 16x16 output tile.
+  if constexpr (!BX) {   // (a BX launch has neither bias nor activation)
   if (p.bias) {
 #pragma unroll
     for (int mi = 0; mi < NT_CO; ++mi) {
@@ -539,6 +613,7 @@ __global__ __launch_bounds__(256) void conv_fast_kernel(const FastArgs p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[mi][ni][r] = 1.f / (1.f + __expf(-acc[mi][ni][r]));
   }
+  }
 
   float s1[NT_CO][4], s2[NT_CO][4];
 #pragma unroll
@@ -554,57 +629,76 @@ __global__ __launch_bounds__(256) void conv_fast_kernel(const FastArgs p) {
   //  together, which would cost ~100 VGPRs — a wave of occupancy — in every launch of this kernel)
   const bool interior = oh0 + TH <= p.Ho && ow0 + TW <= p.Wo && n0 + BN <= p.Cout && !p.accumulate;   // wave-uniform
   if constexpr (BX) {   // host: bx / stats set, bf16, Cout % 4 == 0, omul == 1, no accumulate / bias / activation
-    {
-    const T* const ub = (const T*)p.bx + zimg * p.Ho * p.Wo * p.ldbx;
-    const T* const rb = (const T*)p.res + zimg * p.Ho * p.Wo * p.ldres;
+    // one batch: everything but the store is select, not branch, so that no load of the NEXT batch ends up behind a lane's
+    // condition.  A lane adds up its pixel tiles ni ascending, as it always did (a lane outside the result adds gm = 0);
+    // its two sums of a channel tile are then final (BXS: and go to LDS at once).
+    float* const red = reinterpret_cast<float*>(smem);  // [4 waves][2][BN], as below
+    auto bx_consume = [&](int bi, int set) {
 #pragma unroll
-    for (int mi = 0; mi < NT_CO; ++mi) {
-      const int co = n0 + mi * 16 + 4 * lg;
-      const bool cok = co < p.Cout;
-      f32x4 sc = f32x4{0.f, 0.f, 0.f, 0.f}, sh = sc;
-      if (cok) {
-        sc = *reinterpret_cast<const f32x4*>(p.bsc + (long)grp * p.Cout + co);
-        sh = *reinterpret_cast<const f32x4*>(p.bsh + (long)grp * p.Cout + co);
-      }
+      for (int k = 0; k < MB; ++k) {
+        const int mi = bi * MB + k, co = n0 + mi * 16 + 4 * lg;
+        const f32x4 sc = esc[set][k], sh = esh[set][k];
+        float t1[4] = {0.f, 0.f, 0.f, 0.f}, t2[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ni = 0; ni < NT_PIX; ++ni) {
-        const int pt = pt0 + ni;
-        const int oh = oh0 + pt / TWT, ow = ow0 + (pt % TWT) * 16 + l15;
-        if (cok && oh < p.Ho && ow < p.Wo) {
-          const long pix = (long)oh * p.Wo + ow;
-          const u32x2 uu = *reinterpret_cast<const u32x2*>(ub + pix * p.ldbx + co);
+        for (int ni = 0; ni < NT_PIX; ++ni) {
+          const int pt = pt0 + ni;
+          const int oh = oh0 + pt / TWT, ow = ow0 + (pt % TWT) * 16 + l15;
+          const bool ok = oh < p.Ho && ow < p.Wo && co < p.Cout;
+          T* const yp = yb + ((long)oh * p.Wo + ow) * p.ldy + co;
+          const u32x2 uu = eu[set][k][ni];
           f32x4 v = acc[mi][ni];
           const float u4[4] = {bflo(uu[0]), bfhi(uu[0]), bflo(uu[1]), bfhi(uu[1])};
           if (p.bx_mode == 1) {                 // uniform: mask and scale the convolution's value, then add it to res
-            const u32x2 rr = *reinterpret_cast<const u32x2*>(rb + pix * p.ldres + co);
+            const u32x2 rr = er[set][k][ni];
             const float r4[4] = {bflo(rr[0]), bfhi(rr[0]), bflo(rr[1]), bfhi(rr[1])};
             float o4[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              const float gm = fmaf(u4[r], sc[r], sh[r]) > 0.f ? v[r] : 0.f;
-              s1[mi][r] = fmaf(gm, u4[r], s1[mi][r]);
-              s2[mi][r] += gm;
+              const float gm = (ok && fmaf(u4[r], sc[r], sh[r]) > 0.f) ? v[r] : 0.f;
+              t1[r] = fmaf(gm, u4[r], t1[r]);
+              t2[r] += gm;
               o4[r] = fmaf(gm, sc[r], r4[r]);
             }
-            *reinterpret_cast<u32x2*>(yb + pix * p.ldy + co) = u32x2{pack2bf(o4[0], o4[1]), pack2bf(o4[2], o4[3])};
+            if (ok) *reinterpret_cast<u32x2*>(yp) = u32x2{pack2bf(o4[0], o4[1]), pack2bf(o4[2], o4[3])};
           } else {
-          if (p.res) {                          // uniform
-            const u32x2 rr = *reinterpret_cast<const u32x2*>(rb + pix * p.ldres + co);
-            v += f32x4{bflo(rr[0]), bfhi(rr[0]), bflo(rr[1]), bfhi(rr[1])};
-          }
-          const u32x2 o = u32x2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
-          *reinterpret_cast<u32x2*>(yb + pix * p.ldy + co) = o;
-          const float g4[4] = {bflo(o[0]), bfhi(o[0]), bflo(o[1]), bfhi(o[1])};
+            if (p.res) {                        // uniform
+              const u32x2 rr = er[set][k][ni];
+              v += f32x4{bflo(rr[0]), bfhi(rr[0]), bflo(rr[1]), bfhi(rr[1])};
+            }
+            const u32x2 o = u32x2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+            if (ok) *reinterpret_cast<u32x2*>(yp) = o;
+            const float g4[4] = {bflo(o[0]), bfhi(o[0]), bflo(o[1]), bfhi(o[1])};
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float gm = fmaf(u4[r], sc[r], sh[r]) > 0.f ? g4[r] : 0.f;
-            s1[mi][r] = fmaf(gm, u4[r], s1[mi][r]);
-            s2[mi][r] += gm;
+            for (int r = 0; r < 4; ++r) {
+              const float gm = (ok && fmaf(u4[r], sc[r], sh[r]) > 0.f) ? g4[r] : 0.f;
+              t1[r] = fmaf(gm, u4[r], t1[r]);
+              t2[r] += gm;
+            }
           }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if constexpr (BXS) {
+            const float a = row16_sum(t1[r]), c2 = row16_sum(t2[r]);   // over the 16 pixels of the MFMA tile (DPP)
+            if (l15 == 0) {
+              const int m = mi * 16 + 4 * lg + r;
+              red[(wave * 2 + 0) * BN + m] = a;
+              red[(wave * 2 + 1) * BN + m] = c2;
+            }
+          } else {
+            s1[mi][r] = t1[r];
+            s2[mi][r] = t2[r];
           }
         }
       }
-    }
+    };
+    if constexpr (!BXF) bx_issue(0, 0);
+    if constexpr (BXS) __syncthreads();   // all fragment reads done: LDS is reused for the cross-wave reduction (behind the issue: the wait overlaps the loads)
+#pragma unroll
+    for (int bi = 0; bi < NCH; ++bi) {
+      if (NBS == 2 && bi + 1 < NCH) bx_issue(bi + 1, (bi + 1) & 1);
+      bx_consume(bi, NBS == 2 ? bi & 1 : 0);
+      if (NBS == 1 && bi + 1 < NCH) bx_issue(bi + 1, 0);
     }
   }
   if constexpr (BX) {
@@ -683,8 +777,9 @@ __global__ __launch_bounds__(256) void conv_fast_kernel(const FastArgs p) {
   }
 
   if (p.stats) {  // uniform
-    __syncthreads();  // all fragment reads done: LDS is reused for the cross-wave reduction
     float* red = reinterpret_cast<float*>(smem);  // [4 waves][2][BN]
+    if constexpr (!(BX && BN >= 64)) {   // (the wide BX forms have written `red` in their epilogue)
+    __syncthreads();  // all fragment reads done: LDS is reused for the cross-wave reduction
 #pragma unroll
     for (int mi = 0; mi < NT_CO; ++mi) {
 #pragma unroll
@@ -696,6 +791,7 @@ __global__ __launch_bounds__(256) void conv_fast_kernel(const FastArgs p) {
           red[(wave * 2 + 1) * BN + m] = c2;
         }
       }
+    }
     }
     __syncthreads();
     if (tid < 2 * BN) {
