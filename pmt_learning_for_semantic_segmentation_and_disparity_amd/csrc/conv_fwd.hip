@@ -591,8 +591,12 @@ int path_gemm(const ConvCall& c, const ConvPlan& d) {
 // ---- persistent whole-CU kernel (conv_band.h), bf16, weights resident in LDS.  What its 2-D and 3-D forms share: ----
 bool band_common_ok(const ConvCall& c) {
   const ConvGeom& g = c.g;
-  return !c.ps && !c.bx && c.omul == 1 && c.dtype == SDHIP_BF16 && g.stride == 1 && g.dil == 1 && !c.in_scale &&
-         !((c.accumulate || c.addend) && c.stats) && !(c.accumulate && c.addend) &&
+  // BatchNorm-backward sums (bx, mode 0): an epilogue of the 2-D form (conv_band_bx_kernel); the one launch that takes an addend
+  // AND statistics — they are sums over the stored y, addend included.  SDHIP_CONV_NO_BAND_BX sends such calls on (A/B, tests)
+  const bool bx_ok = !c.bx || (c.bx_mode == 0 && c.flat() && c.stats && !c.accumulate && !c.bias && c.act == 0 && c.Cout % 4 == 0 &&
+                               c.ldbx % 8 == 0 && ((uintptr_t)c.bx & 15) == 0 && !sdhip_diag().conv_no_band_bx);
+  return !c.ps && bx_ok && c.omul == 1 && c.dtype == SDHIP_BF16 && g.stride == 1 && g.dil == 1 && !c.in_scale &&
+         !((c.accumulate || c.addend) && c.stats && !c.bx) && !(c.accumulate && c.addend) &&
          (!c.addend || (c.ldadd % 8 == 0 && ((uintptr_t)c.addend & 15) == 0)) && c.Cin % 8 == 0 &&
          c.ldx % 8 == 0 && ((uintptr_t)c.x & 15) == 0 && c.ldy % 8 == 0 && ((uintptr_t)c.y & 15) == 0 &&
          (long)g.B * g.D * g.H * g.W * c.ldx * 2 < (long)kBandOob && band_ok(sdhip_cdiv(g.Ho, 16) * sdhip_cdiv(g.Wo, 32) * g.B * g.Do) &&
@@ -617,6 +621,14 @@ int path_band2d(const ConvCall& c, const ConvPlan& d) {
   const bool band5 = g.kh == 5 && g.kw == 5 && (c.Cin <= 32 || c.Cin == 64);
   const bool band3 = g.kh == 3 && g.kw == 3 && c.Cin <= 32 && !sdhip_diag().conv_no_band3;
   if (!((band5 || band3) && c.flat() && d.Mpad <= 64 && d.Mpad >= 32 && band_common_ok(c))) return kNotTaken;
+  if (c.bx && !band_bx_form_ok(g.kh, d.Mpad, c.addend != nullptr)) return kNotTaken;
+  if (c.bx) {
+    BandBxArgs f{};
+    static_cast<BandArgs&>(f) = band_args(c, d);
+    f.pad_d = 0;
+    f.bx = c.bx; f.bsc = c.bsc; f.bsh = c.bsh; f.ldbx = c.ldbx;
+    return band5 ? launch_band_bx<5>(f, c.stream) : launch_band_bx<3>(f, c.stream);
+  }
   BandArgs f = band_args(c, d);
   f.pad_d = 0;   // no depth axis: whatever the caller passed for it
   return band5 ? launch_band<5>(f, c.stream) : launch_band<3>(f, c.stream);
@@ -626,7 +638,7 @@ int path_band2d(const ConvCall& c, const ConvPlan& d) {
 // every depth tap is a chunk of its tile (its own input slice and 3x3 weights), z runs fastest over a workgroup's tiles
 int path_band3d(const ConvCall& c, const ConvPlan& d) {
   const ConvGeom& g = c.g;
-  if (!(g.kh == 3 && g.kw == 3 && g.kd == 3 && g.sd == 1 && c.Cin <= 32 && d.Mpad == 32 && band_common_ok(c) && !sdhip_diag().conv_no_band3))
+  if (!(g.kh == 3 && g.kw == 3 && g.kd == 3 && g.sd == 1 && c.Cin <= 32 && d.Mpad == 32 && !c.bx && band_common_ok(c) && !sdhip_diag().conv_no_band3))
     return kNotTaken;
   BandArgs f = band_args(c, d);
   return launch_band<3, 3>(f, c.stream);

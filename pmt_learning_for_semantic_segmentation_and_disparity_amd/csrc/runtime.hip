@@ -37,6 +37,7 @@ static void diag_fill() {
   g_diag.conv_no_gemm = env_set("SDHIP_CONV_NO_GEMM");
   g_diag.conv_no_band = env_set("SDHIP_CONV_NO_BAND");
   g_diag.conv_no_band3 = env_set("SDHIP_CONV_NO_BAND3");
+  g_diag.conv_no_band_bx = env_set("SDHIP_CONV_NO_BAND_BX");
   g_diag.conv_no_point = env_set("SDHIP_CONV_NO_POINT");
   g_diag.conv_no_grow = env_set("SDHIP_CONV_NO_GROW");
   g_diag.conv_no_mid = env_set("SDHIP_CONV_NO_MID");

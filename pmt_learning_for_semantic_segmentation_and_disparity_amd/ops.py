@@ -854,6 +854,7 @@ def _take_parked(slot, xv, need_x):
 
 
 BN_SLOT_MAX_BYTES = _lib.TUNE_BN_SLOT_MAX_MB << 20
+BAND_BX_FORMS = tuple(f for f in _lib.TUNE_BAND_BX_FORMS.split(",") if f)   # forms of the persistent kernel that fuse at any size
 
 
 class BNSlot:
@@ -871,6 +872,35 @@ class BNSlot:
         self.gptr = 0
 
 
+def _band_bx_form(spec, Bimg, H, W, Cin, Cout, has_addend, ldg, bn_slot):
+    """'5x5' / '3x3' if the data gradient of this convolution (Cout channels in at pixel stride ldg, Cin channels out) runs on
+    the persistent whole-CU kernel with the BatchNorm-backward sums in its epilogue (path_band2d of csrc/conv_fwd.hip accepts
+    the bnbwd call; conv_band_bx_kernel), else None.  Mirrors that predicate (band_common_ok included): 5x5 with <= 32 or 64
+    channels in / 3x3 with <= 32, 32 .. 64 (padded) channels out, at least 192 tiles of 16 x 32, u at a pixel stride that is
+    a multiple of 8 and 16-byte aligned, the incoming gradient within the kernel's 2 GiB buffer range, not the one form that
+    is not built (5x5, > 32 out, addend) — and none of the switches set that send such a call past the kernel: a shape
+    Python took for this kernel's and C++ refused would run the halo-tile fused form, which at full resolution is slower
+    than two launches."""
+    env = os.environ
+    if env.get("SDHIP_CONV_NO_BAND_BX") or env.get("SDHIP_CONV_NO_BAND") or env.get("SDHIP_CONV_GENERIC"):
+        return None
+    if spec.stride != 1 or spec.dil != 1 or spec.kh != spec.kw or Cout % 8 or Cin % 8 or ldg % 8:
+        return None
+    if bn_slot is None or bn_slot.u is None or bn_slot.ldu % 8 or bn_slot.u.data_ptr() % 16:
+        return None
+    if Bimg * spec.Ho * spec.Wo * ldg * 2 >= 0x7fffff00:
+        return None
+    mpad = (Cin + 15) & ~15
+    tiles = -(-H // 16) * -(-W // 32) * Bimg
+    if not (32 <= mpad <= 64 and 192 <= tiles < 65536):
+        return None
+    if spec.kh == 5 and (Cout <= 32 or Cout == 64) and not (mpad > 32 and has_addend):
+        return '5x5'
+    if spec.kh == 3 and Cout <= 32 and not env.get("SDHIP_CONV_NO_BAND3"):
+        return '3x3'
+    return None
+
+
 def _conv_backward(ctx_spec, xv, ldx, weight, g, ldg, in_scale, in_shift, in_relu, groups, need_x, need_w, bias=None, acc_into=None,
                    addend=None, bn_slot=None):
     """dgrad (w.r.t. the post-prologue input) and wgrad of one conv; returns (g_post, gw, gb)."""
@@ -883,13 +913,16 @@ def _conv_backward(ctx_spec, xv, ldx, weight, g, ldg, in_scale, in_shift, in_rel
     if need_x:
         wd = packed_weight(weight, spec.kind, 'dgrad', xv.dtype)
         fused_bn = False
-        # Measured (profiles/r02_step_summary.txt): the epilogue's reads of u sit exposed behind the MFMA loop, so on maps
-        # of more than ~40 MB (and in the one-workgroup-per-CU 5x5 kernel at any size) it costs more than the streaming
-        # pass it replaces (full resolution, 32 channels: +33 us against a 27 us pass; 5x5 / 64 channels: +126 against 60);
-        # below that the pass is launch- and latency-bound and the fusion wins (64 channels at 128x256: +3.5 against 18)
+        # On the halo-tile kernels the epilogue's reads of u sit exposed behind the MFMA loop, so on maps of more than ~40 MB
+        # it costs more than the streaming pass it replaces (profiles/r02_step_summary.txt: full resolution, 32 channels,
+        # +33 us against a 27 us pass); below that the pass is launch- and latency-bound and the fusion wins (64 channels
+        # at 128x256: +3.5 against 18).  The persistent kernel (conv_band.h) has an epilogue of its own that issues u in
+        # the layout of its stores, in one batch per tile — a stage ahead where the registers allow it: shapes on that
+        # kernel fuse whatever their size, each form behind its own switch (BAND_BX_FORMS; DESIGN.md section 7 has the table)
+        band_form = _band_bx_form(spec, Bimg, H, W, Cin, Cout, acc_into is not None or addend is not None, ldg, bn_slot) if spec.kd == 1 and spec.D == 1 else None
         if (bn_slot is not None and bn_slot.u is not None and bn_slot.C == Cin and xv.dtype == torch.bfloat16 and spec.stride == 1
                 and spec.sd == 1 and spec.kd == 1 and spec.D == 1 and tuple(bn_slot.u.shape) == (Bimg, Cin, H, W)
-                and spec.kh * spec.kw <= 9 and Bimg * H * W * Cin * 2 <= BN_SLOT_MAX_BYTES):
+                and (band_form in BAND_BX_FORMS or (spec.kh * spec.kw <= 9 and Bimg * H * W * Cin * 2 <= BN_SLOT_MAX_BYTES))):
             # the input of this convolution was relu(bn(u)): the launch that writes its gradient also takes that
             # BatchNorm's two backward reductions (and adds a parked skip gradient on the way)
             other = acc_into if acc_into is not None else addend
