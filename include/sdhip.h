@@ -52,6 +52,18 @@ const char* sdhip_last_error(void);
  * the library is loaded (a set switch is announced on stderr) and never per launch; a test or tool that changes the
  * environment for an A/B run inside one process calls this to re-read them.  No reference counterpart. */
 void sdhip_diag_reload(void);
+/* Which kernel the convolution dispatch chooses.  sdhip_last_path() names the kernel that the last call of
+ * sdhip_conv2d_fwd / _fwd_add / _fwd_bnbwd / _fwd_bnpro / _fwd_phase / sdhip_conv2d_wgrad / sdhip_conv2d_wgrad_group (the
+ * last item's) on this thread chose: the family word first, details in parentheses — "thin", "band(5x5, bx)", "mid",
+ * "fast(4x16, ks 1, single-stage, dma, tail)", "generic(8x32, per_tap)", "gemm1x1", "fast(taps 9, mb 64, cit 4, 4x32, register)",
+ * ...; "unsupported" after an SDHIP_ERR_UNSUPPORTED exit, "" before any call and after a call
+ * that was refused for its arguments (SDHIP_ERR_ARG).  The string is thread-local and valid
+ * until the next call of this function.  While sdhip_dispatch_dry(1) is in force on a thread, those entry points
+ * validate and dispatch exactly as usual and launch NOTHING: no operand is dereferenced and the HIP runtime is not
+ * touched, so the question can be asked with made-up (suitably aligned) addresses and without a GPU.  The callers and
+ * the tests ask the library instead of copying its predicates.  No reference counterpart. */
+void sdhip_dispatch_dry(int on);
+const char* sdhip_last_path(void);
 /* End a stream capture that failed half way (an uncapturable call invalidated it and the caller left its capture block
  * by an exception): hipStreamEndCapture on `stream`, the partial graph destroyed, the sticky error cleared.  Returns 1 if a
  * capture was still open, 0 if none was, < 0 if the stream cannot be brought back.  Host-side recovery for the training

@@ -11,6 +11,7 @@ entry point (`SIGNATURES`) and the numeric constants (`CONSTANTS`) are read from
 import.  A new entry point is declared there, defined in csrc/ and called; nothing is
 added here.
 """
+import contextlib
 import ctypes
 import os
 import re
@@ -177,6 +178,22 @@ def reload_diag():
     _lib.sdhip_diag_reload()
 
 
+@contextlib.contextmanager
+def dispatch_dry():
+    """While active on this thread the convolution entry points validate and dispatch as usual and launch nothing
+    (sdhip_dispatch_dry of include/sdhip.h): `with dispatch_dry(): call(...)`, then `last_path()`."""
+    _lib.sdhip_dispatch_dry(1)
+    try:
+        yield
+    finally:
+        _lib.sdhip_dispatch_dry(0)
+
+
+def last_path():
+    """Name of the kernel the last convolution entry point on this thread chose, dry or real (sdhip_last_path)."""
+    return _lib.sdhip_last_path().decode()
+
+
 def _diag_switch(name):
     """Python-side diagnostic switches are read once, at import, and announced."""
     v = os.environ.get(name)
@@ -197,7 +214,7 @@ DIAG_NO_BN_SLOTS = bool(_diag_switch("SDHIP_DIAG_NO_BN_SLOTS"))
 TUNE_FUSE1_MAX_PIX = int(_diag_switch("SDHIP_TUNE_FUSE1_MAX_PIX") or 32768)
 TUNE_PRO_MAX_PIX = int(_diag_switch("SDHIP_TUNE_PRO_MAX_PIX") or 32768)
 TUNE_BN_SLOT_MAX_MB = int(_diag_switch("SDHIP_TUNE_BN_SLOT_MAX_MB") or 40)
-_forms = _diag_switch("SDHIP_TUNE_BAND_BX_FORMS")                          # "5x5,3x3" / "5x5" / "3x3" / "none" (A/B of ops._band_bx_form)
+_forms = _diag_switch("SDHIP_TUNE_BAND_BX_FORMS")                          # "5x5,3x3" / "5x5" / "3x3" / "none" (A/B: the forms of the persistent kernel ops._conv_backward keeps)
 TUNE_BAND_BX_FORMS = "5x5,3x3" if _forms is None else ("" if _forms == "none" else _forms)
 del _forms
 DIAG_NO_BNPRO = bool(_diag_switch("SDHIP_DIAG_NO_BNPRO"))

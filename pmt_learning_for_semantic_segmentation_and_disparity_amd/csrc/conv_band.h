@@ -199,6 +199,7 @@ int launch_band_bx(BandBxArgs& a, hipStream_t s) {
   // not built — host, band_bx_form_ok: it is the one form that spills, 2 registers)
   if (!band_bx_form_ok(K, a.Mpad, a.res != nullptr))
     SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv_band: the BatchNorm-backward form with an addend is not built for %dx%d with more than 32 output channels", K, K);
+  SDHIP_CHOSE(kFwdBand, K, 1, 1);
   if constexpr (K == 5) {
     if (a.Mpad > 32) return launch_band_bx_bn<K, 64, 5 + 8>(a, grid, s);
   } else {

@@ -52,6 +52,26 @@ struct ConvGeom {
 // limit): the caller goes on to the next path in its chain.
 constexpr int kNotTaken = 1;
 
+// Which kernel the last conv entry point of this thread chose (sdhip_last_path / sdhip_dispatch_dry of include/sdhip.h;
+// the record and the flag live in runtime.hip, which also turns the record into its name).  A launch site says
+// SDHIP_CHOSE(family, details...) behind the last thing that can still decline and before its first HIP runtime call: a
+// few stores, and in dry mode the call ends there, with nothing launched and no operand or runtime touched.
+// A new path adds a family here, its name in sdhip_last_path() and one SDHIP_CHOSE at its launch site.
+enum SdhipPathFamily {
+  kPathNone, kPathUnsupported,
+  kFwdThin, kFwdFanin, kFwdFanout, kFwdGemm, kFwdBand /* k, kd, bx */, kFwdPoint, kFwdGrow, kFwdMid,
+  kFwdFast /* th, tw, ks, stages (0 single-stage, 1 tap-grouped, 2 chunked), dma, tail */, kFwdGeneric /* th, tw, per_tap, prefetch */,
+  kWgThin, kWgSingle, kWgHalf32, kWgGemm1x1, kWgPacked /* qb, dma */, kWgFast /* taps, mb, cit, th, tw, dma */, kWgGeneric /* taps, mb, th, tw */
+};
+struct SdhipPath { int family; int v[6]; };
+SdhipPath& sdhip_path();   // thread-local
+bool sdhip_dry();          // thread-local: sdhip_dispatch_dry(1) is in force
+#define SDHIP_CHOSE(family, ...) do { sdhip_path() = SdhipPath{family, {__VA_ARGS__}}; if (sdhip_dry()) return SDHIP_OK; } while (0)
+// an entry point's way in (before its own argument checks: a refused call leaves "", not the call before it) and out
+// (SDHIP_ERR_UNSUPPORTED is a choice too)
+inline void sdhip_path_enter() { sdhip_path() = SdhipPath{kPathNone, {}}; }
+inline int sdhip_path_exit(int rc) { if (rc == SDHIP_ERR_UNSUPPORTED) sdhip_path() = SdhipPath{kPathUnsupported, {}}; return rc; }
+
 // The image extents and paddings that every family's argument struct carries under these names.
 template <typename Args>
 inline void set_extent(Args& a, const ConvGeom& g) {

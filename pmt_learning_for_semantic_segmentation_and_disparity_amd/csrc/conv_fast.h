@@ -852,8 +852,10 @@ int launch_fast_bx_bn(const FastArgs& a, int bn, size_t lds, hipStream_t s) {   
 
 template <typename T>
 int launch_fast_any(const FastArgs& a, bool big, int ks, int bn, size_t lds, hipStream_t s) {
+  if (a.bx && (!a.dma || sizeof(T) != 2)) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_bnbwd: bf16 without an input prologue / channel tail only");
+  const int nqq = a.kd * (ks == 2 ? sdhip_cdiv(a.Cin, 8 * Chunk<T>::N) : 1);   // pipeline stages = (depth tap, channel chunk) x tap groups
+  SDHIP_CHOSE(kFwdFast, big ? 8 : 4, big ? 32 : 16, ks, nqq * a.ntg == 1 ? 0 : a.ntg > 1 ? 1 : 2, a.dma, a.tail);
   if (a.bx) {
-    if (!a.dma || sizeof(T) != 2) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_bnbwd: bf16 without an input prologue / channel tail only");
     if (big) return ks == 2 ? launch_fast_bx_bn<8, 32, 2>(a, bn, lds, s) : launch_fast_bx_bn<8, 32, 1>(a, bn, lds, s);
     return ks == 2 ? launch_fast_bx_bn<4, 16, 2>(a, bn, lds, s) : launch_fast_bx_bn<4, 16, 1>(a, bn, lds, s);
   }

@@ -405,6 +405,7 @@ int launch(const FwdArgs& a, size_t lds, hipStream_t s) {
 
 template <typename T, int TH, int TW>
 int launch_bn(const FwdArgs& a, int bn, size_t lds, hipStream_t s) {
+  SDHIP_CHOSE(kFwdGeneric, TH, TW, a.per_tap, a.pf_halo);
   switch (bn) {
     case 16: return launch<T, TH, TW, 16>(a, lds, s);
     case 32: return launch<T, TH, TW, 32>(a, lds, s);
@@ -462,6 +463,18 @@ ConvCall conv_call(const void* x, const void* wpacked, void* y, const ConvGeom& 
   c.Cin = Cin; c.ldx = ldx; c.Cout = Cout; c.ldy = ldy;
   c.dtype = dtype; c.stream = (hipStream_t)stream;
   return c;
+}
+
+// the consumer-side BatchNorm finalize of a call, if it has one, into the pin_* / pend_* fields every kernel family that
+// takes it (fast, point, grow) carries under these names
+template <typename Args>
+void set_pin(Args& f, const ConvCall& c) {
+  const ProStats* ps = c.ps;
+  if (!ps) return;
+  f.pin_stats = ps->stats; f.pin_ld = ps->ld; f.pin_nrep = ps->nrep; f.pin_groups = c.groups; f.pin_gamma = ps->gamma; f.pin_beta = ps->beta;
+  f.pin_scale = ps->scale; f.pin_shift = ps->shift; f.pin_mean = ps->mean; f.pin_invstd = ps->invstd; f.pin_rmean = ps->rmean; f.pin_rvar = ps->rvar;
+  f.pin_eps = ps->eps; f.pin_momentum = ps->momentum; f.pin_count = ps->count;
+  f.pend_stats = ps->pend; f.pin_fold = ps->fold; f.pend_ld = ps->pend_ld; f.pend_nrep = ps->pend_nrep; f.pend_c0 = ps->pend_c0; f.pend_n = ps->pend ? ps->pend_n : 0;
 }
 
 // What the paths share, computed once per call.
@@ -524,6 +537,7 @@ int path_thin(const ConvCall& c, const ConvPlan& d) {
         d.T <= kThinMaxT && g.Ho == g.H + 2 * g.pad_t - g.dil * (g.kh - 1) && g.Wo == g.W + 2 * g.pad_l - g.dil * (g.kw - 1) &&
         g.pad_t >= 0 && g.pad_l >= 0 && !sdhip_diag().conv_no_thin))
     return kNotTaken;
+  SDHIP_CHOSE(kFwdThin);
   ThinArgs t{};
   t.x = c.x; t.wp = c.wp; t.y = c.y; t.bias = c.bias; t.stats = c.stats;
   set_extent(t, g);
@@ -585,6 +599,9 @@ int path_gemm(const ConvCall& c, const ConvPlan& d) {
   a.M = (long)g.B * g.H * g.W; a.H = g.H; a.W = g.W; a.ppg = a.M / c.groups;
   a.stats_ld = d.stats_ld; a.nrep = d.nrep; a.rep_stride = d.rep_stride;
   if (!gemm1x1_ok(a, (c.in_scale || c.stats) ? c.groups : 1)) return kNotTaken;
+  // launch_gemm's own decline (the prologue table does not fit LDS) cannot fire behind gemm1x1_ok: K <= 1024 with a prologue
+  static_assert(gemm_lds_bytes(128, 3, 1024 / 64, true) <= 160 * 1024 && gemm_lds_bytes(128, 3, 4096 / 64, false) <= 160 * 1024, "gemm1x1_ok bounds the LDS of every launch");
+  SDHIP_CHOSE(kFwdGemm);
   return launch_gemm_any(a, c.stream);
 }
 
@@ -629,6 +646,7 @@ int path_band2d(const ConvCall& c, const ConvPlan& d) {
     f.bx = c.bx; f.bsc = c.bsc; f.bsh = c.bsh; f.ldbx = c.ldbx;
     return band5 ? launch_band_bx<5>(f, c.stream) : launch_band_bx<3>(f, c.stream);
   }
+  SDHIP_CHOSE(kFwdBand, g.kh, 1, 0);
   BandArgs f = band_args(c, d);
   f.pad_d = 0;   // no depth axis: whatever the caller passed for it
   return band5 ? launch_band<5>(f, c.stream) : launch_band<3>(f, c.stream);
@@ -640,6 +658,7 @@ int path_band3d(const ConvCall& c, const ConvPlan& d) {
   const ConvGeom& g = c.g;
   if (!(g.kh == 3 && g.kw == 3 && g.kd == 3 && g.sd == 1 && c.Cin <= 32 && d.Mpad == 32 && !c.bx && band_common_ok(c) && !sdhip_diag().conv_no_band3))
     return kNotTaken;
+  SDHIP_CHOSE(kFwdBand, 3, 3, 0);
   BandArgs f = band_args(c, d);
   return launch_band<3, 3>(f, c.stream);
 }
@@ -662,18 +681,13 @@ int path_point(const ConvCall& c, const ConvPlan& d) {
         (long)g.B * sdhip_cdiv((long)g.H * g.W, kPointPix) * (c.Cout / kPointBN) <= kPointMaxWG &&
         d.vec_in && d.vec_out && (long)g.H * g.W * c.ldx < (1L << 31) && !dg.conv_generic && !dg.conv_no_point))
     return kNotTaken;
-  const ProStats* ps = c.ps;
+  SDHIP_CHOSE(kFwdPoint);
   PointArgs f{};
   f.x = c.x; f.wp = c.wp; f.y = c.y; f.in_scale = c.in_scale; f.in_shift = c.in_shift; f.stats = c.stats;
   f.HW = g.H * g.W; f.Cin = c.Cin; f.ldx = c.ldx; f.Cout = c.Cout; f.Mpad = d.Mpad; f.ldy = c.ldy;
   f.in_relu = c.in_relu; f.bpg = g.B / c.groups;
   f.stats_ld = d.stats_ld; f.nrep = d.nrep; f.rep_stride = d.rep_stride;
-  if (ps) {
-    f.pin_stats = ps->stats; f.pin_ld = ps->ld; f.pin_nrep = ps->nrep; f.pin_groups = c.groups; f.pin_gamma = ps->gamma; f.pin_beta = ps->beta;
-    f.pin_scale = ps->scale; f.pin_shift = ps->shift; f.pin_mean = ps->mean; f.pin_invstd = ps->invstd; f.pin_rmean = ps->rmean; f.pin_rvar = ps->rvar;
-    f.pin_eps = ps->eps; f.pin_momentum = ps->momentum; f.pin_count = ps->count;
-    f.pend_stats = ps->pend; f.pin_fold = ps->fold; f.pend_ld = ps->pend_ld; f.pend_nrep = ps->pend_nrep; f.pend_c0 = ps->pend_c0; f.pend_n = ps->pend ? ps->pend_n : 0;
-  }
+  set_pin(f, c);
   return launch_point(f, g.B, c.stream);
 }
 
@@ -691,18 +705,13 @@ int path_grow(const ConvCall& c, const ConvPlan& d) {
         (long)g.B * sdhip_cdiv(g.H, kGrowTH) * sdhip_cdiv(g.W, kGrowTW) <= kGrowMaxWG &&
         d.vec_in && d.vec_out && (long)g.H * g.W * c.ldx < (1L << 31) && !dg.conv_generic && !dg.conv_no_grow))
     return kNotTaken;
-  const ProStats* ps = c.ps;
+  SDHIP_CHOSE(kFwdGrow);
   GrowArgs f{};
   f.x = c.x; f.wp = c.wp; f.y = c.y; f.in_scale = c.in_scale; f.in_shift = c.in_shift; f.stats = c.stats;
   f.H = g.H; f.W = g.W; f.Cin = c.Cin; f.ldx = c.ldx; f.ldy = c.ldy; f.tiles_w = sdhip_cdiv(g.W, kGrowTW);
   f.in_relu = c.in_relu; f.bpg = g.B / c.groups;
   f.stats_ld = d.stats_ld; f.nrep = d.nrep; f.rep_stride = d.rep_stride;
-  if (ps) {
-    f.pin_stats = ps->stats; f.pin_ld = ps->ld; f.pin_nrep = ps->nrep; f.pin_groups = c.groups; f.pin_gamma = ps->gamma; f.pin_beta = ps->beta;
-    f.pin_scale = ps->scale; f.pin_shift = ps->shift; f.pin_mean = ps->mean; f.pin_invstd = ps->invstd; f.pin_rmean = ps->rmean; f.pin_rvar = ps->rvar;
-    f.pin_eps = ps->eps; f.pin_momentum = ps->momentum; f.pin_count = ps->count;
-    f.pend_stats = ps->pend; f.pin_fold = ps->fold; f.pend_ld = ps->pend_ld; f.pend_nrep = ps->pend_nrep; f.pend_c0 = ps->pend_c0; f.pend_n = ps->pend ? ps->pend_n : 0;
-  }
+  set_pin(f, c);
   return launch_grow(f, g.B, c.stream);
 }
 
@@ -722,6 +731,7 @@ int path_mid(const ConvCall& c, const ConvPlan& d) {
         (long)g.B * sdhip_cdiv(g.H, kMidTH) * sdhip_cdiv(g.W, kMidTW) <= max_wg &&
         d.vec_in && d.vec_out && (long)g.H * g.W * c.ldx < (1L << 31) && !dg.conv_generic && !dg.conv_no_mid))
     return kNotTaken;
+  SDHIP_CHOSE(kFwdMid);
   MidArgs f{};
   f.x = c.x; f.wp = c.wp; f.y = c.y; f.stats = c.stats;
   f.H = g.H; f.W = g.W; f.ldx = c.ldx; f.ldy = c.ldy; f.tiles_w = sdhip_cdiv(g.W, kMidTW);
@@ -741,7 +751,6 @@ int path_fast(const ConvCall& c, const ConvPlan& d) {
   const int CKh = 8 * d.V, T = d.T, bn = d.bn;
   const int ks = d.chunks_per_row == 4 ? 1 : 2;
   const int rb = 64 * ks, px_per_round = 256 / (4 * ks);
-  const ProStats* ps = c.ps;
   FastArgs f{};
   f.x = c.x; f.wp = c.wp; f.y = c.y; f.bias = c.bias; f.in_scale = c.in_scale; f.in_shift = c.in_shift; f.stats = c.stats;
   set_extent(f, g);
@@ -753,13 +762,8 @@ int path_fast(const ConvCall& c, const ConvPlan& d) {
   f.omul = c.omul; f.ooz = c.ooz; f.ooy = c.ooy; f.oox = c.oox;
   f.bx = c.bx; f.ldbx = c.ldbx; f.bsc = c.bsc; f.bsh = c.bsh;
   f.res = c.bx ? c.addend : nullptr; f.ldres = c.ldadd; f.bx_mode = c.bx_mode; f.bx_groups = c.groups;
-  f.dma = !c.in_scale && !f.tail && !ps;
-  if (ps) {
-    f.pin_stats = ps->stats; f.pin_ld = ps->ld; f.pin_nrep = ps->nrep; f.pin_groups = c.groups; f.pin_gamma = ps->gamma; f.pin_beta = ps->beta;
-    f.pin_scale = ps->scale; f.pin_shift = ps->shift; f.pin_mean = ps->mean; f.pin_invstd = ps->invstd; f.pin_rmean = ps->rmean; f.pin_rvar = ps->rvar;
-    f.pin_eps = ps->eps; f.pin_momentum = ps->momentum; f.pin_count = ps->count;
-    f.pend_stats = ps->pend; f.pin_fold = ps->fold; f.pend_ld = ps->pend_ld; f.pend_nrep = ps->pend_nrep; f.pend_c0 = ps->pend_c0; f.pend_n = ps->pend ? ps->pend_n : 0;
-  }
+  f.dma = !c.in_scale && !f.tail && !c.ps;
+  set_pin(f, c);
   bool fbig = d.big;   // this path's own copy: the generic path starts from d.big again
   for (int attempt = 0; attempt < 2; ++attempt) {
     const int th = fbig ? 8 : 4, tw = fbig ? 32 : 16;
@@ -781,7 +785,7 @@ int path_fast(const ConvCall& c, const ConvPlan& d) {
     }
     if (lds < 4096) lds = 4096;
     f.pin_off = 0; f.pin_cs = 0;
-    if (ps) { f.pin_off = (int)lds; f.pin_cs = (c.Cin + 63) & ~63; lds += 2 * (size_t)f.pin_cs * sizeof(float); }   // the finalize table sits behind everything else
+    if (c.ps) { f.pin_off = (int)lds; f.pin_cs = (c.Cin + 63) & ~63; lds += 2 * (size_t)f.pin_cs * sizeof(float); }   // the finalize table sits behind everything else
     if (lds > kLdsMax) { if (!fbig) break; fbig = false; continue; }
     f.tg = tg;
     f.magic_iwp = IWp > 1 ? (unsigned)(0x100000000ULL / (unsigned)IWp) + 1u : 0u;
@@ -833,7 +837,7 @@ int path_generic(const ConvCall& c, const ConvPlan& d) {
   SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd: no tile configuration fits");
 }
 
-int conv2d_fwd_impl(const ConvCall& c) {
+int conv2d_fwd_dispatch(const ConvCall& c) {
   const ConvGeom& g = c.g;
   SDHIP_CHECK_ARG(c.x && c.wp && c.y, "conv2d_fwd: null pointer");
   SDHIP_CHECK_ARG(c.dtype == SDHIP_F32 || c.dtype == SDHIP_BF16, "conv2d_fwd: unknown dtype %d", c.dtype);
@@ -857,6 +861,10 @@ int conv2d_fwd_impl(const ConvCall& c) {
   if (c.ps) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_bnpro: needs the aligned fast path (ldx %% 8, ldy %% 4, halo tile within LDS)");
   if (c.bx) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_bnbwd: needs the aligned fast path (ldx %% 8, ldy %% 4, halo tile within LDS)");
   return path_generic(c, d);
+}
+
+int conv2d_fwd_impl(const ConvCall& c) {
+  return sdhip_path_exit(conv2d_fwd_dispatch(c));
 }
 
 }  // namespace
@@ -890,6 +898,7 @@ extern "C" int sdhip_conv2d_fwd(const void* x, const void* wpacked, void* y,
                                 int D, int Do, int kd, int sd, int pad_d,
                                 int in_relu, int groups, int act, int accumulate,
                                 int dtype, void* stream) {
+  sdhip_path_enter();
   ConvCall c = conv_call(x, wpacked, y, ConvGeom{B, H, W, Ho, Wo, kh, kw, stride, dil, pad_t, pad_l, D, Do, kd, sd, pad_d},
                          Cin, ldx, Cout, ldy, dtype, stream);
   c.bias = bias; c.in_scale = in_scale; c.in_shift = in_shift;
@@ -907,11 +916,14 @@ extern "C" int sdhip_conv2d_fwd_bnpro(const void* x, const void* wpacked, void* 
                                       float* invstd_out, double count, float eps, float momentum,
                                       int B, int H, int W, int Cin, int ldx, int Ho, int Wo, int Cout, int ldy,
                                       int kh, int kw, int pad_t, int pad_l, int groups, int dtype, void* stream) {
+  sdhip_path_enter();
   SDHIP_CHECK_ARG(in_stats && scale_out && shift_out && mean_out && invstd_out && count >= 1. && in_stats_nrep >= 1 && in_stats_ld >= Cin,
                   "conv2d_fwd_bnpro: statistics / output vectors missing");
   SDHIP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "conv2d_fwd_bnpro: running_mean / running_var come together");
-  if (Cin > kPinMaxC || in_stats_nrep > 4 || (pend_stats && pend_nrep > 4))
+  if (Cin > kPinMaxC || in_stats_nrep > 4 || (pend_stats && pend_nrep > 4)) {
+    sdhip_path_exit(SDHIP_ERR_UNSUPPORTED);
     SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv2d_fwd_bnpro: at most %d input channels and 4 statistics replicas", kPinMaxC);
+  }
   SDHIP_CHECK_ARG(!pend_stats || (pend_n > 0 && pend_c0 >= 0 && pend_c0 + pend_n <= Cin && pend_ld >= pend_n && pend_nrep >= 1 && in_stats_nrep == 1),
                   "conv2d_fwd_bnpro: bad pending-statistics slice (folding needs single-replica slab statistics)");
   ProStats ps{in_stats, in_stats_ld, in_stats_nrep, gamma, beta, scale_out, shift_out, mean_out, invstd_out, running_mean, running_var,
@@ -927,6 +939,7 @@ extern "C" int sdhip_conv2d_fwd_bnpro(const void* x, const void* wpacked, void* 
 extern "C" int sdhip_conv2d_fwd_add(const void* x, const void* wpacked, void* y, const void* addend, int ldadd,
                                     int B, int H, int W, int Cin, int ldx, int Ho, int Wo, int Cout, int ldy,
                                     int kh, int kw, int pad_t, int pad_l, int dtype, void* stream) {
+  sdhip_path_enter();
   SDHIP_CHECK_ARG(addend && ldadd >= Cout, "conv2d_fwd_add: addend missing / pixel stride smaller than Cout");
   ConvCall c = conv_call(x, wpacked, y, geom2d(B, H, W, Ho, Wo, kh, kw, 1, 1, pad_t, pad_l), Cin, ldx, Cout, ldy, dtype, stream);
   c.addend = addend; c.ldadd = ldadd;
@@ -939,6 +952,7 @@ extern "C" int sdhip_conv2d_fwd_bnbwd(const void* x, const void* wpacked, void* 
                                       const void* u, int ldu, const float* scale, const float* shift, const void* addend, int ldadd,
                                       int B, int H, int W, int Cin, int ldx, int Ho, int Wo, int Cout, int ldy,
                                       int kh, int kw, int dil, int pad_t, int pad_l, int groups, int mode, int dtype, void* stream) {
+  sdhip_path_enter();
   SDHIP_CHECK_ARG(mode == 0 || (mode == 1 && addend), "conv2d_fwd_bnbwd: mode 1 (apply) needs the tensor the result is added to");
   SDHIP_CHECK_ARG(dtype == SDHIP_BF16, "conv2d_fwd_bnbwd: bf16 only");
   SDHIP_CHECK_ARG(sums && u && scale && shift && ldu >= Cout && Cout % 4 == 0 && ldu % 4 == 0 && ((uintptr_t)u & 7) == 0 &&
@@ -958,6 +972,7 @@ extern "C" int sdhip_conv2d_fwd_bnbwd(const void* x, const void* wpacked, void* 
 extern "C" int sdhip_conv2d_fwd_phase(const void* x, const void* wpacked, void* y, double* stats, int stats_ld, int stats_nrep,
                                       int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int kh, int kw,
                                       int D, int kd, int groups, int off_d, int off_h, int off_w, int dtype, void* stream) {
+  sdhip_path_enter();
   SDHIP_CHECK_ARG(off_d >= 0 && off_d < 2 && off_h >= 0 && off_h < 2 && off_w >= 0 && off_w < 2, "conv2d_fwd_phase: phase offsets are 0 or 1");
   ConvCall c = conv_call(x, wpacked, y, ConvGeom{B, H, W, H, W, kh, kw, 1, 1, 0, 0, D, D, kd, 1, 0}, Cin, ldx, Cout, ldy, dtype, stream);
   c.stats = stats; c.stats_ld = stats_ld; c.stats_nrep = stats_nrep;

@@ -329,7 +329,7 @@ __global__ __launch_bounds__(512) void gemm1x1_kernel(const GemmArgs p) {
   if (p.stats && st_grp >= 0) flush_stats();
 }
 
-inline size_t gemm_lds_bytes(int nt, int ns, int nq, bool table) {
+constexpr size_t gemm_lds_bytes(int nt, int ns, int nq, bool table) {
   return (size_t)ns * (256 * 128 + (nt < 64 ? 64 : nt) * 128) + (size_t)2 * nt * 4 + (table ? (size_t)2 * nq * 64 * 4 : 0);
 }
 

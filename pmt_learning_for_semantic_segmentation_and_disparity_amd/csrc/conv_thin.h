@@ -337,6 +337,7 @@ inline int fanout_dpw(const FanArgs& a) {
 inline int launch_fanout(FanArgs a, hipStream_t s) {
   a.dpw = fanout_dpw(a);
   if (a.dpw < 1) SDHIP_FAIL(SDHIP_ERR_UNSUPPORTED, "conv fan-out: halo of a %dx%dx%d kernel with dilation %d exceeds the tile buffer", a.kd, a.kh, a.kw, a.dil);
+  SDHIP_CHOSE(kFwdFanout);
   a.zsegs = sdhip_cdiv(a.Do, a.dpw);
   dim3 grid(sdhip_cdiv(a.Ho, 8) * sdhip_cdiv(a.Wo, 32), a.B * a.zsegs);
   hipLaunchKernelGGL(conv_fanout_kernel, grid, dim3(256), 0, s, a);
@@ -488,6 +489,7 @@ inline int launch_fanin(FaninArgs a, int kd, hipStream_t s) {
   while (dpw > 4 && tiles * sdhip_cdiv(a.Do, dpw) < 1024) --dpw;
   a.dpw = dpw; a.zsegs = sdhip_cdiv(a.Do, dpw);
   if ((long)a.B * a.zsegs > 65535) return kNotTaken;
+  SDHIP_CHOSE(kFwdFanin);
   dim3 grid(sdhip_cdiv(a.Ho, 8) * sdhip_cdiv(a.Wo, 32), a.B * a.zsegs);
   if (kd == 3 && a.kh == 3 && a.kw == 3) hipLaunchKernelGGL((conv_fanin_kernel<3, 1, 3>), grid, dim3(256), lds, s, a);
   else if (kd == 3) hipLaunchKernelGGL((conv_fanin_kernel<3, 1>), grid, dim3(256), lds, s, a);

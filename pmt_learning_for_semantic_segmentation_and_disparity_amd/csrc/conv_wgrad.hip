@@ -231,6 +231,7 @@ int launch(const WgArgs& a, hipStream_t s) {
   const int IH = (TH - 1) * g.stride + (g.kh - 1) * g.dil + 1, IW = (TW - 1) * g.stride + (g.kw - 1) * g.dil + 1;
   const size_t lds = (((size_t)IH * IW * 128 + 15) & ~(size_t)15) + (size_t)TH * TW * 128;
   if (lds > 160 * 1024) return kNotTaken;  // caller falls back to a smaller tile
+  SDHIP_CHOSE(kWgGeneric, MAXT, MB, TH, TW);
   static size_t attr_set = 0;
   if (lds > 64 * 1024 && attr_set == 0) {
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
@@ -408,6 +409,7 @@ int wg_thin(const WgArgs& a, int dtype, hipStream_t s) {
         g.Ho == g.H + 2 * g.pad_t - g.dil * (g.kh - 1) && g.Wo == g.W + 2 * g.pad_l - g.dil * (g.kw - 1) && g.pad_t >= 0 && g.pad_l >= 0 &&
         !sdhip_diag().conv_no_thin))
     return kNotTaken;
+  SDHIP_CHOSE(kWgThin);
   ThinWgArgs t{};
   t.x = a.x; t.dy = a.dy; t.dwp = a.dwp; t.dbias = a.dbias;
   set_extent(t, g);
@@ -476,43 +478,38 @@ int wg_fast(const WgArgs& a, int dtype, hipStream_t s, WgfPlan* plan, bool* plan
   f.tpb = a.tpb; f.ntg = a.ntg; f.nq = a.nq;
   if (T == 1 && a.tpb == 1) { f.tpb = 1; f.ntg = 1; }
   f.qb = 0; f.qsh = 0; f.nq_tot = a.nq;
-  // <= 32 channels on both sides, 3x3 (x3), stride 1: 64-byte LDS rows, all depth taps per workgroup (conv_wgrad_half.h)
-  if (a.Cin <= 32 && a.Cout <= 32 && g.kh == 3 && g.kw == 3 && g.stride == 1 && g.dil == 1 && g.sd == 1 && (g.kd == 1 || g.kd == 3) && !a.in_scale &&
-      !a.dbias && g.Wo >= 24 && !sdhip_diag().wgrad_no_half32) {
-    WgfPlan pl;
-    const int rc = g.kd == 3 ? plan_wg32<3>(f, pl) : plan_wg32<1>(f, pl);
-    if (rc != SDHIP_OK) return rc;
-    if (plan) { *plan = pl; *planned = true; return SDHIP_OK; }
-    return launch_wgf_plan(pl, s);
-  }
+  // Every kernel of this path is planned first (plan_*: kNotTaken, or an error); the layer is then launched or handed on.
+  WgfPlan pl;
+  int rc = kNotTaken;
   const bool no_pack = sdhip_diag().wgrad_no_pack;   // diagnostics: A/B against the unpacked kernel
-  // 1x1 with a BatchNorm prologue, >= 96 input channels into a multiple of 128 outputs (DenseNet bottlenecks / transitions):
-  // the pixel-contraction GEMM of conv_wgrad_gemm1x1.h, a [128 x 256] output tile per workgroup.  It stands aside for the
-  // switches that name one of the kernels below (and for its own, SDHIP_WGRAD_NO_GEMM: A/B runs).
-  if (wgrad_gemm1x1_ok(f, T) && !no_pack && !sdhip_diag().wgrad_force_pack && !sdhip_diag().wgrad_no_gemm) {
-    WgfPlan pl;
-    const int rc = plan_wg1(f, pl);
-    if (rc != SDHIP_OK) return rc;
-    if (plan) { *plan = pl; *planned = true; return SDHIP_OK; }
-    return launch_wgf_plan(pl, s);
-  }
-  // 1x1 with many input channels (the same layers without a prologue, or under the switches): pack 2 or 4 channel chunks per workgroup
+  // 1x1 with many input channels (the layers below without a prologue, or under the switches): pack 2 or 4 channel chunks per workgroup
   // Measured (tools/gpu_wgrad1x1_ab.sh): it pays on large maps and wide outputs (192->128 at 16x64x128: 88 -> 52 us,
   // 1024->512 at 16x16x32: 62 -> 54 us); on the small maps of the deep DenseNet blocks the sweep is bound by the
   // per-tile DMA latency either way and the unpacked kernel's smaller tiles win (1024->128 at 16x16x32: 21 vs 31 us).
   const bool pack_pays = a.Cout >= 256 || (long)g.B * g.H * g.W >= 100000;
-  if (T == 1 && g.kd == 1 && g.stride == 1 && g.pad_t == 0 && g.pad_l == 0 && g.Ho == g.H && g.Wo == g.W && a.nq >= 2 && a.Cout > 32 && !no_pack &&
-      (pack_pays || sdhip_diag().wgrad_force_pack)) {
-    WgfArgs p = f;
-    p.qb = a.nq >= 3 ? 4 : 2; p.qsh = p.qb == 4 ? 2 : 1;
-    p.kh = 1; p.kw = p.qb; p.tpb = p.qb; p.ntg = 1; p.nq = sdhip_cdiv(a.nq, p.qb);
-    const int rc = a.in_scale ? launch_wgf_packed<false>(p, s, plan) : launch_wgf_packed<true>(p, s, plan);
-    if (rc != kNotTaken) { if (plan && rc == SDHIP_OK) *planned = true; return rc; }
+  // <= 32 channels on both sides, 3x3 (x3), stride 1: 64-byte LDS rows, all depth taps per workgroup (conv_wgrad_half.h)
+  if (a.Cin <= 32 && a.Cout <= 32 && g.kh == 3 && g.kw == 3 && g.stride == 1 && g.dil == 1 && g.sd == 1 && (g.kd == 1 || g.kd == 3) && !a.in_scale &&
+      !a.dbias && g.Wo >= 24 && !sdhip_diag().wgrad_no_half32) {
+    rc = g.kd == 3 ? plan_wg32<3>(f, pl) : plan_wg32<1>(f, pl);
+  // 1x1 with a BatchNorm prologue, >= 96 input channels into a multiple of 128 outputs (DenseNet bottlenecks / transitions):
+  // the pixel-contraction GEMM of conv_wgrad_gemm1x1.h, a [128 x 256] output tile per workgroup.  It stands aside for the
+  // switches that name one of the kernels below (and for its own, SDHIP_WGRAD_NO_GEMM: A/B runs).
+  } else if (wgrad_gemm1x1_ok(f, T) && !no_pack && !sdhip_diag().wgrad_force_pack && !sdhip_diag().wgrad_no_gemm) {
+    rc = plan_wg1(f, pl);
+  } else {
+    if (T == 1 && g.kd == 1 && g.stride == 1 && g.pad_t == 0 && g.pad_l == 0 && g.Ho == g.H && g.Wo == g.W && a.nq >= 2 && a.Cout > 32 && !no_pack &&
+        (pack_pays || sdhip_diag().wgrad_force_pack)) {
+      WgfArgs p = f;
+      p.qb = a.nq >= 3 ? 4 : 2; p.qsh = p.qb == 4 ? 2 : 1;
+      p.kh = 1; p.kw = p.qb; p.tpb = p.qb; p.ntg = 1; p.nq = sdhip_cdiv(a.nq, p.qb);
+      rc = a.in_scale ? plan_wgf_packed<false>(p, pl) : plan_wgf_packed<true>(p, pl);
+    }
+    // MB = 32 regroups the taps over two wave groups: the tap grouping must match the instantiation (see plan_wgf_taps)
+    if (rc == kNotTaken) rc = a.in_scale ? plan_wgf_taps<false>(f, T, pl) : plan_wgf_taps<true>(f, T, pl);
   }
-  // MB = 32 regroups the taps over two wave groups: the tap grouping must match the instantiation (see launch_wgf_taps)
-  const int rc = a.in_scale ? launch_wgf_taps<false>(f, T, s, plan) : launch_wgf_taps<true>(f, T, s, plan);
-  if (plan && rc == SDHIP_OK) *planned = true;
-  return rc;   // kNotTaken: no tile fits LDS -> general kernel
+  if (rc != SDHIP_OK || sdhip_dry()) return rc;   // kNotTaken: no tile fits LDS -> general kernel
+  if (plan) { *plan = pl; *planned = true; return SDHIP_OK; }
+  return launch_wgf_plan(pl, s);
 }
 
 }  // namespace
@@ -520,6 +517,7 @@ int wg_fast(const WgArgs& a, int dtype, hipStream_t s, WgfPlan* plan, bool* plan
 // One layer.  plan == nullptr: launch now.  plan != nullptr: a layer of the bf16 fast path is only PLANNED (*planned = true,
 // nothing launched) so that the caller can group it with others; every other path launches as usual.
 static int wgrad_one(const SdhipWgradItem& it, int prezeroed, int dtype, void* stream, WgfPlan* plan, bool* planned) {
+  sdhip_path_enter();   // (per item of a group: the name is the last item's)
   SDHIP_CHECK_ARG(it.x && it.dy && it.dw_packed, "conv2d_wgrad: null pointer");
   SDHIP_CHECK_ARG(dtype == SDHIP_F32 || dtype == SDHIP_BF16, "conv2d_wgrad: unknown dtype %d", dtype);
   SDHIP_CHECK_ARG(it.B > 0 && it.H > 0 && it.W > 0 && it.Cin > 0 && it.Cout > 0 && it.Ho > 0 && it.Wo > 0, "conv2d_wgrad: empty tensor");
@@ -542,7 +540,7 @@ static int wgrad_one(const SdhipWgradItem& it, int prezeroed, int dtype, void* s
   a.vec_dy = (it.lddy % V == 0) && (((uintptr_t)it.dy & 15) == 0);
   hipStream_t s = (hipStream_t)stream;
   const long n = (long)it.kd * sdhip_conv_packed_elems(it.Cout, it.Cin, T, dtype);
-  if (!prezeroed) {
+  if (!prezeroed && !sdhip_dry()) {
     if (sdhip_zero_async(it.dw_packed, n * sizeof(float), s) != hipSuccess) SDHIP_FAIL(SDHIP_ERR_LAUNCH, "conv2d_wgrad: memset failed");
     if (it.dbias && sdhip_zero_async(it.dbias, (size_t)it.Cout * sizeof(float), s) != hipSuccess) SDHIP_FAIL(SDHIP_ERR_LAUNCH, "conv2d_wgrad: memset failed");
   }
@@ -589,9 +587,10 @@ extern "C" int sdhip_conv2d_wgrad(const void* x, const void* dy, float* dw_packe
                                   int kh, int kw, int stride, int dil, int pad_t, int pad_l,
                                   int D, int Do, int kd, int sd, int pad_d,
                                   int in_relu, int groups, int prezeroed, int dtype, void* stream) {
+  sdhip_path_enter();
   const SdhipWgradItem it{x, dy, dw_packed, dbias, in_scale, in_shift, B, H, W, Cin, ldx, Ho, Wo, Cout, lddy,
                           kh, kw, stride, dil, pad_t, pad_l, D, Do, kd, sd, pad_d, in_relu, groups};   // field order = argument order
-  return wgrad_layer(it, prezeroed, dtype, stream, nullptr);
+  return sdhip_path_exit(wgrad_layer(it, prezeroed, dtype, stream, nullptr));
 }
 
 
@@ -677,13 +676,14 @@ int launch_wgf_group(std::vector<WgfPlan>& pls, size_t lo, size_t hi, hipStream_
 }  // namespace
 
 extern "C" int sdhip_conv2d_wgrad_group(const SdhipWgradItem* items, int n, int max_workgroups, int dtype, void* stream) {
+  sdhip_path_enter();
   SDHIP_CHECK_ARG(items && n > 0, "conv2d_wgrad_group: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   std::vector<WgfPlan> plans;
   plans.reserve(n);
   for (int i = 0; i < n; ++i) {
     const int rc = wgrad_layer(items[i], 1, dtype, stream, &plans);   // the group's buffers arrive zeroed
-    if (rc != SDHIP_OK) return rc;
+    if (rc != SDHIP_OK) return sdhip_path_exit(rc);
   }
   // buckets = instantiations, in order of first appearance; <= kWgfGroupMax layers per grid
   std::vector<char> done(plans.size(), 0);

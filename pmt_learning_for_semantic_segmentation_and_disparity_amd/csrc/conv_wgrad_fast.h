@@ -492,6 +492,8 @@ int plan_wgf(const WgfArgs& a, WgfPlan& pl) {
   if (lds > 160 * 1024) return kNotTaken;                 // caller tries a smaller tile
   if (!DMAX && hrounds > (MAXT == 1 ? (TH * TW) / 64 : 5)) return kNotTaken;             // register-path prefetch plan (XPF in the kernel)
   if (a.qb && (IWp % 64) && (64 % IWp)) return kNotTaken;   // packed rows: a lane must meet the same chunk in every load round
+  if (a.qb) SDHIP_CHOSE(kWgPacked, a.qb, DMAX);
+  else SDHIP_CHOSE(kWgFast, MAXT, MB, CIT, TH, TW, DMAX);
   static bool attr_set = false;
   if (lds > 64 * 1024 && !attr_set) {
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
@@ -537,40 +539,30 @@ inline int launch_wgf_plan(const WgfPlan& pl, hipStream_t s) {
   return SDHIP_OK;
 }
 
-// out == nullptr: launch now.  out != nullptr: only plan (the grouped entry point collects plans first).
-template <int TH, int TW, int MAXT, int MB, bool DMAX, int CIT = 4>
-int launch_wgf(const WgfArgs& a, hipStream_t s, WgfPlan* out) {
-  WgfPlan pl;
-  const int rc = plan_wgf<TH, TW, MAXT, MB, DMAX, CIT>(a, pl);
-  if (rc != 0) return rc;
-  if (out) { *out = pl; return SDHIP_OK; }
-  return launch_wgf_plan(pl, s);
-}
-
 // tile choice: wide maps 4x32, else 4x16; kNotTaken = nothing fits (caller falls back to the general kernel)
 template <int MAXT, int MB, bool DMAX, int CIT = 4>
-int launch_wgf_tile(const WgfArgs& a, hipStream_t s, WgfPlan* out) {
+int plan_wgf_tile(const WgfArgs& a, WgfPlan& pl) {
   if (a.Wo >= 24) {
-    const int rc = launch_wgf<4, 32, MAXT, MB, DMAX, CIT>(a, s, out);
+    const int rc = plan_wgf<4, 32, MAXT, MB, DMAX, CIT>(a, pl);
     if (rc != kNotTaken) return rc;
   }
-  return launch_wgf<4, 16, MAXT, MB, DMAX, CIT>(a, s, out);
+  return plan_wgf<4, 16, MAXT, MB, DMAX, CIT>(a, pl);
 }
 
 template <bool DMAX>
-int launch_wgf_taps(const WgfArgs& a, int T, hipStream_t s, WgfPlan* out) {
+int plan_wgf_taps(const WgfArgs& a, int T, WgfPlan& pl) {
   const bool narrow = a.Cout <= 32;   // 32 output channels per workgroup: the second wave group takes the odd taps instead
-  if (T == 1) return narrow ? launch_wgf_tile<1, 32, DMAX>(a, s, out) : launch_wgf_tile<1, 64, DMAX>(a, s, out);
+  if (T == 1) return narrow ? plan_wgf_tile<1, 32, DMAX>(a, pl) : plan_wgf_tile<1, 64, DMAX>(a, pl);
   const bool half = a.Cin <= 32 && !sdhip_diag().wgrad_no_half;   // two input-channel tiles instead of four (CIT)
   if (a.tpb <= 9) {
-    if (half) return narrow ? launch_wgf_tile<9, 32, DMAX, 2>(a, s, out) : launch_wgf_tile<9, 64, DMAX, 2>(a, s, out);
-    return narrow ? launch_wgf_tile<9, 32, DMAX>(a, s, out) : launch_wgf_tile<9, 64, DMAX>(a, s, out);
+    if (half) return narrow ? plan_wgf_tile<9, 32, DMAX, 2>(a, pl) : plan_wgf_tile<9, 64, DMAX, 2>(a, pl);
+    return narrow ? plan_wgf_tile<9, 32, DMAX>(a, pl) : plan_wgf_tile<9, 64, DMAX>(a, pl);
   }
-  return half ? launch_wgf_tile<25, 32, DMAX, 2>(a, s, out) : launch_wgf_tile<25, 32, DMAX>(a, s, out);
+  return half ? plan_wgf_tile<25, 32, DMAX, 2>(a, pl) : plan_wgf_tile<25, 32, DMAX>(a, pl);
 }
 
 // chunk-packed 1x1 weight gradient (WgfArgs::qb): 4x16 pixel tiles, up to 4 chunks as taps
 template <bool DMAX>
-int launch_wgf_packed(const WgfArgs& a, hipStream_t s, WgfPlan* out) { return launch_wgf<4, 16, 4, 64, DMAX>(a, s, out); }
+int plan_wgf_packed(const WgfArgs& a, WgfPlan& pl) { return plan_wgf<4, 16, 4, 64, DMAX>(a, pl); }
 
 }  // namespace

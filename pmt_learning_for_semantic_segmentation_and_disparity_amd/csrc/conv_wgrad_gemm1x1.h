@@ -233,6 +233,7 @@ inline int plan_wg1(const WgfArgs& f, WgfPlan& pl) {
   a.nq_tot = f.nq; a.nq = sdhip_cdiv(f.nq, 4);
   a.tpb = 1; a.ntg = 1; a.qb = 0; a.qsh = 0;
   const size_t lds = 2 * (size_t)kWg1Stage;
+  SDHIP_CHOSE(kWgGemm1x1);
   static bool attr_set = false;
   if (!attr_set) {
     if (hipFuncSetAttribute((const void*)wgrad_gemm1x1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||

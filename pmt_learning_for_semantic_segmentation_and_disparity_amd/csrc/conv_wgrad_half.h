@@ -193,6 +193,7 @@ int plan_wg32(const WgfArgs& a, WgfPlan& pl) {
   auto kern = wgrad32_kernel<KD>;
   auto gkern = wgrad32_group_kernel<KD>;
   constexpr size_t lds = 2 * (size_t)(KD * 14 + 8) * 1024;
+  SDHIP_CHOSE(kWgHalf32);
   static bool attr_set = false;
   if (lds > 64 * 1024 && !attr_set) {
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||

@@ -153,6 +153,7 @@ inline int launch_single_wgrad(SingleWgArgs a, hipStream_t s) {
   if (dpw < 1) return kNotTaken;                        // halo does not fit: the caller takes another kernel
   a.dpw = dpw; a.zsegs = sdhip_cdiv(a.D, dpw);
   if ((long)a.B * a.zsegs > 65535) return kNotTaken;
+  SDHIP_CHOSE(kWgSingle);
   dim3 grid(sdhip_cdiv(a.H, 8) * sdhip_cdiv(a.W, 32), a.B * a.zsegs);
   hipLaunchKernelGGL(conv_single_wgrad_kernel, grid, dim3(256), 0, s, a);
   SDHIP_LAUNCH_CHECK();

@@ -2,6 +2,7 @@
 // error channel.  No global mutable state besides the per-thread message, so
 // entry points are re-entrant from autograd's backward threads.
 #include "sdhip_common.h"
+#include "conv_common.h"
 #include <vector>
 
 #define SDHIP_ABI_VERSION 2
@@ -17,6 +18,45 @@ void sdhip_set_error(const char* fmt, ...) {
 
 extern "C" int sdhip_abi_version(void) { return SDHIP_ABI_VERSION; }
 extern "C" const char* sdhip_last_error(void) { return g_err; }
+
+// ---- which kernel the conv dispatch chose (conv_common.h: SDHIP_CHOSE) ----------------------------------------------
+static thread_local SdhipPath g_path = {kPathNone, {0}};
+static thread_local bool g_dry = false;
+static thread_local char g_path_name[96] = "";
+
+SdhipPath& sdhip_path() { return g_path; }
+bool sdhip_dry() { return g_dry; }
+extern "C" void sdhip_dispatch_dry(int on) { g_dry = on != 0; }
+
+extern "C" const char* sdhip_last_path(void) {
+  const int* v = g_path.v;
+  char* o = g_path_name;
+  const size_t n = sizeof(g_path_name);
+  switch (g_path.family) {
+    case kPathNone: return "";
+    case kPathUnsupported: return "unsupported";
+    case kFwdThin: case kWgThin: return "thin";
+    case kFwdFanin: return "fanin";
+    case kFwdFanout: return "fanout";
+    case kFwdGemm: return "gemm";
+    case kFwdPoint: return "point";
+    case kFwdGrow: return "grow";
+    case kFwdMid: return "mid";
+    case kWgSingle: return "single";
+    case kWgHalf32: return "half32";
+    case kWgGemm1x1: return "gemm1x1";
+    case kFwdBand: snprintf(o, n, "band(%dx%d%s%s)", v[0], v[0], v[1] > 1 ? "x3" : "", v[2] ? ", bx" : ""); break;
+    case kFwdFast:
+      snprintf(o, n, "fast(%dx%d, ks %d, %s, %s%s)", v[0], v[1], v[2], v[3] == 0 ? "single-stage" : v[3] == 1 ? "tap-grouped" : "chunked", v[4] ? "dma" : "register", v[5] ? ", tail" : "");
+      break;
+    case kFwdGeneric: snprintf(o, n, "generic(%dx%d, %s)", v[0], v[1], v[2] ? "per_tap" : v[3] ? "prefetch" : "plain"); break;
+    case kWgPacked: snprintf(o, n, "fast(packed x%d, %s)", v[0], v[1] ? "dma" : "register"); break;
+    case kWgFast: snprintf(o, n, "fast(taps %d, mb %d, cit %d, %dx%d, %s)", v[0], v[1], v[2], v[3], v[4], v[5] ? "dma" : "register"); break;
+    case kWgGeneric: snprintf(o, n, "generic(taps %d, mb %d, %dx%d)", v[0], v[1], v[2], v[3]); break;
+    default: return "?";
+  }
+  return o;
+}
 
 // ---- diagnostic / tuning switches: read ONCE (library load), never per launch --------------------------------------
 // A stray environment variable must not silently change numerics mid-run: the table is filled at load, a set DIAG switch

@@ -5,7 +5,6 @@ Tensors keep the reference's logical NCHW shapes but live in channels-last
 returns the pixel stride the C ABI wants.  Nothing in this file computes on the
 CPU or through ATen kernels: a non-GPU tensor is an error.
 """
-import os
 import torch
 
 from . import _lib
@@ -872,33 +871,19 @@ class BNSlot:
         self.gptr = 0
 
 
-def _band_bx_form(spec, Bimg, H, W, Cin, Cout, has_addend, ldg, bn_slot):
-    """'5x5' / '3x3' if the data gradient of this convolution (Cout channels in at pixel stride ldg, Cin channels out) runs on
-    the persistent whole-CU kernel with the BatchNorm-backward sums in its epilogue (path_band2d of csrc/conv_fwd.hip accepts
-    the bnbwd call; conv_band_bx_kernel), else None.  Mirrors that predicate (band_common_ok included): 5x5 with <= 32 or 64
-    channels in / 3x3 with <= 32, 32 .. 64 (padded) channels out, at least 192 tiles of 16 x 32, u at a pixel stride that is
-    a multiple of 8 and 16-byte aligned, the incoming gradient within the kernel's 2 GiB buffer range, not the one form that
-    is not built (5x5, > 32 out, addend) — and none of the switches set that send such a call past the kernel: a shape
-    Python took for this kernel's and C++ refused would run the halo-tile fused form, which at full resolution is slower
-    than two launches."""
-    env = os.environ
-    if env.get("SDHIP_CONV_NO_BAND_BX") or env.get("SDHIP_CONV_NO_BAND") or env.get("SDHIP_CONV_GENERIC"):
-        return None
-    if spec.stride != 1 or spec.dil != 1 or spec.kh != spec.kw or Cout % 8 or Cin % 8 or ldg % 8:
-        return None
-    if bn_slot is None or bn_slot.u is None or bn_slot.ldu % 8 or bn_slot.u.data_ptr() % 16:
-        return None
-    if Bimg * spec.Ho * spec.Wo * ldg * 2 >= 0x7fffff00:
-        return None
-    mpad = (Cin + 15) & ~15
-    tiles = -(-H // 16) * -(-W // 32) * Bimg
-    if not (32 <= mpad <= 64 and 192 <= tiles < 65536):
-        return None
-    if spec.kh == 5 and (Cout <= 32 or Cout == 64) and not (mpad > 32 and has_addend):
-        return '5x5'
-    if spec.kh == 3 and Cout <= 32 and not env.get("SDHIP_CONV_NO_BAND3"):
-        return '3x3'
-    return None
+_BAND_BX_NAMES = {"band(5x5, bx)": "5x5", "band(3x3, bx)": "3x3"}     # sdhip_last_path -> the form's word in BAND_BX_FORMS
+_DRY_Y = ctypes_ptr(1 << 20)                # stand-ins for tensors that do not exist yet when the dispatch is asked: it
+_DRY_SUMS = ctypes_ptr(2 << 20)             # reads their alignment only, and the allocator's is 256 bytes
+
+
+def _bnbwd_band_form(args):
+    """'5x5' / '3x3' if the library runs the sdhip_conv2d_fwd_bnbwd call with these arguments on the persistent whole-CU
+    kernel with the BatchNorm-backward sums in its epilogue (conv_band_bx_kernel), else None.  The library's own dispatch
+    answers, in dry mode: nothing is launched, no operand is read.  A call the entry point refuses outright (channel counts or
+    pixel strides that are no multiple of 4: SDHIP_ERR_ARG) runs on no kernel: None, and the caller never makes it."""
+    with _lib.dispatch_dry():
+        rc = _lib._lib.sdhip_conv2d_fwd_bnbwd(*args)
+    return _BAND_BX_NAMES.get(_lib.last_path()) if rc == 0 else None
 
 
 def _conv_backward(ctx_spec, xv, ldx, weight, g, ldg, in_scale, in_shift, in_relu, groups, need_x, need_w, bias=None, acc_into=None,
@@ -919,22 +904,25 @@ def _conv_backward(ctx_spec, xv, ldx, weight, g, ldg, in_scale, in_shift, in_rel
         # at 128x256: +3.5 against 18).  The persistent kernel (conv_band.h) has an epilogue of its own that issues u in
         # the layout of its stores, in one batch per tile — a stage ahead where the registers allow it: shapes on that
         # kernel fuse whatever their size, each form behind its own switch (BAND_BX_FORMS; DESIGN.md section 7 has the table)
-        band_form = _band_bx_form(spec, Bimg, H, W, Cin, Cout, acc_into is not None or addend is not None, ldg, bn_slot) if spec.kd == 1 and spec.D == 1 else None
+        # — which kernel the call would run on is the library's to say: it is asked, in dry mode, with the call's own arguments
         if (bn_slot is not None and bn_slot.u is not None and bn_slot.C == Cin and xv.dtype == torch.bfloat16 and spec.stride == 1
-                and spec.sd == 1 and spec.kd == 1 and spec.D == 1 and tuple(bn_slot.u.shape) == (Bimg, Cin, H, W)
-                and (band_form in BAND_BX_FORMS or (spec.kh * spec.kw <= 9 and Bimg * H * W * Cin * 2 <= BN_SLOT_MAX_BYTES))):
+                and spec.sd == 1 and spec.kd == 1 and spec.D == 1 and tuple(bn_slot.u.shape) == (Bimg, Cin, H, W)):
             # the input of this convolution was relu(bn(u)): the launch that writes its gradient also takes that
             # BatchNorm's two backward reductions (and adds a parked skip gradient on the way)
             other = acc_into if acc_into is not None else addend
-            gpost, ldgp = alloc_nhwc(Bimg, Cin, H, W, xv.dtype, xv.device)
-            sums = _zeros((NREP, bn_slot.groups, 2, Cin), torch.float64, xv.device)[0]
             ov, ldo = nhwc_view(other) if other is not None else (None, 0)
-            fused_bn = try_call("sdhip_conv2d_fwd_bnbwd", ptr(g), ptr(wd), ptr(gpost), ptr(sums), Cin, NREP, ptr(bn_slot.u), bn_slot.ldu,
-                                ptr(bn_slot.scale), ptr(bn_slot.shift), ptr(ov), ldo, B, spec.Ho, spec.Wo, Cout, ldg, H, W, Cin, ldgp,
-                                spec.kh, spec.kw, spec.dil, spec.dil * (spec.kh - 1) - spec.pad_t,
-                                spec.dil * (spec.kw - 1) - spec.pad_l, bn_slot.groups, 0, dt, stream_ptr())
-            if fused_bn:
-                bn_slot.sums, bn_slot.gptr = sums, gpost.data_ptr()
+
+            def bnbwd_args(y, ldy, sums):
+                return (ptr(g), ptr(wd), y, sums, Cin, NREP, ptr(bn_slot.u), bn_slot.ldu, ptr(bn_slot.scale), ptr(bn_slot.shift), ptr(ov), ldo,
+                        B, spec.Ho, spec.Wo, Cout, ldg, H, W, Cin, ldy, spec.kh, spec.kw, spec.dil, spec.dil * (spec.kh - 1) - spec.pad_t,
+                        spec.dil * (spec.kw - 1) - spec.pad_l, bn_slot.groups, 0, dt, stream_ptr())
+            if ((spec.kh * spec.kw <= 9 and Bimg * H * W * Cin * 2 <= BN_SLOT_MAX_BYTES)
+                    or _bnbwd_band_form(bnbwd_args(_DRY_Y, (Cin + 7) & ~7, _DRY_SUMS)) in BAND_BX_FORMS):     # (the pixel stride alloc_nhwc gives)
+                gpost, ldgp = alloc_nhwc(Bimg, Cin, H, W, xv.dtype, xv.device)
+                sums = _zeros((NREP, bn_slot.groups, 2, Cin), torch.float64, xv.device)[0]
+                fused_bn = try_call("sdhip_conv2d_fwd_bnbwd", *bnbwd_args(ptr(gpost), ldgp, ptr(sums)))
+                if fused_bn:
+                    bn_slot.sums, bn_slot.gptr = sums, gpost.data_ptr()
         # Conv3d(k=3, stride 2, padding 1) over even extents (hourglass conv1 / conv3, stackhourglass.py:13-19): its data gradient is
         # the transposed convolution that doubles every extent — eight sub-pixel phases of 1..8 taps over dY itself (27 taps per dY
         # voxel), not a stride-1 correlation over the zero-stuffed dY (8 x 27: seven of eight products are zeros)

@@ -36,6 +36,45 @@ def test_abi_version_and_error_channel():
     assert rc < 0 and b"null" in _lib._lib.sdhip_last_error()
 
 
+def _fwd(_lib, x=ctypes.c_void_p(1 << 20), w=ctypes.c_void_p(2 << 20), y=ctypes.c_void_p(3 << 20), Cin=16, stream=None):
+    """sdhip_conv2d_fwd, bf16 3x3 16 -> 16 on 2 x 9 x 19; by default with made-up 256-byte-aligned operand addresses."""
+    return _lib._lib.sdhip_conv2d_fwd(x, w, y, None, None, None, None, 0, 1, 2, 9, 19, Cin, 16, 9, 19, 16, 16,
+                                      3, 3, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 1, 0, 0, _lib.BF16, stream)
+
+
+def test_dry_dispatch_names_a_kernel_without_a_gpu():
+    """In dry mode an entry point validates and dispatches and launches nothing: on a machine without a GPU a launch attempt
+    returns SDHIP_ERR_LAUNCH, so the 0 here shows there was none, and no made-up address was dereferenced."""
+    from pmt_learning_for_semantic_segmentation_and_disparity_amd import _lib
+    with _lib.dispatch_dry():
+        assert _fwd(_lib) == 0 and _lib.last_path().startswith("fast(4x16"), _lib.last_path()
+        assert _fwd(_lib, x=ctypes.c_void_p((1 << 20) + 2)) == 0 and _lib.last_path().startswith("generic("), _lib.last_path()     # x misaligned
+        assert _fwd(_lib, Cin=0) == _lib.ERR_ARG and _lib.last_path() == ""                                                                                   # validation as usual
+        P = [ctypes.c_void_p(i << 20) for i in range(1, 5)]
+        assert _lib._lib.sdhip_conv2d_fwd_add(*P, 16, 2, 9, 19, 16, 16, 9, 19, 16, 16, 3, 3, 1, 1, _lib.BF16, None) == _lib.ERR_UNSUPPORTED
+    assert _lib.last_path() == "unsupported"      # the name outlives the mode
+
+
+def test_dry_mode_ends_with_its_block():
+    """dispatch_dry() switches the flag off on the way out, by an exception too: the next call launches again — without a
+    GPU that is an SDHIP_ERR_LAUNCH; with one it is run on real tensors and writes y."""
+    import pytest
+    import torch
+    from pmt_learning_for_semantic_segmentation_and_disparity_amd import _lib
+    with pytest.raises(KeyError):
+        with _lib.dispatch_dry():
+            assert _fwd(_lib) == 0
+            raise KeyError("out")
+    if not torch.cuda.is_available():
+        assert _fwd(_lib) == _lib.ERR_LAUNCH
+        return
+    x, y = torch.zeros(2, 9, 19, 16, dtype=torch.bfloat16, device="cuda"), torch.full((2, 9, 19, 16), float("nan"), dtype=torch.bfloat16, device="cuda")
+    w = torch.zeros(_lib.packed_elems(16, 16, 9, _lib.BF16), dtype=torch.bfloat16, device="cuda")
+    assert _fwd(_lib, _lib.ptr(x), _lib.ptr(w), _lib.ptr(y), stream=_lib.stream_ptr()) == 0
+    torch.cuda.synchronize()
+    assert bool((y == 0).all()) and _lib.last_path().startswith("fast(4x16")
+
+
 def test_product_has_no_cpu_path():
     import pytest
     import torch
@@ -103,6 +142,8 @@ def test_pinned_derivations():
     assert L.sdhip_last_error.restype is ctypes.c_char_p and S["sdhip_last_error"] == []
     assert L.sdhip_diag_reload.restype is None and S["sdhip_diag_reload"] == []
     assert L.sdhip_abi_version.restype is ctypes.c_int and S["sdhip_abi_version"] == []
+    assert L.sdhip_dispatch_dry.restype is None and S["sdhip_dispatch_dry"] == _types("i")
+    assert L.sdhip_last_path.restype is ctypes.c_char_p and S["sdhip_last_path"] == []
 
 
 def test_unknown_types_raise():

@@ -53,7 +53,7 @@ def _with_nan_tail(t, C, ld):
 
 def _run_mode0(B, H, W, Cin, Cout, groups, with_add, env):
     from pmt_learning_for_semantic_segmentation_and_disparity_amd import ops
-    from pmt_learning_for_semantic_segmentation_and_disparity_amd._lib import call, ptr, stream_ptr, dtype_code
+    from pmt_learning_for_semantic_segmentation_and_disparity_amd._lib import call, ptr, stream_ptr, dtype_code, last_path
     dev, bf = "cuda", torch.bfloat16
     g = torch.Generator().manual_seed(B * 1000 + H * 37 + W + Cout)
     npix, ld = B * H * W, Cout + 8
@@ -77,6 +77,7 @@ def _run_mode0(B, H, W, Cin, Cout, groups, with_add, env):
         ops._conv_launch(x, Cin, wd, y0, Cout, None, None, None, None, B, H, W, Cin, H, W, Cout, 3, 3, 1, 1, 1, 1, False, 1, 0, False)
         call("sdhip_conv2d_fwd_bnbwd", ptr(x), ptr(wd), ptr(y1), ptr(sums), Cout, ops.NREP, ptr(u), ld, ptr(sc), ptr(sh),
              ptr(a), ld if with_add else 0, B, H, W, Cin, Cin, H, W, Cout, ld, 3, 3, 1, 1, 1, groups, 0, dt, stream_ptr())
+        assert last_path().startswith("fast(8x32" if "SDHIP_CONV_BIG" in env else "fast(4x16"), (last_path(), env)     # the kernel under test ran
         torch.cuda.synchronize()
     ref = y0
     if with_add:
@@ -100,7 +101,7 @@ def _run_mode0(B, H, W, Cin, Cout, groups, with_add, env):
 
 def _run_mode1(B, H, W, K, C, Ct, groups, env):
     from pmt_learning_for_semantic_segmentation_and_disparity_amd import ops
-    from pmt_learning_for_semantic_segmentation_and_disparity_amd._lib import call, ptr, stream_ptr, dtype_code
+    from pmt_learning_for_semantic_segmentation_and_disparity_amd._lib import call, ptr, stream_ptr, dtype_code, last_path
     dev, bf = "cuda", torch.bfloat16
     g = torch.Generator().manual_seed(C * 100 + H * 7 + W)
     npix = B * H * W
@@ -126,6 +127,7 @@ def _run_mode1(B, H, W, K, C, Ct, groups, env):
              npix, C, groups, 1, 1, 0, dt, stream_ptr())
         call("sdhip_conv2d_fwd_bnbwd", ptr(x), ptr(wd), ptr(gs), ptr(both), C, ops.NREP, ptr(slab), Ct, ptr(sc), ptr(sh), ptr(gs), Ct,
              B, H, W, K, K, H, W, C, Ct, 1, 1, 1, 0, 0, groups, 1, dt, stream_ptr())
+        assert last_path().startswith("fast(8x32" if "SDHIP_CONV_BIG" in env else "fast(4x16"), (last_path(), env)
         torch.cuda.synchronize()
     a, b = gs[:, :C].float(), gs_ref.float()
     err, bound = (a - b).abs().max().item(), 3e-2 * b.abs().max().item()

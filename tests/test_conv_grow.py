@@ -3,8 +3,9 @@ into 32, on small maps: conv2 of the DenseNet dense layers), through sdhip_conv2
 sdhip_conv2d_fwd_bnpro (the consumer-side BatchNorm finalize), against the float64 references and bounds of
 tests/test_conv_kernels.py.
 
-Without a GPU: grow_taken() mirrors path_grow of csrc/conv_fwd.hip term by term; it names every case below, rejects each
-single violation of the predicate and every case of the tables of test_conv_kernels.py (whose tile assumptions therefore hold).
+Without a GPU: the library's own dispatch, asked in dry mode (test_conv_kernels.chosen: sdhip_dispatch_dry / sdhip_last_path),
+takes the kernel for every case below, declines each single violation of path_grow's predicate, one step past each of its
+limits, and every case of the tables of test_conv_kernels.py.
 With a GPU: x and y are channel slices of NaN-filled slabs, so a NaN in y is a padding lane, a dead channel or a pixel past
 the image that reached an MFMA; the draw keeps |shift| >= 0.25 with both signs of scale and shift, so a padding pixel that
 was normalised instead of zeroed is far outside the bound.  Shapes are the smallest at which the kernel takes another
@@ -34,7 +35,6 @@ from test_conv_kernels import (BF16, BNPRO_COMBOS, EPS32, F32, MOM32, P, StatBuf
 
 NO_GROW = {"SDHIP_CONV_NO_GROW": "1"}
 SLICE = (64, 160)       # y as channels [64, 96) of a 160-channel slab, as a dense layer writes its growth channels
-GROW_MAX_MAP, GROW_MAX_WG = 2048, 512     # kGrowMaxMap, kGrowMaxWG of csrc/conv_grow.h
 
 
 def gr(name, **kw):
@@ -50,48 +50,35 @@ CASES += [gr("map16x32", H=16, W=32, B=2, groups=1, stats=(3, 0)), gr("map3x5", 
 BYNAME = {c.name: c for c in CASES}
 
 
-def _lay(lay, C):
-    return R.layout(lay, C) if isinstance(lay, str) else lay
-
-
-def grow_taken(c, dtype, env=None):
-    """Mirror of path_grow (csrc/conv_fwd.hip)."""
-    env = dict(c.env, **(env or {}))
-    Cin = K.cin_of(c, dtype)
-    (kx, ldx), (ky, ldy) = _lay(c.lx, Cin), _lay(c.ly, c.Cout)
-    return bool(isbf(dtype) and c.pro is not None and c.stats is not None and not c.bias and c.act == 0 and not c.acc and
-                c.kh == 3 and c.kw == 3 and c.kd == 1 and c.D == 1 and c.Do == 1 and c.stride == 1 and c.dil == 1 and
-                c.pad_t == 1 and c.pad_l == 1 and c.Ho == c.H and c.Wo == c.W and
-                Cin % 32 == 0 and 64 <= Cin <= 256 and c.Cout == 32 and c.H * c.W <= GROW_MAX_MAP and
-                c.B * K.cdiv(c.H, 4) * K.cdiv(c.W, 16) <= GROW_MAX_WG and
-                ldx % 8 == 0 and (kx * 2) % 16 == 0 and ldy % 4 == 0 and (ky * 2) % 8 == 0 and c.H * c.W * ldx < 2 ** 31 and
-                "SDHIP_CONV_NO_GROW" not in env and "SDHIP_CONV_GENERIC" not in env)
+def on_grow(c, dtype, env=None):
+    """Does the dispatch of sdhip_conv2d_fwd (csrc/conv_fwd.hip: path_grow) run the case on conv_grow.h?"""
+    return K.chosen(c, dtype, env) == "grow"
 
 
 def test_grow_predicate():
     for c in CASES:
-        assert grow_taken(c, BF16), c.name
-        assert not grow_taken(c, F32), c.name
-        assert not grow_taken(c, BF16, NO_GROW) and not grow_taken(c, BF16, K.GENERIC_ENV), c.name
+        assert on_grow(c, BF16), c.name
+        assert not on_grow(c, F32), c.name
+        assert not on_grow(c, BF16, NO_GROW) and not on_grow(c, BF16, K.GENERIC_ENV), c.name
     for tag, kw in (("k1", dict(kh=1, kw=1)), ("k5", dict(kh=5, kw=5)), ("stride2", dict(stride=2)), ("dil2", dict(dil=2)),
                     ("cin48", dict(Cin=48)), ("cin288", dict(Cin=288)), ("cout24", dict(Cout=24)), ("cout64", dict(Cout=64)),
                     ("nopro", dict(pro=None)), ("nostats", dict(stats=None)), ("bias", dict(bias=1)), ("act", dict(act=1)), ("acc", dict(acc=1)),
                     ("lx_ldodd", dict(lx="ldodd")), ("ly_ldodd", dict(ly="ldodd")), ("lx_misal", dict(lx="misal")), ("ly_misal", dict(ly="misal")),
-                    ("map48x48", dict(H=48, W=48, B=2, groups=1)), ("grid", dict(B=2 * GROW_MAX_WG, H=1, W=1))):
-        assert not grow_taken(gr(tag, **kw), BF16), tag
+                    ("map48x48", dict(H=48, W=48, B=2, groups=1)), ("grid", dict(B=1024, H=1, W=1))):
+        assert not on_grow(gr(tag, **kw), BF16), tag
     pad0 = gr("pad0")
     pad0.update(pad_t=0, pad_l=0)
-    assert not grow_taken(pad0, BF16)
+    assert not on_grow(pad0, BF16)
     # the headline step's blocks (16 images): what was measured faster is taken
     for tag, H, W in (("block4", 8, 16), ("block3", 16, 32), ("block2", 32, 64)):      # block 2: 512 workgroups, the limit
-        assert grow_taken(gr(tag, B=16, H=H, W=W), BF16), tag
-    assert not grow_taken(gr("block1", B=16, H=64, W=128), BF16) and not grow_taken(gr("block2_B32", B=32, H=32, W=64), BF16)
+        assert on_grow(gr(tag, B=16, H=H, W=W), BF16), tag
+    assert not on_grow(gr("block1", B=16, H=64, W=128), BF16) and not on_grow(gr("block2_B32", B=32, H=32, W=64), BF16)
     for dtype in (F32, BF16):
         for c in K.FWD:
-            assert not grow_taken(c, dtype), c.name
+            assert not on_grow(c, dtype), c.name
         for Cin in (32, 96, 160):        # the shapes of test_conv_kernels.test_conv2d_fwd_bnpro
             for kh in (1, 3):
-                assert not grow_taken(mk("bnpro", kh=kh, kw=kh, Cin=Cin, Cout=24, pro="relu", lx="slab8", ly="slab8", stats=(3, 1)), dtype)
+                assert not on_grow(mk("bnpro", kh=kh, kw=kh, Cin=Cin, Cout=24, pro="relu", lx="slab8", ly="slab8", stats=(3, 1)), dtype)
 
 
 # =========================================================================== GPU: sdhip_conv2d_fwd with in_scale / in_shift
@@ -108,6 +95,7 @@ def test_conv_grow_fwd(name):
     got, ybits = {}, {}
     for tag, env in (("grow", {}), ("fast", NO_GROW), ("grow again", {})):
         y, sb = gpu_fwd(c, BF16, d, env)
+        assert K.family(K.last_path()) == tag.split()[0], (name, tag, K.last_path())
         label = "grow %s %s" % (name, tag)
         got[tag] = y.np()
         check(label, got[tag], ref, bound)
@@ -128,8 +116,6 @@ def test_conv_grow_bnpro(Cin):
     dtype, kh, pad = BF16, 3, 1
     for (G, nrep, pend_nrep, running, out_stats) in BNPRO_COMBOS:
         d = draw_bnpro(kh, Cin, G, nrep, pend_nrep, running, dtype, Cout=32)
-        assert grow_taken(mk("bnpro", kh=3, kw=3, B=d.B, H=d.H, W=d.W, Cin=Cin, Cout=32, pro="relu", groups=G, lx="slab8", ly="slab8",
-                             stats=(3, 1)), dtype)      # (the finalize form needs no statistics epilogue: the mirror speaks of the given-prologue form)
         c0 = Cin - 32
         r = CR.bnpro(d.x, d.w, d.in_stats, d.count, d.gamma, d.beta, d.rm0, d.rv0, EPS32, MOM32, G, d.pend, c0, pad, pad)
         S = r["in_stats"].sum(0)[:, :, :Cin] if pend_nrep else R.replica_sum(d.in_stats)
@@ -154,6 +140,7 @@ def test_conv_grow_bnpro(Cin):
             rm.p if rm else None, rv.p if rv else None, P(outs[0], 32), P(outs[1], 32), P(outs[2], 32), P(outs[3], 32),
             ctypes.c_double(d.count), ctypes.c_float(EPS32), ctypes.c_float(MOM32),
             d.B, d.H, d.W, Cin, x.ld, d.H, d.W, d.Cout, y.ld, kh, kh, pad, pad, G, code(dtype))
+        assert K.last_path() == "grow", (Cin, G, K.last_path())
         label = "grow bnpro Cin%d G%d nrep%d pend%d" % (Cin, G, nrep, pend_nrep)
         for key, o in zip(("scale", "shift", "mean", "invstd"), outs):
             check(label + " " + key, o[8:8 + G * Cin].double().cpu().numpy().reshape(G, Cin), r[key], bf_[key])

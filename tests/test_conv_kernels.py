@@ -2,11 +2,12 @@
 conv_fast.h, conv_wgrad.hip, conv_wgrad_fast.h), entry point by entry point, against the float64 references of tests/convops_ref.py.
 
 Without a GPU: the references compose to the torch operations (F.conv2d / conv3d on explicitly padded input, autograd's
-weight and data gradients, F.conv_transpose3d from the eight phases, BatchNorm2d(train) -> ReLU -> conv), a Python mirror of
-the dispatch predicates names the kernel every case of the tables below runs on and a test asserts that the tables reach
-every fast and generic sub-branch in both dtypes, and the comparator rejects a list of plausible wrong references at the
-very bounds the GPU tests use.  With a GPU (marker `gpu`): every entry point is called through the C ABI on inputs rounded
-to the dtype under test, each stage on exact inputs, tensors as channel slices of NaN-filled slabs (the lanes [C, ld) of
+weight and data gradients, F.conv_transpose3d from the eight phases, BatchNorm2d(train) -> ReLU -> conv), the library's own
+dispatch, asked in dry mode (chosen(): sdhip_dispatch_dry / sdhip_last_path — it launches nothing), names the kernel every
+case of the tables below runs on and a test asserts that the tables reach every fast and generic sub-branch in both dtypes,
+and the comparator rejects a list of plausible wrong references at the very bounds the GPU tests use.  With a GPU (marker
+`gpu`): every entry point is called through the C ABI on inputs rounded to the dtype under test (sdhip_last_path after the
+launch must name the kernel the case is meant for), each stage on exact inputs, tensors as channel slices of NaN-filled slabs (the lanes [C, ld) of
 every pixel hold NaN: a NaN in a result is a kernel that relies on zero weights), and compared with the reference within a
 bound derived from the rounding model below.  No element is excluded from any comparison.
 
@@ -20,7 +21,7 @@ Bounds (u = 2^-24; A = sum |w| |pro(x)| over the n = Cin * kh * kw * kd terms of
                 + half_ulp_bf16(|z| (1 + u)); propagated as sum |w| e_z (ReLU 1-Lipschitz)
   statistics    against f64 sums of the GPU's OWN stored y: a workgroup sums its TH x TW tile in f32 (NT_PIX values per lane,
                 the 16 lanes of an MFMA row by DPP / shuffles, the 4 waves through LDS) before the f64 atomic:
-                TH TW u sum |y| (sum y^2), tile from the dispatch mirror
+                TH TW u sum |y| (sum y^2), tile from the name of the kernel that ran
   weight grad   npix u sum |dy pro(x)| per element, npix = B Do Ho Wo (f32 MFMA accumulation, then f32 atomics in any order),
                 + sum |dy| e_z for a prologue; dbias: npix u sum |dy|
   bnpro         per-channel vectors: b_finalize (the bounds tests/test_bn_kernels.py applies to sdhip_bn_finalize); y: the
@@ -203,178 +204,64 @@ def wg_cases():
 WG = wg_cases()
 
 
-# =========================================================================== mirror of the dispatch predicates
-def _addr_ok(lay, dtype, align):
-    """Is the first element of a slice with this layout `align`-byte aligned?  (torch allocations are 256-byte aligned.)"""
-    k, _ = R.layout(lay, 8)
-    return (k * (2 if isbf(dtype) else 4)) % align == 0
+# =========================================================================== asking the library which kernel it chooses
+BASE_ADDR = 1 << 20     # a made-up 256-byte-aligned allocation, as torch's are: dry mode looks at alignment and at nothing behind it
 
 
-def fwd_path(c, dtype, env=None):
-    """Mirror of conv2d_fwd_impl (csrc/conv_fwd.hip, conv_plan and the chain of path_* functions: the block-width choice,
-    `big`, the thin / fan-in / fan-out / GEMM / band conditions, the fast path's tile loop and the generic kernel's) with
-    the default tuning values of csrc/runtime.hip (tune_big 512, tune_split 1024, tune_s2_small 1) and fanin_ok / fanout_ok
-    (csrc/conv_thin.h), gemm1x1_ok (csrc/conv_gemm.h), band_ok (csrc/conv_band.h).  Returns (name, tile (th, tw))."""
-    env = dict(c.env, **(env or {}))
-    bf = isbf(dtype)
-    V, es, CKh = (8, 2, 64) if bf else (4, 4, 32)
-    Cin, Cout = cin_of(c, dtype), c.Cout
-    _, ldx = R.layout(c.lx, Cin)
-    _, ldy = R.layout(c.ly, Cout)
-    x16, y_al = _addr_ok(c.lx, dtype, 16), _addr_ok(c.ly, dtype, 4 * es)
-    kh, kw, kd, s, d, T = c.kh, c.kw, c.kd, c.stride, c.dil, c.kh * c.kw
-    H, W, Ho, Wo, B, D, Do = c.H, c.W, c.Ho, c.Wo, c.B, c.D, c.Do
-    in_scale, acc, stats = c.pro is not None, c.acc, c.stats is not None
-    Mpad = cdiv(Cout, 16) * 16
-    vec_in = ldx % V == 0 and x16
-    vec_out = ldy % 4 == 0 and y_al
-    bn = 16
-    for cand in (128, 64, 32):
-        if cdiv(Mpad, cand) * cand * 4 <= Mpad * 5:
-            bn = cand
-            break
-    if kh * kw * kd * Cin <= 128 and Mpad <= 128:
-        bn = 128 if Mpad > 64 else 64 if Mpad > 32 else 32 if Mpad > 16 else 16
-    blocks_big = cdiv(Ho, 8) * cdiv(Wo, 32) * B * Do * cdiv(Mpad, bn)
-    conv_big, generic, no_thin = "SDHIP_CONV_BIG" in env, "SDHIP_CONV_GENERIC" in env, "SDHIP_CONV_NO_THIN" in env
-    big = (blocks_big >= 512 and Wo >= 24) or conv_big
-    if s == 2 and kd > 1 and not conv_big:
-        big = False
-    if not big:
-        px_blocks = cdiv(Ho, 4) * cdiv(Wo, 16) * B * Do
-        while bn > 32 and px_blocks * cdiv(Mpad, bn) < 1024:
-            bn >>= 1
-    rows = min(Mpad, bn)
-    cpr = 4 if Cin <= CKh // 2 else 8
-    per_tap_any = (kh > 1 or kw > 1) and d >= 4 and kd == 1
-    flat = kd == 1 and D == 1 and Do == 1
-    if (Cout == 1 and Cin <= V and vec_in and s == 1 and flat and not in_scale and not acc and T <= 49 and
-            Ho == H + 2 * c.pad_t - d * (kh - 1) and Wo == W + 2 * c.pad_l - d * (kw - 1) and not no_thin):
-        return "thin", None
-    fanin_ok = (Cout == 1 and Cin % 8 == 0 and Cin >= 16 and s == 1 and d == 1 and c.sd == 1 and T * kd <= 32 and ldx % 8 == 0 and x16 and
-                ((kd == 3 and Cin <= 32) or (kd == 1 and Cin <= 64)))
-    if bf and fanin_ok and not in_scale and not acc and not stats and not no_thin:
-        return "fanin", None
-    if (bf and Cin == 1 and 8 <= Cout <= 64 and T * kd <= 32 and s == 1 and c.sd == 1 and ldy % 4 == 0 and not in_scale and not acc and
-            not stats and not c.bias and c.act == 0 and not no_thin):
-        return "fanout", None
-    if (bf and kh == 1 and kw == 1 and flat and s == 1 and c.pad_t == 0 and c.pad_l == 0 and not acc and not generic and
-            "SDHIP_CONV_NO_GEMM" not in env and B * H * W >= (65536 if in_scale else 32768) and ldx % 8 == 0 and x16 and ldy % 4 == 0):
-        return "gemm", None
-    band5, band3 = kh == 5 and kw == 5 and (Cin <= 32 or Cin == 64), kh == 3 and kw == 3 and Cin <= 32
-    ntl = cdiv(Ho, 16) * cdiv(Wo, 32) * B * Do
-    if (bf and (((band5 or band3) and flat and 32 <= Mpad <= 64) or (kh == 3 and kw == 3 and kd == 3 and c.sd == 1 and Cin <= 32 and Mpad == 32)) and
-            s == 1 and d == 1 and not in_scale and Cin % 8 == 0 and 192 <= ntl < 65536 and not generic):
-        return "band", None
-    if not per_tap_any and ldx % V == 0 and x16 and vec_out and not generic:
-        ks = 1 if cpr == 4 else 2
-        rb, ppr = 64 * ks, 256 // (4 * ks)
-        tail = Cin % V != 0
-        dma = not in_scale and not tail
-        fbig = big
-        for _ in range(2):
-            th, tw = (8, 32) if fbig else (4, 16)
-            IH, IW = (th - 1) * s + (kh - 1) * d + 1, (tw - 1) * s + (kw - 1) * d + 1
-            IWp = (IW + 7) & ~7
-            hrows = cdiv(IH * IWp, ppr) * ppr
-            nqq = kd * (cdiv(Cin, CKh) if ks == 2 else 1)
-            hb = hrows * rb * (1 if (fbig or nqq == 1) else 2)
-            if not fbig and hrows > (6 if (dma and ks == 1) else 5) * ppr:
-                fbig = True
-                continue
-            wbuf = lambda tg: cdiv(tg * bn, ppr) * ppr * rb      # noqa: E731
-            tg = T
-            if nqq == 1 and hb + wbuf(T) <= 80 * 1024:
-                lds = hb + wbuf(T)
-            else:
-                while tg > 1 and hb + 2 * wbuf(tg) > 80 * 1024:
-                    tg -= 1
-                lds = hb + 2 * wbuf(tg)
-            if lds > 160 * 1024:
-                if not fbig:
-                    break
-                fbig = False
-                continue
-            stages = "single-stage" if nqq * cdiv(T, tg) == 1 else "tap-grouped" if tg < T else "chunked"
-            return "fast(%dx%d, ks %d, %s, %s%s)" % (th, tw, ks, stages, "dma" if dma else "register", ", tail" if tail else ""), (th, tw)
-    for _ in range(2):
-        th, tw = (8, 32) if big else (4, 16)
-        eh, ew = (0, 0) if per_tap_any else ((kh - 1) * d, (kw - 1) * d)
-        halo = ((th - 1) * s + eh + 1) * ((tw - 1) * s + ew + 1) * 128
-        pf = (not per_tap_any and not big and vec_in and Cin % V == 0 and (halo // 128) * cpr <= 1024 and 2 * halo + 2 * bn * 128 <= 80 * 1024)
-        tg = 1 if per_tap_any else max(1, min(T, 1024 // (rows * cpr)))
-        hb = halo * (2 if pf else 1)
-        while tg > 1 and hb + 2 * tg * bn * 128 > 80 * 1024:
-            tg -= 1
-        if hb + 2 * tg * bn * 128 > 160 * 1024:
-            if big:
-                big = False
-                continue
-            return "unsupported", None
-        return "generic(%dx%d, %s)" % (th, tw, "per_tap" if per_tap_any else "prefetch" if pf else "plain"), (th, tw)
-    return "unsupported", None
+def _slice_addr(slot, lay, C, dtype):
+    """Address and pixel stride of a tensor's first element inside slab `slot`: the slab's base plus the slice offset."""
+    k, ld = R.layout(lay, C) if isinstance(lay, str) else lay
+    return ctypes.c_void_p(BASE_ADDR * (slot + 1) + k * (2 if isbf(dtype) else 4)), ld
 
 
-def wg_path(c, dtype, env=None):
-    """Mirror of wgrad_one / wgrad_layer (csrc/conv_wgrad.hip: the thin, single-map, half-row, chunk-packed and tap-kernel
-    conditions, launch_tile's tile fall-back) and of launch_wgf_taps / launch_wgf_tile / plan_wgf (csrc/conv_wgrad_fast.h:
-    MAXT, MB, CIT, the 4x32 / 4x16 choice and its LDS / prefetch-round limits), single_wgrad_ok (csrc/conv_wgrad_single.h)."""
-    env = dict(c.env, **(env or {}))
-    bf = isbf(dtype)
-    V = 8 if bf else 4
-    Cin, Cout = cin_of(c, dtype), c.Cout
-    _, ldx = R.layout(c.lx, Cin)
-    _, ldy = R.layout(c.ly, Cout)
-    vec_x, vec_dy = ldx % V == 0 and _addr_ok(c.lx, dtype, 16), ldy % V == 0 and _addr_ok(c.ly, dtype, 16)
-    kh, kw, kd, s, d, T = c.kh, c.kw, c.kd, c.stride, c.dil, c.kh * c.kw
-    in_scale, no_thin = c.pro is not None, "SDHIP_CONV_NO_THIN" in env
-    nq = cdiv(Cin, 8 * V)
-    maxt = 9 if T <= 9 else 25
-    tpb = cdiv(T, cdiv(T, maxt))
-    flat = kd == 1 and c.D == 1 and c.Do == 1
-    if (Cout == 1 and Cin <= V and vec_x and s == 1 and flat and not in_scale and T <= 25 and
-            c.Ho == c.H + 2 * c.pad_t - d * (kh - 1) and c.Wo == c.W + 2 * c.pad_l - d * (kw - 1) and not no_thin):
-        return "thin"
-    if bf and Cout == 1 and 8 < Cin <= 32 and T * kd <= 32 and s == 1 and d == 1 and c.sd == 1 and vec_x and not in_scale and not c.dbias and not no_thin:
-        return "single"
-    if bf and Cin == 64 and Cout <= 32 and kh == 3 and kw == 3 and s == 1 and d == 1 and c.sd == 1 and kd == 3 and not in_scale and not c.dbias and c.Wo >= 24 and vec_x:
-        return "half32"
-    if bf and vec_x and vec_dy and "SDHIP_WGRAD_GENERIC" not in env:
-        if (Cin <= 32 and Cout <= 32 and kh == 3 and kw == 3 and s == 1 and d == 1 and c.sd == 1 and kd in (1, 3) and not in_scale and not c.dbias and
-                c.Wo >= 24):
-            return "half32"
-        dmax = not in_scale
-
-        def fits(TH, TW, MAXT, qb=0):
-            IH, IW = (TH - 1) * s + (kh - 1) * d + 1, (TW - 1) * (qb if qb else s) + ((qb if qb else kw) - 1) * d + 1
-            hr = cdiv(IH * ((IW + 15) & ~15), 64)
-            if 2 * (hr * 8192 + TH * TW * 128) > 160 * 1024:
-                return False
-            return dmax or hr <= ((TH * TW) // 64 if MAXT == 1 else 5)
-        pack_pays = Cout >= 256 or c.B * c.H * c.W >= 100000 or "SDHIP_WGRAD_FORCE_PACK" in env
-        if (T == 1 and flat and s == 1 and c.pad_t == 0 and c.pad_l == 0 and nq >= 2 and Cout > 32 and "SDHIP_WGRAD_NO_PACK" not in env and pack_pays):
-            qb = 4 if nq >= 3 else 2
-            IWp = ((15 * qb + (qb - 1) + 1) + 15) & ~15
-            if fits(4, 16, 4, qb) and not (IWp % 64 and 64 % IWp):
-                return "fast(packed x%d, %s)" % (qb, "dma" if dmax else "register")
-        narrow, half = Cout <= 32, Cin <= 32
-        if T == 1:
-            MAXT, MB, CIT = 1, 32 if narrow else 64, 4
-        elif tpb <= 9:
-            MAXT, MB, CIT = 9, 32 if narrow else 64, 2 if half else 4
+def chosen(c, dtype, env=None, entry="fwd", **over):
+    """Name of the kernel the library's own dispatch takes for the case (sdhip_last_path after a dry call, which launches
+    nothing and needs no GPU): entry 'fwd' = sdhip_conv2d_fwd with the arguments of gpu_fwd, 'wgrad' = sdhip_conv2d_wgrad
+    with those of gpu_wgrad, 'add' = sdhip_conv2d_fwd_add, 'bnbwd' = sdhip_conv2d_fwd_bnbwd (over: addend, mode; u and the
+    addend in the case's layouts lu / la, dense if it has none).  The operands sit where the case's layouts put them in
+    256-byte-aligned slabs.  'rejected': the entry point refused the arguments (e.g. bnbwd in f32)."""
+    from pmt_learning_for_semantic_segmentation_and_disparity_amd import _lib
+    Cin = cin_of(c, dtype)
+    x, ldx = _slice_addr(0, c.lx, Cin, dtype)
+    y, ldy = _slice_addr(1, c.ly, c.Cout, dtype)
+    tab = [ctypes.c_void_p(BASE_ADDR * i) for i in range(3, 9)]      # packed weights, tables, statistics: aligned as allocated
+    sc, sh = (tab[1], tab[2]) if c.pro else (None, None)
+    with diag_switches(**dict(c.env, **(env or {}))), _lib.dispatch_dry():
+        if entry == "fwd":
+            nrep, strided = c.stats or (1, 0)
+            args = (x, tab[0], y, tab[3] if c.bias else None, sc, sh, tab[4] if c.stats else None, (c.Cout + 5 if strided else c.Cout) if c.stats else 0, nrep,
+                    c.B, c.H, c.W, Cin, ldx, c.Ho, c.Wo, c.Cout, ldy, c.kh, c.kw, c.stride, c.dil, c.pad_t, c.pad_l,
+                    c.D, c.Do, c.kd, c.sd, c.pad_d, 1 if c.pro == "relu" else 0, c.groups, c.act, c.acc, code(dtype), None)
+        elif entry == "wgrad":
+            args = (x, y, tab[0], tab[3] if c.dbias else None, sc, sh, c.B, c.H, c.W, Cin, ldx, c.Ho, c.Wo, c.Cout, ldy, c.kh, c.kw, c.stride, c.dil,
+                    c.pad_t, c.pad_l, c.D, c.Do, c.kd, c.sd, c.pad_d, 1 if c.pro == "relu" else 0, c.groups, c.prezeroed, code(dtype), None)
         else:
-            MAXT, MB, CIT = 25, 32, 2 if half else 4
-        for TH, TW in ((4, 32), (4, 16)):
-            if TW == 32 and c.Wo < 24:
-                continue
-            if fits(TH, TW, MAXT):
-                return "fast(taps %d, mb %d, cit %d, %dx%d, %s)" % (MAXT, MB, CIT, TH, TW, "dma" if dmax else "register")
-    MB = 64 if (bf and maxt == 9) else 32
-    for TH, TW in (((8, 32), (4, 32)) if c.Wo >= 24 else ()) + ((4, 16),):
-        IH, IW = (TH - 1) * s + (kh - 1) * d + 1, (TW - 1) * s + (kw - 1) * d + 1
-        if IH * IW * 128 + TH * TW * 128 <= 160 * 1024:
-            return "generic(taps %d, mb %d, %dx%d)" % (maxt, MB, TH, TW)
-    return "unsupported"
+            u, ldu = _slice_addr(9, c.get("lu", "dense"), c.Cout, dtype)
+            add, ldadd = _slice_addr(10, c.get("la", "dense"), c.Cout, dtype)
+            tail = (c.B, c.H, c.W, Cin, ldx, c.Ho, c.Wo, c.Cout, ldy, c.kh, c.kw)
+            if entry == "add":
+                args = (x, tab[0], y, add, ldadd) + tail + (c.pad_t, c.pad_l, code(dtype), None)
+            else:       # the data gradient with the BatchNorm-backward epilogue, sums [32][G][2][Cout]
+                args = (x, tab[0], y, tab[4], c.Cout, 32, u, ldu, tab[1], tab[2], add if over.get("addend") else None, ldadd if over.get("addend") else 0) + \
+                    tail + (c.dil, c.pad_t, c.pad_l, c.groups, over.get("mode", 0), code(dtype), None)
+        rc = getattr(_lib._lib, {"fwd": "sdhip_conv2d_fwd", "wgrad": "sdhip_conv2d_wgrad", "add": "sdhip_conv2d_fwd_add", "bnbwd": "sdhip_conv2d_fwd_bnbwd"}[entry])(*args)
+        return _lib.last_path() if rc in (0, _lib.ERR_UNSUPPORTED) else "rejected"
+
+
+def last_path():
+    """Name of the kernel the last (real or dry) convolution call on this thread ran on."""
+    from pmt_learning_for_semantic_segmentation_and_disparity_amd import _lib
+    return _lib.last_path()
+
+
+def family(path):
+    return path.split("(")[0]
+
+
+def tile_of(path):
+    """(th, tw) of a fast(...) / generic(...) name: the tile whose values the statistics epilogue sums in f32."""
+    th, tw = path.split("(")[1].split(",")[0].split("x")
+    return int(th), int(tw)
 
 
 GENERIC_ENV = {"SDHIP_CONV_GENERIC": "1"}
@@ -387,11 +274,11 @@ def test_case_tables_reach_every_branch():
     for dtype in (F32, BF16):
         seen = set()
         for c in FWD:
-            p, _ = fwd_path(c, dtype)
+            p = chosen(c, dtype)
             assert p.startswith(c.want), (c.name, dtype, p)
             seen.add(p)
             if c.want == "fast":
-                pg, _ = fwd_path(c, dtype, GENERIC_ENV)
+                pg = chosen(c, dtype, GENERIC_ENV)
                 assert pg.startswith("generic"), (c.name, dtype, pg)
                 seen.add(pg)
         print("\n".join(sorted(seen)))
@@ -404,12 +291,12 @@ def test_case_tables_reach_every_branch():
                     assert any(p.startswith("fast(" + tile) and ks in p and stg in p for p in seen), (dtype, tile, ks, stg)
         seen = set()
         for c in WG:
-            p = wg_path(c, dtype)
+            p = chosen(c, dtype, entry="wgrad")
             want = c.want if isbf(dtype) else "generic"            # f32 always runs the generic tile kernel
             assert p.startswith(want), (c.name, dtype, p)
             seen.add(p)
             if want == "fast":
-                pg = wg_path(c, dtype, WGENERIC_ENV)
+                pg = chosen(c, dtype, WGENERIC_ENV, entry="wgrad")
                 assert pg.startswith("generic"), (c.name, pg)
                 seen.add(pg)
         print("\n".join(sorted(seen)))
@@ -700,7 +587,7 @@ def test_comparator_rejects_wrong_references(dtype):
             d = draw(c, dtype)
             y, _ = fwd_ref(c, dtype, d)
             ys = quant(y, dtype)
-            _rej(name + " unrounded statistics", CR.conv_stats(y, c.groups), CR.conv_stats(ys, c.groups), stats_bound(ys, c.groups, fwd_path(c, dtype)[1]))
+            _rej(name + " unrounded statistics", CR.conv_stats(y, c.groups), CR.conv_stats(ys, c.groups), stats_bound(ys, c.groups, tile_of(chosen(c, dtype))))
     wg = {c.name: c for c in WG}
     for name in ("img9x19", "k3s2_9x19", "lx_ldodd", "pro_G2"):                        # weight gradient: the last pixel row left out
         c = wg[name]
@@ -884,7 +771,7 @@ def gpu_fwd(c, dtype, d, env=None):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("name", [c.name for c in FWD])
 def test_conv2d_fwd(name, dtype):
-    """sdhip_conv2d_fwd on the kernel the dispatch mirror names, and every fast case a second time on the generic kernel
+    """sdhip_conv2d_fwd on the kernel the dispatch names (and then ran on), and every fast case a second time on the generic kernel
     (SDHIP_CONV_GENERIC), against the same reference: y within the bound with no element excluded, the slab around y
     untouched, no NaN from the NaN lanes [Cin, ld) of x or from beyond the coefficient tables, the statistics the sums of the
     stored y."""
@@ -892,14 +779,15 @@ def test_conv2d_fwd(name, dtype):
     d = draw(c, dtype)
     ref, bound = fwd_ref(c, dtype, d)
     for env in ([{}, GENERIC_ENV] if c.want == "fast" else [{}]):
-        path, tile = fwd_path(c, dtype, env)
+        path = chosen(c, dtype, env)
         y, sb = gpu_fwd(c, dtype, d, env)
+        assert last_path() == path and family(path) == ("generic" if env else c.want), (name, env, path, last_path())
         label = "fwd %s %s" % (name, path)
         got = y.np()
         check(label, got, ref, bound)
         assert y.pads_intact(), label
         if sb:
-            check_stats(label + " stats", sb, got, c.groups, tile)
+            check_stats(label + " stats", sb, got, c.groups, tile_of(path))
 
 
 # =========================================================================== GPU: sdhip_conv2d_fwd_phase
@@ -1022,9 +910,9 @@ FORCE_PACK, NO_PACK = {"SDHIP_WGRAD_FORCE_PACK": "1"}, {"SDHIP_WGRAD_NO_PACK": "
 
 def test_packed_wgrad_cases_reach_the_chunk_packed_kernel():
     for c in WGPACK:
-        assert wg_path(c, BF16, FORCE_PACK).startswith("fast(packed x%d" % (2 if c.Cin == 128 else 4)), c.name
-        assert wg_path(c, BF16, NO_PACK).startswith("fast(taps 1, mb 64"), c.name
-        assert wg_path(c, BF16).startswith("fast(taps 1, mb 64"), c.name      # the heuristic keeps these small maps off the packed kernel
+        assert chosen(c, BF16, FORCE_PACK, entry="wgrad").startswith("fast(packed x%d" % (2 if c.Cin == 128 else 4)), c.name
+        assert chosen(c, BF16, NO_PACK, entry="wgrad").startswith("fast(taps 1, mb 64"), c.name
+        assert chosen(c, BF16, entry="wgrad").startswith("fast(taps 1, mb 64"), c.name      # the heuristic keeps these small maps off the packed kernel
 
 
 def gpu_wgrad(c, dtype, d, env=None):
@@ -1070,15 +958,18 @@ def check_wgrad(label, c, dtype, d, res, refs):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("name", [c.name for c in WG])
 def test_conv2d_wgrad(name, dtype):
-    """sdhip_conv2d_wgrad on the kernel the dispatch mirror names (bf16 fast cases again under SDHIP_WGRAD_GENERIC), then
+    """sdhip_conv2d_wgrad on the kernel the dispatch names and then ran on (bf16 fast cases again under SDHIP_WGRAD_GENERIC), then
     sdhip_conv_unpack_wgrad: the packed buffer (pad rows and channel tail exactly zero, nothing written past it) and the
     (M, K, T) gradient against the reference, dbias, prezeroed 0 on a NaN-filled buffer and 1 on a zeroed one."""
     c = WGBY[name]
     d = draw(c, dtype)
     refs = wg_ref(c, dtype, d)
-    fast = wg_path(c, dtype).startswith("fast")
-    for env in ([{}, WGENERIC_ENV] if fast else [{}]):
-        check_wgrad("wgrad %s %s" % (name, wg_path(c, dtype, env)), c, dtype, d, gpu_wgrad(c, dtype, d, env), refs)
+    want = c.want if isbf(dtype) else "generic"                    # f32 always runs the generic tile kernel
+    for env in ([{}, WGENERIC_ENV] if want == "fast" else [{}]):
+        path = chosen(c, dtype, env, entry="wgrad")
+        res = gpu_wgrad(c, dtype, d, env)
+        assert last_path() == path and family(path) == ("generic" if env else want), (name, env, path, last_path())
+        check_wgrad("wgrad %s %s" % (name, path), c, dtype, d, res, refs)
 
 
 @pytest.mark.gpu
@@ -1090,4 +981,7 @@ def test_conv2d_wgrad_chunk_packed(name):
     d = draw(c, BF16)
     refs = wg_ref(c, BF16, d)
     for env in (FORCE_PACK, NO_PACK):
-        check_wgrad("wgrad %s %s" % (name, wg_path(c, BF16, env)), c, BF16, d, gpu_wgrad(c, BF16, d, env), refs)
+        path = chosen(c, BF16, env, entry="wgrad")
+        res = gpu_wgrad(c, BF16, d, env)
+        assert last_path() == path and path.startswith("fast(packed" if env is FORCE_PACK else "fast(taps 1"), (name, path, last_path())
+        check_wgrad("wgrad %s %s" % (name, path), c, BF16, d, res, refs)

@@ -2,9 +2,10 @@
 blocks on the 1/4-resolution maps), through sdhip_conv2d_fwd (plain and with the statistics epilogue) and
 sdhip_conv2d_fwd_bnbwd mode 0 (the data gradient with the BatchNorm-backward sums, with and without an addend).
 
-Without a GPU: mid_taken() mirrors path_mid of csrc/conv_fwd.hip term by term; it names every case below, rejects each
-single violation of the predicate and every case of the tables of test_conv_kernels.py (whose tile assumptions therefore
-hold), and says which of the headline step's shapes the path takes.
+Without a GPU: the library's own dispatch, asked in dry mode (test_conv_kernels.chosen: sdhip_dispatch_dry / sdhip_last_path),
+takes the kernel for every case below in every form, declines each single violation of path_mid's predicate, one step past
+each of its limits (as shipped and as set by SDHIP_TUNE_MID_*) and every case of the tables of test_conv_kernels.py, and
+takes those of the headline step's shapes it was measured faster on.
 With a GPU: the operands are channel slices of NaN-filled slabs, so a NaN in y or in a sum is a padding lane, a dead pixel
 or a channel past the slice that reached an MFMA or an epilogue.  The kernel keeps the halo-tile kernel's reduction order
 per output element, so y must have the BITS of the same call under SDHIP_CONV_NO_MID=1; next to that it is held against
@@ -34,11 +35,10 @@ import convops_ref as CR  # noqa: E402
 import rowops_ref as R  # noqa: E402
 import test_conv_kernels as K  # noqa: E402
 from rowops_ref import check, diag_switches  # noqa: E402
-from test_conv_kernels import BF16, F32, P, StatBuf, Table, Vol, bits, check_stats, code, dev, draw, fwd_ref, gpu_fwd, isbf, mk, run  # noqa: E402
+from test_conv_kernels import BF16, F32, P, StatBuf, Table, Vol, bits, check_stats, code, dev, draw, fwd_ref, gpu_fwd, mk, run  # noqa: E402
 
 NO_MID = {"SDHIP_CONV_NO_MID": "1"}
 LIFT = {"SDHIP_TUNE_MID_MIN_MAP": "1"}        # the tests' maps are below kMidMinMap
-MID_MIN_MAP, MID_MAX_MAP, MID_MAX_WG = 8192, 8192, 256     # kMidMinMap, kMidMaxMap, kMidMaxWG of csrc/conv_mid.h
 SLICE = (64, 160)       # channels [64, 128) of a 160-channel slab
 
 
@@ -53,73 +53,58 @@ CASES = [md("map8x32"), md("map16x64", H=16, W=64), md("map9x33", H=9, W=33), md
 BYNAME = {c.name: c for c in CASES}
 
 
-def _lay(lay, C):
-    return R.layout(lay, C) if isinstance(lay, str) else lay
-
-
-def mid_taken(c, dtype, env=None, bx=False, addend=False, mode=0):
-    """Mirror of path_mid (csrc/conv_fwd.hip)."""
-    env = dict(c.env, **(env or {}))
-    Cin = K.cin_of(c, dtype)
-    (kx, ldx), (ky, ldy) = _lay(c.lx, Cin), _lay(c.ly, c.Cout)
-    min_map = int(env.get("SDHIP_TUNE_MID_MIN_MAP", 0)) or MID_MIN_MAP
-    max_map = int(env.get("SDHIP_TUNE_MID_MAX_MAP", 0)) or MID_MAX_MAP
-    max_wg = int(env.get("SDHIP_TUNE_MID_MAX_WG", 0)) or MID_MAX_WG
-    return bool(isbf(dtype) and c.kh == 3 and c.kw == 3 and c.kd == 1 and c.D == 1 and c.Do == 1 and c.stride == 1 and c.dil == 1 and
-                c.pad_t == 1 and c.pad_l == 1 and c.Ho == c.H and c.Wo == c.W and Cin == 64 and c.Cout == 64 and
-                c.pro is None and not c.bias and c.act == 0 and not c.acc and (mode == 0 if bx else not addend) and
-                min_map <= c.H * c.W <= max_map and c.B * K.cdiv(c.H, 8) * K.cdiv(c.W, 32) <= max_wg and
-                ldx % 8 == 0 and (kx * 2) % 16 == 0 and ldy % 4 == 0 and (ky * 2) % 8 == 0 and c.H * c.W * ldx < 2 ** 31 and
-                "SDHIP_CONV_NO_MID" not in env and "SDHIP_CONV_GENERIC" not in env)
+def on_mid(c, dtype, env=None, bx=False, addend=False, mode=0):
+    """Does the dispatch (csrc/conv_fwd.hip: path_mid) run the case on conv_mid.h?  bx: through sdhip_conv2d_fwd_bnbwd;
+    addend alone: sdhip_conv2d_fwd_add; neither: sdhip_conv2d_fwd."""
+    return K.chosen(c, dtype, env, entry="bnbwd" if bx else "add" if addend else "fwd", addend=addend, mode=mode) == "mid"
 
 
 def test_mid_predicate():
     for c in CASES:
         for kw in (dict(), dict(bx=True), dict(bx=True, addend=True)):
-            assert mid_taken(c, BF16, **kw), c.name
-            assert not mid_taken(c, F32, **kw), c.name
-            assert not mid_taken(c, BF16, NO_MID, **kw) and not mid_taken(c, BF16, K.GENERIC_ENV, **kw), c.name
-        assert not mid_taken(c, BF16, bx=True, addend=True, mode=1) and not mid_taken(c, BF16, addend=True), c.name
+            assert on_mid(c, BF16, **kw), c.name
+            assert not on_mid(c, F32, **kw), c.name
+            assert not on_mid(c, BF16, NO_MID, **kw) and not on_mid(c, BF16, K.GENERIC_ENV, **kw), c.name
+        assert not on_mid(c, BF16, bx=True, addend=True, mode=1) and not on_mid(c, BF16, addend=True), c.name
         stats = md(c.name, **dict({k: c[k] for k in ("B", "H", "W", "groups", "lx", "ly")}, stats=(2, 1)))
-        assert mid_taken(stats, BF16), c.name
+        assert on_mid(stats, BF16), c.name
     for tag, kw in (("k1", dict(kh=1, kw=1)), ("k5", dict(kh=5, kw=5)), ("stride2", dict(stride=2)), ("dil2", dict(dil=2)),
                     ("cin32", dict(Cin=32)), ("cin128", dict(Cin=128)), ("cout32", dict(Cout=32)), ("cout128", dict(Cout=128)),
                     ("pro", dict(pro="relu")), ("bias", dict(bias=1)), ("act", dict(act=1)), ("acc", dict(acc=1)),
                     ("lx_ldodd", dict(lx="ldodd")), ("ly_ldodd", dict(ly="ldodd")), ("lx_misal", dict(lx="misal")), ("ly_misal", dict(ly="misal")),
                     ("vol", dict(D=4, kd=3, pad_d=1))):
-        assert not mid_taken(md(tag, **kw), BF16), tag
+        assert not on_mid(md(tag, **kw), BF16), tag
     pad0 = md("pad0")
     pad0.update(pad_t=0, pad_l=0)
-    assert not mid_taken(pad0, BF16)
+    assert not on_mid(pad0, BF16)
     # one step past each limit, with the limits as shipped (no override) and as set
-    assert mid_taken(md("at", B=8, H=64, W=128, env={}), BF16)
-    assert not mid_taken(md("below", B=8, H=64, W=127, env={}), BF16) and not mid_taken(md("above", B=7, H=64, W=129, env={}), BF16)
-    assert not mid_taken(md("grid", B=9, H=64, W=128, env={}), BF16)
-    assert mid_taken(md("wg", B=MID_MAX_WG), BF16) and not mid_taken(md("wg+1", B=MID_MAX_WG + 1), BF16)
-    assert mid_taken(md("max", env={"SDHIP_TUNE_MID_MIN_MAP": "1", "SDHIP_TUNE_MID_MAX_MAP": "256"}), BF16)
-    assert not mid_taken(md("max+1", H=1, W=257, env={"SDHIP_TUNE_MID_MIN_MAP": "1", "SDHIP_TUNE_MID_MAX_MAP": "256"}), BF16)
-    assert not mid_taken(md("min-1", H=1, W=255, env={"SDHIP_TUNE_MID_MIN_MAP": "256"}), BF16)
+    assert on_mid(md("at", B=8, H=64, W=128, env={}), BF16)
+    assert not on_mid(md("below", B=8, H=64, W=127, env={}), BF16) and not on_mid(md("above", B=7, H=64, W=129, env={}), BF16)
+    assert not on_mid(md("grid", B=9, H=64, W=128, env={}), BF16)
+    assert on_mid(md("wg", B=256), BF16) and not on_mid(md("wg+1", B=257), BF16)
+    assert on_mid(md("max", env={"SDHIP_TUNE_MID_MIN_MAP": "1", "SDHIP_TUNE_MID_MAX_MAP": "256"}), BF16)
+    assert not on_mid(md("max+1", H=1, W=257, env={"SDHIP_TUNE_MID_MIN_MAP": "1", "SDHIP_TUNE_MID_MAX_MAP": "256"}), BF16)
+    assert not on_mid(md("min-1", H=1, W=255, env={"SDHIP_TUNE_MID_MIN_MAP": "256"}), BF16)
     # the headline step (8 images, one group): the 64 -> 64 layers on the 64x128 maps are taken in every form; the 32x64 maps,
     # the 128 -> 64 c1 layers, Cout 128 and a batch of 16 (512 workgroups) are not
     for kw in (dict(), dict(bx=True), dict(bx=True, addend=True)):
-        assert mid_taken(md("quarter", B=8, H=64, W=128, env={}), BF16, **kw)
-        assert not mid_taken(md("eighth", B=8, H=32, W=64, env={}), BF16, **kw)
-        assert not mid_taken(md("c1", B=8, H=64, W=128, Cin=128, env={}), BF16, **kw)
-        assert not mid_taken(md("downup3", B=8, H=64, W=128, Cout=128, env={}), BF16, **kw)
-        assert not mid_taken(md("B16", B=16, H=64, W=128, env={}), BF16, **kw)
-    assert mid_taken(md("quarter_stats", B=8, H=64, W=128, stats=(32, 0), env={}), BF16)
-    # the tables of test_conv_kernels.py: none of their cases is taken, with or without the lifted limits, so fwd_path's
-    # tile assumptions hold for them
+        assert on_mid(md("quarter", B=8, H=64, W=128, env={}), BF16, **kw)
+        assert not on_mid(md("eighth", B=8, H=32, W=64, env={}), BF16, **kw)
+        assert not on_mid(md("c1", B=8, H=64, W=128, Cin=128, env={}), BF16, **kw)
+        assert not on_mid(md("downup3", B=8, H=64, W=128, Cout=128, env={}), BF16, **kw)
+        assert not on_mid(md("B16", B=16, H=64, W=128, env={}), BF16, **kw)
+    assert on_mid(md("quarter_stats", B=8, H=64, W=128, stats=(32, 0), env={}), BF16)
+    # the tables of test_conv_kernels.py: none of their cases is taken, with or without the lifted limits
     taken = {}
     for dtype in (F32, BF16):
         for c in K.FWD:
-            taken[(c.name, dtype)] = mid_taken(c, dtype) or mid_taken(c, dtype, LIFT)
+            taken[(c.name, dtype)] = on_mid(c, dtype) or on_mid(c, dtype, LIFT)
         for Cin in (32, 96, 160):        # the shapes of test_conv_kernels.test_conv2d_fwd_bnpro
             for kh in (1, 3):
-                taken[("bnpro%d_%d" % (Cin, kh), dtype)] = mid_taken(mk("bnpro", kh=kh, kw=kh, Cin=Cin, Cout=24, pro="relu", lx="slab8", ly="slab8", stats=(3, 1)), dtype, LIFT)
+                taken[("bnpro%d_%d" % (Cin, kh), dtype)] = on_mid(mk("bnpro", kh=kh, kw=kh, Cin=Cin, Cout=24, pro="relu", lx="slab8", ly="slab8", stats=(3, 1)), dtype, LIFT)
     assert not any(taken.values()), sorted(k for k, v in taken.items() if v)
     # the existing GPU tests with 3x3 64 -> 64 shapes stay on the kernels they were written for (maps below kMidMinMap)
-    assert not mid_taken(md("test_band", B=3, H=48, W=64, env={}), BF16) and not mid_taken(md("test_conv", B=2, H=20, W=36, env={}), BF16, bx=True)
+    assert not on_mid(md("test_band", B=3, H=48, W=64, env={}), BF16) and not on_mid(md("test_conv", B=2, H=20, W=36, env={}), BF16, bx=True)
 
 
 # =========================================================================== GPU
@@ -140,8 +125,9 @@ def test_conv_mid_plain(name):
     d, ref, bound = _problem(name)
     ybits = {}
     for tag, env in (("mid", {}), ("fast", NO_MID)):
-        assert mid_taken(c, BF16, env) == (tag == "mid")
+        assert on_mid(c, BF16, env) == (tag == "mid")
         y, _ = gpu_fwd(c, BF16, d, env)
+        assert K.family(K.last_path()) == tag, (name, tag, K.last_path())
         check("mid plain %s %s" % (name, tag), y.np(), ref, bound)
         assert y.pads_intact(), (name, tag)
         ybits[tag] = bits(y.v)
@@ -158,8 +144,9 @@ def test_conv_mid_stats(name):
     d, ref, bound = _problem(name)
     ybits, sbits = {}, {}
     for tag, env in (("mid", {}), ("fast", NO_MID), ("mid again", {})):
-        assert mid_taken(c, BF16, env) == (tag != "fast")
+        assert on_mid(c, BF16, env) == (tag != "fast")
         y, sb = gpu_fwd(c, BF16, d, env)
+        assert K.family(K.last_path()) == tag.split()[0], (name, tag, K.last_path())
         label = "mid stats %s %s" % (name, tag)
         got = y.np()
         check(label, got, ref, bound)
@@ -201,8 +188,9 @@ def test_conv_mid_bnbwd(name, addend):
     sh = K.f32(rng.standard_normal((G, 64)) * 0.3)
     out = {}
     for tag, env in (("mid", {}), ("fast", NO_MID)):
-        assert mid_taken(c, BF16, env, bx=True, addend=bool(addend)) == (tag == "mid")
+        assert on_mid(c, BF16, env, bx=True, addend=bool(addend)) == (tag == "mid")
         y, sb = gpu_bnbwd(c, d, u, sc, sh, add, env)
+        assert K.family(K.last_path()) == tag, (name, tag, K.last_path())
         label = "mid bnbwd %s add%d %s" % (name, addend, tag)
         ys = y.np()
         if addend:

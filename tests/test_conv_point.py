@@ -2,8 +2,9 @@
 conv1 of the DenseNet bottlenecks), through sdhip_conv2d_fwd (given in_scale / in_shift) and sdhip_conv2d_fwd_bnpro (the
 consumer-side BatchNorm finalize), against the float64 references and bounds of tests/test_conv_kernels.py.
 
-Without a GPU: point_taken() mirrors path_point of csrc/conv_fwd.hip; it names every case below, rejects each single
-violation of the predicate and every case of the tables of test_conv_kernels.py (whose tile assumptions therefore hold).
+Without a GPU: the library's own dispatch, asked in dry mode (test_conv_kernels.chosen: sdhip_dispatch_dry / sdhip_last_path),
+takes the kernel for every case below, declines each single violation of path_point's predicate and every case of the
+tables of test_conv_kernels.py.
 With a GPU: tensors are channel slices of NaN-filled slabs (x inside a 1024-channel slab as in a dense block: a NaN in y is
 a lane past Cin or a pixel row past the image that reached an MFMA), shapes are the smallest at which the kernel takes
 another path: a k-step tail inside a 64-channel weight row (160, 288, 992), fewer k-steps than waves (128, 160), uneven
@@ -45,43 +46,31 @@ CASES += [pt("map3x5", H=3, W=5, Cin=160, lx="slab8"), pt("map5x13", H=5, W=13, 
 BYNAME = {c.name: c for c in CASES}
 
 
-def _lay(lay, C):
-    return R.layout(lay, C) if isinstance(lay, str) else lay
-
-
-def point_taken(c, dtype, env=None):
-    """Mirror of path_point (csrc/conv_fwd.hip)."""
-    env = dict(c.env, **(env or {}))
-    Cin = K.cin_of(c, dtype)
-    (kx, ldx), (ky, ldy) = _lay(c.lx, Cin), _lay(c.ly, c.Cout)
-    return bool(isbf(dtype) and c.kh == 1 and c.kw == 1 and c.kd == 1 and c.D == 1 and c.Do == 1 and c.stride == 1 and
-                c.pad_t == 0 and c.pad_l == 0 and c.Ho == c.H and c.Wo == c.W and c.pro is not None and c.stats is not None and not c.bias and c.act == 0 and
-                not c.acc and 128 <= Cin <= 1024 and Cin % 8 == 0 and c.Cout % 32 == 0 and c.Cout <= 256 and c.B * c.H * c.W <= 32768 and c.H * c.W <= 512 and
-                c.B * K.cdiv(c.H * c.W, 64) * (c.Cout // 32) <= 512 and
-                ldx % 8 == 0 and (kx * 2) % 16 == 0 and ldy % 4 == 0 and (ky * 2) % 8 == 0 and c.H * c.W * ldx < 2 ** 31 and
-                "SDHIP_CONV_NO_POINT" not in env and "SDHIP_CONV_GENERIC" not in env)
+def on_point(c, dtype, env=None):
+    """Does the dispatch of sdhip_conv2d_fwd (csrc/conv_fwd.hip: path_point) run the case on conv_point.h?"""
+    return K.chosen(c, dtype, env) == "point"
 
 
 def test_point_predicate():
     for c in CASES:
-        assert point_taken(c, BF16), c.name
-        assert not point_taken(c, F32), c.name
-        assert not point_taken(c, BF16, NO_POINT) and not point_taken(c, BF16, K.GENERIC_ENV), c.name
+        assert on_point(c, BF16), c.name
+        assert not on_point(c, F32), c.name
+        assert not on_point(c, BF16, NO_POINT) and not on_point(c, BF16, K.GENERIC_ENV), c.name
     for tag, kw in (("cin96", dict(Cin=96)), ("cout24", dict(Cout=24)), ("cout136", dict(Cout=136)), ("k3", dict(kh=3, kw=3)),
                     ("stride2", dict(stride=2)), ("nopro", dict(pro=None)), ("acc", dict(acc=1)), ("bias", dict(bias=1)),
                     ("ldodd", dict(lx="ldodd")), ("cin1032", dict(Cin=1032, lx="dense")), ("pixels", dict(B=4, H=128, W=128)),
                     ("act", dict(act=1)), ("nostats", dict(stats=None)), ("ly_ldodd", dict(ly="ldodd")), ("lx_misal", dict(lx="misal"))):
-        assert not point_taken(pt(tag, **kw), BF16), tag
-    assert point_taken(pt("block3", B=16, H=16, W=32, Cin=992), BF16)                  # 512 workgroups: the limit
-    assert not point_taken(pt("block2", B=16, H=32, W=64, Cin=480), BF16)              # 2048
-    assert not point_taken(pt("transition3", B=16, H=16, W=32, Cin=1024, Cout=512), BF16)
-    assert not point_taken(pt("cout512", Cin=1024, Cout=512), BF16) and not point_taken(pt("map32x32", H=32, W=32), BF16)
+        assert not on_point(pt(tag, **kw), BF16), tag
+    assert on_point(pt("block3", B=16, H=16, W=32, Cin=992), BF16)                  # 512 workgroups: the limit
+    assert not on_point(pt("block2", B=16, H=32, W=64, Cin=480), BF16)              # 2048
+    assert not on_point(pt("transition3", B=16, H=16, W=32, Cin=1024, Cout=512), BF16)
+    assert not on_point(pt("cout512", Cin=1024, Cout=512), BF16) and not on_point(pt("map32x32", H=32, W=32), BF16)
     for dtype in (F32, BF16):
         for c in K.FWD:
-            assert not point_taken(c, dtype), c.name
+            assert not on_point(c, dtype), c.name
         for Cin in (32, 96, 160):        # the shapes of test_conv_kernels.test_conv2d_fwd_bnpro
             for kh in (1, 3):
-                assert not point_taken(mk("bnpro", kh=kh, kw=kh, Cin=Cin, Cout=24, pro="relu", lx="slab8", ly="slab8"), dtype)
+                assert not on_point(mk("bnpro", kh=kh, kw=kh, Cin=Cin, Cout=24, pro="relu", lx="slab8", ly="slab8"), dtype)
 
 
 # =========================================================================== GPU: sdhip_conv2d_fwd with in_scale / in_shift
@@ -98,6 +87,7 @@ def test_conv_point_fwd(name):
     got, ybits = {}, {}
     for tag, env in (("point", {}), ("fast", NO_POINT), ("point again", {})):
         y, sb = gpu_fwd(c, BF16, d, env)
+        assert K.family(K.last_path()) == tag.split()[0], (name, tag, K.last_path())
         label = "point %s %s" % (name, tag)
         got[tag] = y.np()
         check(label, got[tag], ref, bound)
@@ -118,8 +108,6 @@ def test_conv_point_bnpro(Cin):
     dtype, kh, pad = BF16, 1, 0
     for (G, nrep, pend_nrep, running, out_stats) in BNPRO_COMBOS:
         d = draw_bnpro(kh, Cin, G, nrep, pend_nrep, running, dtype, Cout=128)
-        assert point_taken(mk("bnpro", kh=1, kw=1, B=d.B, H=d.H, W=d.W, Cin=Cin, Cout=128, pro="relu", groups=G, lx="slab8", ly="slab8",
-                              stats=(3, 1)), dtype)      # (the finalize form needs no statistics epilogue: the mirror speaks of the given-prologue form)
         c0 = Cin - 32
         r = CR.bnpro(d.x, d.w, d.in_stats, d.count, d.gamma, d.beta, d.rm0, d.rv0, EPS32, MOM32, G, d.pend, c0, pad, pad)
         S = r["in_stats"].sum(0)[:, :, :Cin] if pend_nrep else R.replica_sum(d.in_stats)
@@ -144,6 +132,7 @@ def test_conv_point_bnpro(Cin):
             rm.p if rm else None, rv.p if rv else None, P(outs[0], 32), P(outs[1], 32), P(outs[2], 32), P(outs[3], 32),
             ctypes.c_double(d.count), ctypes.c_float(EPS32), ctypes.c_float(MOM32),
             d.B, d.H, d.W, Cin, x.ld, d.H, d.W, d.Cout, y.ld, kh, kh, pad, pad, G, code(dtype))
+        assert K.last_path() == "point", (Cin, G, K.last_path())
         label = "point bnpro Cin%d G%d nrep%d pend%d" % (Cin, G, nrep, pend_nrep)
         for key, o in zip(("scale", "shift", "mean", "invstd"), outs):
             check(label + " " + key, o[8:8 + G * Cin].double().cpu().numpy().reshape(G, Cin), r[key], bf_[key])

@@ -15,8 +15,9 @@ Shapes are the smallest that reach each way the kernel can go wrong: channel tai
 (3x5: 15 of 64 rows real, 5x13: 64 + 1), two statistics groups with different coefficients (negative scales, shifts of
 either sign and |shift| >= 0.25: relu(shift) on a masked row would show), one and many slab shares per workgroup.
 
-gemm1x1_taken mirrors the branch's predicate in wg_fast (csrc/conv_wgrad.hip); wg_path of test_conv_kernels.py does not know
-the branch and names the kernel that runs under SDHIP_WGRAD_NO_GEMM for these shapes.
+Without a GPU: the library's own dispatch, asked in dry mode (test_conv_kernels.chosen: sdhip_dispatch_dry / sdhip_last_path),
+names "gemm1x1" for every case, another kernel in f32, under SDHIP_WGRAD_NO_GEMM and under each switch the branch stands
+aside for, and for each single violation of its predicate (wg_fast of csrc/conv_wgrad.hip, wgrad_gemm1x1_ok).
 """
 import os
 import sys
@@ -47,30 +48,25 @@ SPLIT = mk("split64x128", 4, 64, 128, 96)                                       
 BY = {c.name: c for c in CASES + [SPLIT]}
 
 
-def gemm1x1_taken(c, dtype, env=None):
-    """Mirror of the first 1x1 branch of wg_fast (csrc/conv_wgrad.hip) and of wgrad_gemm1x1_ok (csrc/conv_wgrad_gemm1x1.h)."""
-    env = dict(c.env, **(env or {}))
-    Cin = K.cin_of(c, dtype)
-    kx, ldx = c.lx if not isinstance(c.lx, str) else K.R.layout(c.lx, Cin)
-    ky, ldy = c.ly if not isinstance(c.ly, str) else K.R.layout(c.ly, c.Cout)
-    vec = ldx % 8 == 0 and ldy % 8 == 0 and kx % 8 == 0 and ky % 8 == 0
-    return (K.isbf(dtype) and vec and not any(s in env for s in STAND_ASIDE) and "SDHIP_WGRAD_NO_GEMM" not in env and
-            c.kh * c.kw == 1 and c.kd == 1 and c.D == 1 and c.Do == 1 and c.stride == 1 and c.pad_t == 0 and c.pad_l == 0 and
-            c.Ho == c.H and c.Wo == c.W and c.Cout % 128 == 0 and Cin >= 96 and Cin % 8 == 0 and c.pro is not None and not c.dbias)
+def on_gemm1x1(c, dtype, env=None):
+    """Does the dispatch of sdhip_conv2d_wgrad (csrc/conv_wgrad.hip: the GEMM branch of wg_fast) run the case on conv_wgrad_gemm1x1.h?"""
+    return K.chosen(c, dtype, env, entry="wgrad") == "gemm1x1"
 
 
-def test_predicate_mirror():
+def test_gemm1x1_predicate():
     for c in CASES + [SPLIT]:
-        assert gemm1x1_taken(c, BF16), c.name
-        assert not gemm1x1_taken(c, F32), c.name
-        assert not gemm1x1_taken(c, BF16, NO_GEMM), c.name
+        assert on_gemm1x1(c, BF16), c.name
+        assert not on_gemm1x1(c, F32), c.name
+        assert not on_gemm1x1(c, BF16, NO_GEMM), c.name
         for sw in STAND_ASIDE:
-            assert not gemm1x1_taken(c, BF16, {sw: "1"}), (c.name, sw)
+            assert not on_gemm1x1(c, BF16, {sw: "1"}), (c.name, sw)
     base = dict(B=4, H=16, W=32, Cin=128, Cout=128, kh=1, kw=1, pro="relu", groups=2)
-    assert gemm1x1_taken(K.mk("ok", **base), BF16)
+    assert on_gemm1x1(K.mk("ok", **base), BF16)
     for name, kw in (("cout64", dict(Cout=64)), ("cin64", dict(Cin=64)), ("t9", dict(kh=3, kw=3)), ("s2", dict(stride=2)),
                      ("nopro", dict(pro=None)), ("dbias", dict(dbias=1)), ("ldodd", dict(lx="ldodd")), ("cout136", dict(Cout=136))):
-        assert not gemm1x1_taken(K.mk(name, **dict(base, **kw)), BF16), name
+        assert not on_gemm1x1(K.mk(name, **dict(base, **kw)), BF16), name
+    for c in K.WG + K.WGPACK:      # the tables of test_conv_kernels.py stay on the kernels they were written for
+        assert not on_gemm1x1(c, BF16), c.name
 
 
 _REFS = {}
@@ -96,8 +92,10 @@ def test_gemm1x1_wgrad(name):
     c = BY[name]
     d, r = refs(c)
     new = K.gpu_wgrad(c, BF16, d)
+    assert K.last_path() == "gemm1x1", (name, K.last_path())
     K.check_wgrad("gemm1x1 %s" % name, c, BF16, d, new, r)
     old = K.gpu_wgrad(c, BF16, d, NO_GEMM)
+    assert K.family(K.last_path()) == "fast", (name, K.last_path())
     K.check_wgrad("gemm1x1 %s NO_GEMM" % name, c, BF16, d, old, r)
     K.check("gemm1x1 %s new vs old" % name, new[1], old[1], r[2])
 
@@ -121,7 +119,9 @@ def test_pixel_split_alone_and_grouped():
     c = SPLIT
     d, r = refs(c)
     K.check_wgrad("gemm1x1 split", c, BF16, d, K.gpu_wgrad(c, BF16, d), r)
+    assert K.last_path() == "gemm1x1", K.last_path()
     K.check_wgrad("gemm1x1 split NO_GEMM", c, BF16, d, K.gpu_wgrad(c, BF16, d, NO_GEMM), r)
+    assert K.family(K.last_path()) == "fast", K.last_path()
     L = _as_layer(c, d)
     dev = L["x"].device
     got = [G._run_single(L, dev)[0], G._run_group([L], dev, 0)[0][0], G._run_group([L], dev, 96)[0][0]]
